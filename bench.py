@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- whole-job throughput of the UPSNet per-image inference hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -38,7 +38,7 @@ PEAK_HBM_GBS = 8000.0           # HBM3E spec peak (6.3 TB/s achievable per the s
 
 
 def ensure_ranks(args):
-    """`--gpus N` means N ranks, one per GPU. Started plainly (no WORLD_SIZE in the environment) with N > 1, re-exec this very
+    """`--gpus N` means N ranks, one per GPU. Started plainly (no WORLD_SIZE in the environment) with N > 1, run this very
     command line under torch.distributed.run; started by a launcher, require that its world size IS N. Never measure fewer
     GPUs than the line will claim."""
     n = args.gpus
@@ -67,7 +67,35 @@ def ensure_ranks(args):
         ncpu = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
         env.setdefault('OMP_NUM_THREADS', str(max(1, min(16, ncpu // n))))
         sys.stdout.flush()
-        os.execvpe(cmd[0], cmd, env)
+        # a fresh child process, not an exec: this one has already opened the GPU runtime (device_count above)
+        import subprocess
+        sys.exit(subprocess.call(cmd, env=env))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out):
+    """The output dict of the last timed step (what a caller of the timed path receives) as out_dir/<name>.npy: floating tensors in
+    float32 (float64 stays float64), integer / boolean ones in float64 (exact). If they exceed 64 MB in all, each array above
+    1/8 of that is replaced by a fixed, seeded sample of its flattened elements (same shape -> same positions)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, t in sorted(out.items()):
+        if not torch.is_tensor(t):
+            continue
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in 'biu' else np.float32)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        for name, a in arrays.items():
+            if a.nbytes > DUMP_LIMIT_BYTES // 8:
+                k = DUMP_LIMIT_BYTES // 8 // a.itemsize
+                idx = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+                arrays[name] = a.reshape(-1)[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def roialign_microbench(H, W, n_iter=10):
@@ -166,6 +194,8 @@ def main():
                          '(the headline model predicts ~1 px offsets like a trained DCN; reported as roofline.deformable_wide_offsets)')
     ap.add_argument('--no-roialign', action='store_true',
                     help='skip the ROIAlign report (roofline.roialign: the launches of the sampled image + the isolated kernel on random ROIs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step (rank 0) as DIR/<name>.npy (float32 / float64, 64 MB at most)')
     args = ap.parse_args()
     steps_explicit = any(a == '--steps' or a.startswith('--steps=') for a in sys.argv[1:])
     ensure_ranks(args)
@@ -220,6 +250,11 @@ def main():
     ops.PROFILE['enabled'] = False
     res['model'].overlap_streams = overlap[0]
     rank, world = res['rank'], res['world']
+    dumped = None
+    if args.dump_outputs and rank == 0 and res['last_out'] is not None:
+        # now, before any other forward: on the graph path the outputs are views into the graph's buffers
+        torch.cuda.synchronize()
+        dumped = dump_outputs(args.dump_outputs, res['last_out'])
     if rank != 0:
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
@@ -229,7 +264,8 @@ def main():
     n_images = args.steps * world
     value = n_images / res['elapsed']
     net = sorted(res['net_times'])
-    p50_ms = 1000.0 * net[len(net) // 2]
+    # (fewer timed images than images in flight give no steady-state sample: the mean time per image then)
+    p50_ms = 1000.0 * (net[len(net) // 2] if net else res['elapsed'] / max(args.steps, 1))
     lat = sorted(res.get('latencies') or [0.0])
     lat_ms = 1000.0 * lat[len(lat) // 2]
 
@@ -600,6 +636,8 @@ def main():
                    'gather': res.get('gather')},
         'roofline': roofline, 'cpu_baseline': cpu_baseline, 'configs2': configs2,
     }
+    if dumped is not None:
+        line['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
     print(json.dumps(line), flush=True)
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.barrier()

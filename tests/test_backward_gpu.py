@@ -1,6 +1,7 @@
-"""Backward natives: HIP kernels vs the oracle vs the REFERENCE's own kernels (oracle/_ref), and the
-autograd Functions end to end against a float64 torch restatement. Scatter kernels (atomics in the reference as well):
-|diff| <= 1e-5 * (1 + |x|) * contributions; gather kernels (col2im_coord): bit-exact."""
+"""Backward natives: HIP kernels vs the oracle vs the REFERENCE's own kernels (oracle/_ref, their outputs
+replayed from tests/golden/ref_backward.npz: oracle/refvec.py), and the autograd Functions end to end against a float64 torch
+restatement. Scatter kernels (atomics in the reference as well): |diff| <= 1e-5 * (1 + |x|) * contributions; gather kernels
+(col2im_coord): bit-exact."""
 import ctypes
 import os
 
@@ -10,17 +11,20 @@ import torch
 
 import oracle
 from conftest import ROOT, gen_rois, torch_deform_im2col
+from oracle.refvec import RefLib, RefVectors
 
 pytestmark = pytest.mark.gpu
 P = ctypes.c_void_p
 CASES = [(16, 20, 33, 1, 1, 1, 1), (8, 12, 12, 2, 1, 2, 2), (4, 15, 15, 1, 2, 1, 1), (6, 9, 10, 0, 1, 1, 3)]
 
 
+VEC = RefVectors(os.path.join(ROOT, "tests", "golden", "ref_backward.npz"))
+
+
 @pytest.fixture(scope="module")
 def ref():
-    path = os.path.join(ROOT, "oracle", "_ref", "libupsnet_ref.so")
-    assert os.path.exists(path), "%s missing: run `make -C oracle ref` where /root/reference exists" % path
-    return ctypes.CDLL(path)
+    yield RefLib(VEC, os.path.join(ROOT, "oracle", "_ref", "libupsnet_ref.so"))
+    VEC.save()
 
 
 _ALIVE = []
@@ -74,10 +78,13 @@ def test_roi_align_backward(ref):
         g = torch.zeros((B, C, H, W), device='cuda')
         assert U.roi_align_backward(ph, ph, sr, 0.25, cu(top), cu(rois), g) == 1
         _close(g.cpu().numpy(), want, 1e-4)
-        r = torch.zeros((B, C, H, W), device='cuda')
-        ref.ref_roi_align_backward(None, p(cu(top)), ctypes.c_float(0.25), B, rois.shape[0], H, W, C, ph, ph, sr, p(cu(rois)), p(r))
-        torch.cuda.synchronize()
-        _close(r.cpu().numpy(), want, 1e-4)                      # the reference kernel agrees with the oracle to the same bound
+        def run(lib):
+            r = torch.zeros((B, C, H, W), device='cuda')
+            lib.ref_roi_align_backward(None, p(cu(top)), ctypes.c_float(0.25), B, rois.shape[0], H, W, C, ph, ph, sr, p(cu(rois)), p(r))
+            torch.cuda.synchronize()
+            return r.cpu().numpy()
+        r = ref("roi_align_backward", (top, rois, B, C, H, W, ph, sr), want, run)
+        _close(r, want, 1e-4)                                    # the reference kernel agrees with the oracle to the same bound
         # accumulates (reference semantics): a second call doubles
         U.roi_align_backward(ph, ph, sr, 0.25, cu(top), cu(rois), g)
         _close(g.cpu().numpy(), 2 * want, 2e-4)
@@ -97,10 +104,12 @@ def test_deform_col2im(ref, C, H, W, pad, stride, dil, dg):
     g = torch.zeros(im.shape, device='cuda')
     U.deform_col2im(cu(col), cu(off), im.shape, col.shape, *args, B, dg, g)
     _close(g.cpu().numpy(), want)
-    r = torch.zeros(im.shape, device='cuda')
-    ref.ref_deform_col2im(None, p(cu(col)), p(cu(off)), C, H, W, k, k, pad, pad, stride, stride, dil, dil, B, dg, p(r))
-    torch.cuda.synchronize()
-    _close(r.cpu().numpy(), want)
+    def run(lib):
+        r = torch.zeros(im.shape, device='cuda')
+        lib.ref_deform_col2im(None, p(cu(col)), p(cu(off)), C, H, W, k, k, pad, pad, stride, stride, dil, dil, B, dg, p(r))
+        torch.cuda.synchronize()
+        return r.cpu().numpy()
+    _close(ref("deform_col2im", (col, off, C, H, W, k, pad, stride, dil, B, dg), want, run), want)
     # v2: the pybind wrapper is batch 1 (mod_deform_conv_cuda.cpp:86), one call per image
     for b in range(B):
         cb = np.ascontiguousarray(col[:, b:b + 1])
@@ -108,11 +117,13 @@ def test_deform_col2im(ref, C, H, W, pad, stride, dil, dg):
         g = torch.zeros((C, H, W), device='cuda')
         U.mod_deform_col2im(cu(cb), cu(off[b]), cu(mask[b]), (1, C, H, W), (C * k * k, Ho, Wo), *args, dg, g)
         _close(g.cpu().numpy(), want[0])
-        r = torch.zeros((C, H, W), device='cuda')
-        ref.ref_mod_deform_col2im(None, p(cu(cb)), p(cu(off[b])), p(cu(mask[b])), 1, C, H, W, Ho, Wo, k, k, pad, pad, stride, stride,
-                                  dil, dil, dg, p(r))
-        torch.cuda.synchronize()
-        _close(r.cpu().numpy(), want[0])
+        def run(lib):
+            r = torch.zeros((C, H, W), device='cuda')
+            lib.ref_mod_deform_col2im(None, p(cu(cb)), p(cu(off[b])), p(cu(mask[b])), 1, C, H, W, Ho, Wo, k, k, pad, pad, stride, stride,
+                                      dil, dil, dg, p(r))
+            torch.cuda.synchronize()
+            return r.cpu().numpy()
+        _close(ref("mod_deform_col2im", (cb, off[b], mask[b], C, H, W, Ho, Wo, k, pad, stride, dil, dg), want[0], run), want[0])
 
 
 @pytest.mark.parametrize("C,H,W,pad,stride,dil,dg", CASES)
@@ -131,21 +142,27 @@ def test_deform_col2im_coord_bit_exact(ref, C, H, W, pad, stride, dil, dg):
     g = torch.full(off.shape, 7.0, device='cuda')
     U.deform_col2im_coord(cu(col), cu(im), cu(off), im.shape, col.shape, *args, B, dg, g)
     assert np.array_equal(g.cpu().numpy(), want)
-    r = torch.zeros(off.shape, device='cuda')
-    ref.ref_deform_col2im_coord(None, p(cu(col)), p(cu(im)), p(cu(off)), C, H, W, k, k, pad, pad, stride, stride, dil, dil, B, dg, p(r))
-    torch.cuda.synchronize()
-    assert np.array_equal(r.cpu().numpy(), want)                 # oracle == the reference's kernel, bit for bit
+    def run(lib):
+        r = torch.zeros(off.shape, device='cuda')
+        lib.ref_deform_col2im_coord(None, p(cu(col)), p(cu(im)), p(cu(off)), C, H, W, k, k, pad, pad, stride, stride, dil, dil, B, dg, p(r))
+        torch.cuda.synchronize()
+        return r.cpu().numpy()
+    r = ref("deform_col2im_coord", (col, im, off, C, H, W, k, pad, stride, dil, B, dg), want, run)
+    assert np.array_equal(r, want)                               # oracle == the reference's kernel, bit for bit
     for b in range(B):
         cb = np.ascontiguousarray(col[:, b:b + 1])
         w_off, w_mask = oracle.deform_col2im_coord(cb, im[b:b + 1], off[b:b + 1], *args, dg, mask=mask[b:b + 1])
         go, gm = torch.full(off[b].shape, 7.0, device='cuda'), torch.full(mask[b].shape, 7.0, device='cuda')
         U.mod_deform_col2im_coord(cu(cb), cu(im[b]), cu(off[b]), cu(mask[b]), (1, C, H, W), (C * k * k, Ho, Wo), *args, dg, go, gm)
         assert np.array_equal(go.cpu().numpy(), w_off[0]) and np.array_equal(gm.cpu().numpy(), w_mask[0])
-        ro, rm = torch.zeros(off[b].shape, device='cuda'), torch.zeros(mask[b].shape, device='cuda')
-        ref.ref_mod_deform_col2im_coord(None, p(cu(cb)), p(cu(im[b])), p(cu(off[b])), p(cu(mask[b])), 1, C, H, W, Ho, Wo, k, k, pad, pad,
-                                        stride, stride, dil, dil, dg, p(ro), p(rm))
-        torch.cuda.synchronize()
-        assert np.array_equal(ro.cpu().numpy(), w_off[0]) and np.array_equal(rm.cpu().numpy(), w_mask[0])
+        def run(lib):
+            ro, rm = torch.zeros(off[b].shape, device='cuda'), torch.zeros(mask[b].shape, device='cuda')
+            lib.ref_mod_deform_col2im_coord(None, p(cu(cb)), p(cu(im[b])), p(cu(off[b])), p(cu(mask[b])), 1, C, H, W, Ho, Wo, k, k, pad, pad,
+                                            stride, stride, dil, dil, dg, p(ro), p(rm))
+            torch.cuda.synchronize()
+            return ro.cpu().numpy(), rm.cpu().numpy()
+        ro, rm = ref("mod_deform_col2im_coord", (cb, im[b], off[b], mask[b], C, H, W, Ho, Wo, k, pad, stride, dil, dg), (w_off[0], w_mask[0]), run)
+        assert np.array_equal(ro, w_off[0]) and np.array_equal(rm, w_mask[0])
 
 
 def test_mod_col2im_pad_quirk(ref):
@@ -158,11 +175,17 @@ def test_mod_col2im_pad_quirk(ref):
     off = (rng.normal(size=(18, Ho, Wo)) * 2).astype(np.float32)
     mask = rng.uniform(0, 2, size=(9, Ho, Wo)).astype(np.float32)
     col = rng.normal(size=(C * 9, Ho, Wo)).astype(np.float32)
-    g, r = torch.zeros((C, H, W), device='cuda'), torch.zeros((C, H, W), device='cuda')
+    g = torch.zeros((C, H, W), device='cuda')
     U.mod_deform_col2im(cu(col), cu(off), cu(mask), (1, C, H, W), (C * 9, Ho, Wo), (k, k), (1, 2), (1, 1), (1, 1), dg, g)
-    ref.ref_mod_deform_col2im(None, p(cu(col)), p(cu(off)), p(cu(mask)), 1, C, H, W, Ho, Wo, k, k, 1, 2, 1, 1, 1, 1, dg, p(r))
+
+    def run(lib):
+        r = torch.zeros((C, H, W), device='cuda')
+        lib.ref_mod_deform_col2im(None, p(cu(col)), p(cu(off)), p(cu(mask)), 1, C, H, W, Ho, Wo, k, k, 1, 2, 1, 1, 1, 1, dg, p(r))
+        torch.cuda.synchronize()
+        return r.cpu().numpy()
+    r = ref("mod_deform_col2im_pad_quirk", (col, off, mask, C, H, W, Ho, Wo, k, dg), None, run)
     torch.cuda.synchronize()
-    _close(g.cpu().numpy(), r.cpu().numpy())
+    _close(g.cpu().numpy(), r)
 
 
 def _torch_dcn(data, offset, mask, weight, bias, k, pad, stride, dil, dg):

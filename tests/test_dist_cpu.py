@@ -14,6 +14,7 @@ def _worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from upsnet_amd.upsnet_end2end_test import gather_results, init_distributed, shard_indices
+    torch.cuda.is_available = lambda: False      # the host path (gloo, CPU tensors) also where GPUs are visible: this rank never opens one
     r, w, dev = init_distributed()
     assert (r, w) == (rank, world) and dist.get_backend() == 'gloo'
     ids = shard_indices(7, rank, world)           # uneven: rank 0 gets 4 images, rank 1 gets 3
