@@ -683,6 +683,32 @@ int upsnet_im_post_rle(void *stream, const float *pred_boxes, const float *mask_
                        int num_mask_channels, int mask_size, int im_height, int im_width, int cap, unsigned *transitions,
                        int *transition_count);
 
+/* ============================== Evaluation: panoptic quality and semantic confusion matrix ============================== */
+
+/* BaseDataset.evaluate_panoptic -> _pq_compute_single_core (upsnet/dataset/base_dataset.py:209-330,514-610) for one image, on the
+ * device, added into running per-category accumulators:
+ *   pred_2ch uint8 [H,W,3] (get_unified_pan_result's output: channel 0 category, 255 = VOID; channel 1 instance);
+ *   gt_rgb uint8 [H,W,3] GT panoptic PNG, id = R + 256 G + 65536 B, id 0 = VOID;
+ *   segments int64 [num_segments][4] = (id, category_id, iscrowd, area) in segments_info (JSON) order, area as given in the JSON;
+ *   cat_known uint8 [256]: non-zero for the categories of the dataset's category table;
+ *   tp / fp / fn int64 [256], iou float64 [256]: accumulators indexed by category (added to, never cleared);
+ *   status uint64 [1]: the first error, 0 if none; ((image_index + 1) << 8 | category) when a pred category is not in cat_known
+ *     (that image then adds nothing, like the reference, which raises KeyError).
+ * workspace: upsnet_pq_workspace_bytes(max_gt) bytes (0 for max_gt outside 0..4096), 8-byte aligned, ZEROED ONCE before its first
+ * use; every call leaves it zeroed again. num_segments <= max_gt, H * W < 2^31. Three launches on `stream`, no host synchronisation.
+ * Ids must be unique and non-zero, categories in 0..254 (the caller validates; the kernels stay in bounds regardless). */
+size_t upsnet_pq_workspace_bytes(int max_gt);
+int upsnet_pq_accumulate(void *stream, const unsigned char *pred_2ch, const unsigned char *gt_rgb, int height, int width,
+                         const int64_t *segments, int num_segments, const unsigned char *cat_known, int image_index, int max_gt,
+                         void *workspace, int64_t *tp, int64_t *fp, int64_t *fn, double *iou, uint64_t *status);
+
+/* BaseDataset.get_confusion_matrix (upsnet/dataset/base_dataset.py:806-824) added into confusion int64 [class_num, class_num]:
+ * for every pixel with gt_label != ignore_label (ignore_label = -1: no pixel dropped), index = gt * class_num + pred, counted iff
+ * index < class_num^2 -- a pred value >= class_num therefore aliases into another cell, as np.bincount does in the reference.
+ * gt_label / pred_label uint8 [npix]; class_num in 1..256. */
+int upsnet_confusion_accumulate(void *stream, const unsigned char *gt_label, const unsigned char *pred_label, long npix,
+                                int class_num, int ignore_label, int64_t *confusion);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,9 @@ _SIGNATURES = {
     "upsnet_im_post_rle": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "upsnet_fcn_score_combine": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P]),
     "upsnet_panoptic_argmax": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P]),
+    "upsnet_pq_workspace_bytes": (c_size_t, [c_int]),
+    "upsnet_pq_accumulate": (c_int, [P, P, P, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, P, P, P]),
+    "upsnet_confusion_accumulate": (c_int, [P, P, P, c_long, c_int, c_int, P]),
 }
 
 _lib = None

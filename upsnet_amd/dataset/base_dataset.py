@@ -1,13 +1,97 @@
-"""Post-processing of the network outputs -- host mirror of BaseDataset.get_unified_pan_result
-(upsnet/dataset/base_dataset.py:332-371), running on the device (csrc/postprocess.hip)."""
+"""Post-processing and evaluation of the network outputs -- host mirror of the reference's BaseDataset methods after the inference
+path: get_unified_pan_result (upsnet/dataset/base_dataset.py:332-371, csrc/postprocess.hip), evaluate_panoptic (:209-330, PQ through
+dataset/pq.py and csrc/pq_eval.hip) with its PQStat / PQStatCat host classes (:44-96), and get_confusion_matrix (:806-824) plus the
+mIoU of evaluate_ssegs (cityscapes.py:445-492), all counting on the device."""
+import json
+import os
+from collections import defaultdict
+
+import numpy as np
 import torch
 
 from .. import ops
 from ..config.config import config
 
 
+class PQStatCat(object):
+    """Per-category PQ counts: matched IoU sum, true positives, false positives, false negatives."""
+
+    def __init__(self):
+        self.iou = 0.0
+        self.tp = 0
+        self.fp = 0
+        self.fn = 0
+
+    def __iadd__(self, other):
+        self.iou += other.iou
+        self.tp += other.tp
+        self.fp += other.fp
+        self.fn += other.fn
+        return self
+
+
+class PQStat(object):
+    """PQStatCat per category id (created on first access); `+=` merges per category."""
+
+    def __init__(self):
+        self.pq_per_cat = defaultdict(PQStatCat)
+
+    def __getitem__(self, i):
+        return self.pq_per_cat[i]
+
+    def __iadd__(self, other):
+        for label, stat in other.pq_per_cat.items():
+            self.pq_per_cat[label] += stat
+        return self
+
+    def pq_average(self, categories, isthing):
+        """Mean PQ / SQ / RQ over the categories (isthing None: all; True / False: things / stuff) that have any tp, fp or fn, and
+        the per-category results; the reference's float arithmetic and summation order (categories in the table's order)."""
+        pq, sq, rq, n = 0, 0, 0, 0
+        per_class = {}
+        for label, info in categories.items():
+            if isthing is not None and isthing != (info['isthing'] == 1):
+                continue
+            s = self.pq_per_cat[label]
+            iou, tp, fp, fn = s.iou, s.tp, s.fp, s.fn
+            if tp + fp + fn == 0:
+                per_class[label] = {'pq': 0.0, 'sq': 0.0, 'rq': 0.0}
+                continue
+            n += 1
+            denom = tp + 0.5 * fp + 0.5 * fn
+            pq_c = iou / denom
+            sq_c = iou / tp if tp != 0 else 0
+            rq_c = tp / denom
+            per_class[label] = {'pq': pq_c, 'sq': sq_c, 'rq': rq_c, 'iou': iou, 'tp': tp, 'fp': fp, 'fn': fn}
+            pq += pq_c
+            sq += sq_c
+            rq += rq_c
+        return {'pq': pq / n, 'sq': sq / n, 'rq': rq / n, 'n': n}, per_class
+
+
+def _as_device_u8(a, dev):
+    """uint8 device tensor of integer labels 0..255 (the reference passes float32 GT / uint8 pred arrays); ValueError otherwise."""
+    t = torch.as_tensor(a)
+    if t.dtype != torch.uint8:
+        t = t.to(dev)
+        if t.numel() and (bool((t != t.round()).any()) or int(t.min()) < 0 or int(t.max()) > 255):
+            raise ValueError("labels must be integers in 0..255")
+        t = t.to(torch.uint8)
+    return t.to(dev).contiguous()
+
+
+def load_panoptic_png(path):
+    """GT panoptic PNG -> uint8 [H,W,3] RGB (id = R + 256 G + 65536 B). Raises where the reference's loader skips an unreadable
+    file silently (base_dataset.py:455-464), which would misalign every later image with its annotation."""
+    from PIL import Image
+    im = np.array(Image.open(path))
+    if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] < 3:
+        raise ValueError("%s: not an RGB panoptic PNG (%s %s)" % (path, im.shape, im.dtype))
+    return np.ascontiguousarray(im[:, :, :3])
+
+
 class BaseDataset(object):
-    """Only the result-shaping methods of the reference class that sit directly after the inference path."""
+    """Only the result-shaping and scoring methods of the reference class that follow the inference path."""
 
     def get_unified_pan_result(self, segs, pans, cls_inds, stuff_area_limit=4 * 64 * 64):
         """segs / pans: per-image int64 label maps ([H,W] or [1,H,W], device tensors; numpy arrays are uploaded);
@@ -20,3 +104,49 @@ class BaseDataset(object):
             seg, pan, cls_ind = (torch.as_tensor(t).to(dev) for t in (seg, pan, cls_ind))
             out.append(ops.unified_pan_result(pan, seg, cls_ind, id_last_stuff, config.dataset.num_seg_classes, stuff_area_limit))
         return out
+
+    def load_panoptic_gt(self):
+        """(images, annotations, categories) of self.panoptic_json_file; images yields the uint8 [H,W,3] GT PNGs of
+        self.panoptic_gt_folder in the JSON's 'images' order (as the reference loads them), lazily."""
+        with open(self.panoptic_json_file, 'r') as f:
+            gt_json = json.load(f)
+        categories = {el['id']: el for el in gt_json['categories']}
+        images = (load_panoptic_png(os.path.join(self.panoptic_gt_folder, item['file_name'])) for item in gt_json['images'])
+        return images, gt_json['annotations'], categories
+
+    def evaluate_panoptic(self, pred_pans_2ch, output_dir, max_gt_segments=4096):
+        """PQ / SQ / RQ of the 2-channel predictions (get_unified_pan_result's list, at GT resolution) against the panoptic GT,
+        computed on the device (dataset/pq.py: semantics, summation order and deviations). Returns the reference's dict
+        {'All', 'Things', 'Stuff', 'per_class'} and logs its tables. Unlike the reference nothing is written to output_dir (the pred
+        PNG / JSON dumps only recolour the segments; PQ does not depend on them)."""
+        from .pq import PanopticEvaluator
+        images, annotations, categories = self.load_panoptic_gt()
+        if len(pred_pans_2ch) != len(annotations):
+            raise ValueError("%d predictions for %d GT annotations" % (len(pred_pans_2ch), len(annotations)))
+        ev = PanopticEvaluator(categories, max_gt_segments=max_gt_segments)
+        for pred, gt, ann in zip(pred_pans_2ch, images, annotations):
+            ev.add(pred, gt, ann['segments_info'])
+        return ev.summary()
+
+    def get_confusion_matrix(self, gt_label, pred_label, class_num):
+        """Confusion matrix [class_num, class_num] float64 (numpy) of two label arrays of one shape, counted on the device: cell
+        (gt, pred) for index gt * class_num + pred < class_num^2; a pred value >= class_num aliases into another cell, as the
+        reference's np.bincount does. Labels must be integers in 0..255."""
+        dev = torch.device('cuda', torch.cuda.current_device())
+        cm = torch.zeros((class_num, class_num), dtype=torch.int64, device=dev)
+        ops.confusion_accumulate(_as_device_u8(gt_label, dev), _as_device_u8(pred_label, dev), class_num, -1, cm)
+        return cm.cpu().numpy().astype(np.float64)
+
+    def evaluate_ssegs_arrays(self, gts, preds, num_seg_classes):
+        """evaluate_ssegs (cityscapes.py:445-492) over in-memory label maps instead of PNG files: pixels with gt == 255 dropped,
+        confusion matrices summed on the device, then the reference's IoU formula. Returns {'meanIU', 'IU_array', 'confusion_matrix'}."""
+        dev = torch.device('cuda', torch.cuda.current_device())
+        cm = torch.zeros((num_seg_classes, num_seg_classes), dtype=torch.int64, device=dev)
+        for gt, pred in zip(gts, preds):
+            ops.confusion_accumulate(_as_device_u8(gt, dev), _as_device_u8(pred, dev), num_seg_classes, 255, cm)
+        confusion_matrix = cm.cpu().numpy().astype(np.float64)
+        pos = confusion_matrix.sum(1)
+        res = confusion_matrix.sum(0)
+        tp = np.diag(confusion_matrix)
+        IU_array = tp / np.maximum(1.0, pos + res - tp)
+        return {'meanIU': IU_array.mean(), 'IU_array': IU_array, 'confusion_matrix': confusion_matrix}

@@ -1198,6 +1198,52 @@ def unified_pan_result(pan, seg, cls_inds, id_last_stuff, num_seg_classes, stuff
     return out
 
 
+def pq_workspace(max_gt, device):
+    """Zeroed workspace of pq_accumulate for images of at most max_gt GT segments (0..4096); every call leaves it zeroed again."""
+    nbytes = int(lib().upsnet_pq_workspace_bytes(int(max_gt)))
+    if nbytes == 0:
+        raise ValueError("pq_workspace: max_gt %d outside 0..4096" % max_gt)
+    return torch.zeros((nbytes,), dtype=torch.uint8, device=device)
+
+
+def pq_accumulate(pred_2ch, gt_rgb, segments, cat_known, image_index, max_gt, workspace, tp, fp, fn, iou, status):
+    """_pq_compute_single_core of ONE image on the device, added into the running accumulators (include/upsnet_hip.h):
+    pred_2ch / gt_rgb uint8 [H,W,3]; segments int64 [n,4] = (id, category_id, iscrowd, area) in segments_info order; cat_known uint8
+    [256]; tp / fp / fn int64 [256], iou float64 [256], status int64 [1] (first error). No host synchronisation."""
+    require_cuda(pred_2ch, gt_rgb, segments, cat_known, workspace, tp, fp, fn, iou, status)
+    if pred_2ch.dtype != torch.uint8 or gt_rgb.dtype != torch.uint8 or pred_2ch.dim() != 3 or pred_2ch.shape[2] != 3 \
+            or tuple(pred_2ch.shape) != tuple(gt_rgb.shape):
+        raise ValueError("pq_accumulate: pred_2ch %s %s and gt_rgb %s %s must both be uint8 [H,W,3]"
+                         % (tuple(pred_2ch.shape), pred_2ch.dtype, tuple(gt_rgb.shape), gt_rgb.dtype))
+    if segments.dtype != torch.int64 or segments.dim() != 2 or segments.shape[1] != 4:
+        raise ValueError("pq_accumulate: segments must be int64 [n,4]")
+    for t, dt, n in ((cat_known, torch.uint8, 256), (tp, torch.int64, 256), (fp, torch.int64, 256), (fn, torch.int64, 256),
+                     (iou, torch.float64, 256), (status, torch.int64, 1)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise ValueError("pq_accumulate: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
+    pred_2ch, gt_rgb, segments = pred_2ch.contiguous(), gt_rgb.contiguous(), segments.contiguous()
+    H, W = pred_2ch.shape[:2]
+    check(lib().upsnet_pq_accumulate(stream(), ptr(pred_2ch), ptr(gt_rgb), H, W, ptr(segments) if segments.numel() else None,
+                                     int(segments.shape[0]), ptr(cat_known), int(image_index), int(max_gt), ptr(workspace), ptr(tp), ptr(fp),
+                                     ptr(fn), ptr(iou), ptr(status)), "pq_accumulate")
+
+
+def confusion_accumulate(gt_label, pred_label, class_num, ignore_label, confusion):
+    """get_confusion_matrix on the device, added into confusion int64 [class_num, class_num]: gt_label / pred_label uint8 of one
+    shape; pixels with gt == ignore_label dropped (-1: none); index gt * C + pred counted iff < C^2 (pred >= C aliases, as
+    np.bincount does in the reference)."""
+    require_cuda(gt_label, pred_label, confusion)
+    if gt_label.dtype != torch.uint8 or pred_label.dtype != torch.uint8 or gt_label.shape != pred_label.shape:
+        raise ValueError("confusion_accumulate: gt %s %s and pred %s %s must both be uint8 of one shape"
+                         % (tuple(gt_label.shape), gt_label.dtype, tuple(pred_label.shape), pred_label.dtype))
+    if confusion.dtype != torch.int64 or tuple(confusion.shape) != (class_num, class_num) or not confusion.is_contiguous():
+        raise ValueError("confusion_accumulate: confusion must be a contiguous int64 [%d,%d] tensor" % (class_num, class_num))
+    gt_label, pred_label = gt_label.contiguous(), pred_label.contiguous()
+    check(lib().upsnet_confusion_accumulate(stream(), ptr(gt_label), ptr(pred_label), int(gt_label.numel()), int(class_num),
+                                            int(ignore_label), ptr(confusion)), "confusion_accumulate")
+    return confusion
+
+
 def mask_roi_dedup(a_src, a_cls, a_num, b_src, b_cls, b_boxes, b_num):
     """Rows of the B detections inside [A ; unmatched of B] (matching on (source ROI, class)). Returns (map int32 [capB],
     extra_boxes [capB,5], num_extra device int32 [1])."""
