@@ -709,6 +709,44 @@ int upsnet_pq_accumulate(void *stream, const unsigned char *pred_2ch, const unsi
 int upsnet_confusion_accumulate(void *stream, const unsigned char *gt_label, const unsigned char *pred_label, long npix,
                                 int class_num, int ignore_label, int64_t *confusion);
 
+/* ============================== Evaluation: COCO box / mask AP (pycocotools COCOeval, default Params) ============================== */
+
+/* COCOeval.evaluate() for ONE image, on the device: computeIoU + evaluateImg (maxDet 100) for every category row, written as one record
+ * per detection at rec_*[0 .. num_det) (the caller passes the arrays offset to this image's first record):
+ *   rec_score double (the det score), rec_img int (image_index), rec_rk int (row << 8 | rank inside (image, row), score descending,
+ *   ties in input order; -1 when the class has no row or the rank is >= 100), rec_match / rec_ign uint64: bit a * 10 + t = matched /
+ *   ignored for area range a and IoU threshold t (written only for rec_rk >= 0). npig int64 [num_rows][4] += the non-ignored GTs.
+ * Detections: det_score double [num_det], det_cls int64 [num_det] (1-based classes; row = class_to_row[cls] for 0 <= cls < num_classes,
+ *   -1 = not scored); bbox: det_xyxy double [num_det][4] (x2 - x1 + 1 = width, as xyxy_to_xywh); segm: either det_box_f32 [num_det][4]
+ *   + mask_prob float [num_det][num_mask_channels][mask_size][mask_size] pasted by the im_post rule, or run-lengths det_trans (sorted
+ *   column-major change positions, the first starting a run of ones) with det_trans_off int64 [num_det + 1].
+ * GT, grouped by row (gt_row_off int [num_rows + 1]), input order inside a row: gt_box double [num_gt][4] xywh (bbox), gt_area double
+ *   (the JSON area: area ranges only), gt_crowd int; segm masks: run-lengths (gt_trans, gt_trans_off [num_gt_rle + 1], gt_trans_dst =
+ *   the GT index of each) and / or uint8 [H,W] device masks gt_u8[j] (a HOST array of device pointers) for GT gt_u8_dst[j] (host ints).
+ * rows_with_gt int [num_rows_with_gt]: the rows with at least one GT. params double [18]: min(iouThr, 1 - 1e-10) for the 10 thresholds,
+ *   then (lo, hi) of the 4 area ranges. workspace: upsnet_det_eval_image_workspace_bytes(...) bytes, 256-byte aligned; no zeroing.
+ * H * W < 2^31; scores must not be NaN. Launches on `stream` only, no host synchronisation. */
+size_t upsnet_det_eval_image_workspace_bytes(int num_det, int num_rows, int num_gt, int height, int width, int segm);
+int upsnet_det_eval_image(void *stream, int segm, int height, int width, int num_rows, int num_det, const double *det_xyxy,
+                          const double *det_score, const int64_t *det_cls, const int *class_to_row, int num_classes,
+                          const float *det_box_f32, const float *mask_prob, int num_mask_channels, int mask_size,
+                          const int *det_trans, const int64_t *det_trans_off, int num_gt, const int *gt_row_off,
+                          const double *gt_box, const double *gt_area, const int *gt_crowd, const int *gt_trans,
+                          const int64_t *gt_trans_off, const int *gt_trans_dst, int num_gt_rle, const unsigned char *const *gt_u8,
+                          const int *gt_u8_dst, int num_gt_u8, const int *rows_with_gt, int num_rows_with_gt,
+                          const double *params, int image_index, void *workspace, double *rec_score, int *rec_img, int *rec_rk,
+                          uint64_t *rec_match, uint64_t *rec_ign, int64_t *npig);
+
+/* COCOeval.accumulate() over num_records records of upsnet_det_eval_image: img_ord int [number of images]: the position of image_index
+ * in ascending image_id order; rec_thrs double [101] (recThrs); npig as accumulated. Outputs (fully written): precision / scores double
+ * [10][101][num_rows][4][3], recall double [10][num_rows][4][3], -1 where npig == 0. workspace:
+ * upsnet_det_eval_accumulate_workspace_bytes(num_records, num_rows) bytes, 256-byte aligned; no zeroing. */
+size_t upsnet_det_eval_accumulate_workspace_bytes(long num_records, int num_rows);
+int upsnet_det_eval_accumulate(void *stream, long num_records, const double *rec_score, const int *rec_img, const int *rec_rk,
+                               const uint64_t *rec_match, const uint64_t *rec_ign, const int *img_ord, int num_rows,
+                               const int64_t *npig, const double *rec_thrs, void *workspace, double *precision, double *recall,
+                               double *scores);
+
 #ifdef __cplusplus
 }
 #endif

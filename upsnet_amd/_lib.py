@@ -126,6 +126,11 @@ _SIGNATURES = {
     "upsnet_pq_workspace_bytes": (c_size_t, [c_int]),
     "upsnet_pq_accumulate": (c_int, [P, P, P, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, P, P, P]),
     "upsnet_confusion_accumulate": (c_int, [P, P, P, c_long, c_int, c_int, P]),
+    "upsnet_det_eval_image_workspace_bytes": (c_size_t, [c_int] * 6),
+    "upsnet_det_eval_image": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, c_int, c_int, P, P, c_int, P, P, P, P,
+                                      P, P, P, c_int, P, P, c_int, P, c_int, P, c_int, P, P, P, P, P, P, P]),
+    "upsnet_det_eval_accumulate_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "upsnet_det_eval_accumulate": (c_int, [P, c_long, P, P, P, P, P, P, c_int, P, P, P, P, P, P]),
 }
 
 _lib = None

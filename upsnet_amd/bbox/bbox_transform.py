@@ -37,6 +37,19 @@ def clip_boxes(boxes, im_shape):
     return boxes
 
 
+def xyxy_to_xywh(boxes):
+    """Corner boxes (x1, y1, x2, y2) -> (x, y, width, height) in inclusive pixel units: width = (x2 - x1) + 1, computed in the dtype
+    of the input, so a float64 array of results gives the float64 boxes of the COCO results JSON. Accepts one box as a 4-sequence
+    (returns a tuple) or an [n, 4] array."""
+    if isinstance(boxes, np.ndarray):
+        b = boxes
+        return np.concatenate([b[:, :2], b[:, 2:4] - b[:, :2] + 1], axis=1)
+    if isinstance(boxes, (list, tuple)) and len(boxes) == 4:
+        x1, y1, x2, y2 = boxes
+        return (x1, y1, x2 - x1 + 1, y2 - y1 + 1)
+    raise TypeError('xyxy_to_xywh: expected an [n, 4] array or one box of 4 numbers, got %r' % type(boxes).__name__)
+
+
 def expand_boxes(boxes, scale):
     """Boxes [n,4] grown about their centres by `scale` (bbox_transform.py:365-381; float64 result like the reference's np.zeros)."""
     half = np.stack([boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]], 1) * .5

@@ -12,7 +12,7 @@
 //                        present id (the reference's enumerate index), stuff-area filter -> a 256-entry LUT id -> (cat, ins)
 //   unipan_apply_kernel  one pass: LUT lookup, uint8 [H,W,3] written (3rd channel zero)
 #include "common.h"
-#include "resize.h"
+#include "impaste.h"
 #include "upsnet_hip.h"
 
 #define UP_IDS 256
@@ -169,9 +169,6 @@ extern "C" int upsnet_unified_pan_result(void *stream, const int64_t *pan, const
 // are the differences of that list (host: upsnet_amd/dataset/rle.py, which also does pycocotools' string compression).
 // Pass 1 counts the transitions per column, a workgroup prefix sum gives the offsets, pass 2 writes the positions.
 #define IMP_T 256
-#define IMP_MAXMS 34   // padded mask side (28 + 2 in every config)
-
-struct ImpBox { int bx0, by0, w, h, x_0, x_1, y_0, y_1; };
 
 __device__ static inline int imp_column(const float *__restrict__ s_pad, const int ps, const ImpBox &b, const int x, const int H,
                                         unsigned prev, unsigned *__restrict__ out, const long col_base)
@@ -199,25 +196,9 @@ im_post_rle_kernel(const float *__restrict__ boxes, const float *__restrict__ ma
     __shared__ int s_carry;
     const int d = blockIdx.x, tid = threadIdx.x;
     const int ps = ms + 2;
-    const int ch = num_ch > 1 ? (int)cls_inds[d] : 0;
-    const float *src = mask_prob + ((long)d * num_ch + ch) * ms * ms;
-    for (int i = tid; i < ps * ps; i += IMP_T) {
-        const int py = i / ps, px = i - py * ps;
-        s_pad[i] = (py >= 1 && py <= ms && px >= 1 && px <= ms) ? src[(py - 1) * ms + (px - 1)] : 0.f;
-    }
+    imp_load_pad(s_pad, mask_prob, cls_inds, d, num_ch, ms, tid, IMP_T);
     if (tid == 0) s_carry = 0;
-    // expand_boxes (bbox_transform.py:365-381) in float32, then astype(int32) (truncation)
-    const float scale = (float)(((double)ms + 2.0) / (double)ms);
-    const float bx1 = boxes[d * 4 + 0], by1 = boxes[d * 4 + 1], bx2 = boxes[d * 4 + 2], by2 = boxes[d * 4 + 3];
-    float w_half = (bx2 - bx1) * .5f, h_half = (by2 - by1) * .5f;
-    const float x_c = (bx2 + bx1) * .5f, y_c = (by2 + by1) * .5f;
-    w_half = w_half * scale; h_half = h_half * scale;
-    const int rx1 = (int)(x_c - w_half), rx2 = (int)(x_c + w_half), ry1 = (int)(y_c - h_half), ry2 = (int)(y_c + h_half);
-    ImpBox b;
-    b.w = max(rx2 - rx1 + 1, 1); b.h = max(ry2 - ry1 + 1, 1);
-    b.bx0 = rx1; b.by0 = ry1;
-    b.x_0 = max(rx1, 0); b.x_1 = min(rx2 + 1, W);
-    b.y_0 = max(ry1, 0); b.y_1 = min(ry2 + 1, H);
+    const ImpBox b = imp_box(boxes + d * 4, ms, H, W);
     __syncthreads();
     unsigned *out = trans + (long)d * cap;
     const bool touch = b.y_1 == H;   // only then the last pixel of a column (row H-1) can be set and precede the next column

@@ -3,6 +3,7 @@ path: get_unified_pan_result (upsnet/dataset/base_dataset.py:332-371, csrc/postp
 dataset/pq.py and csrc/pq_eval.hip) with its PQStat / PQStatCat host classes (:44-96), and get_confusion_matrix (:806-824) plus the
 mIoU of evaluate_ssegs (cityscapes.py:445-492), all counting on the device."""
 import json
+import logging
 import os
 from collections import defaultdict
 
@@ -11,6 +12,8 @@ import torch
 
 from .. import ops
 from ..config.config import config
+
+logger = logging.getLogger(__name__)
 
 
 class PQStatCat(object):
@@ -127,6 +130,79 @@ class BaseDataset(object):
         for pred, gt, ann in zip(pred_pans_2ch, images, annotations):
             ev.add(pred, gt, ann['segments_info'])
         return ev.summary()
+
+    # ---------------------------------------------------------------------------------------------- COCO box / mask AP
+    def load_instances_gt(self):
+        """(image_ids ascending, {image_id: (height, width)}, {image_id: [annotations in JSON order]}, category ids in JSON order) of
+        the COCO instances JSON self.instances_json_file. Class c >= 1 of all_boxes / all_segms is the c-th category of the JSON's
+        'categories' list, as the reference's classes follow COCO.getCatIds()."""
+        with open(self.instances_json_file, 'r') as f:
+            gt_json = json.load(f)
+        image_ids = sorted(int(im['id']) for im in gt_json['images'])
+        sizes = {int(im['id']): (int(im['height']), int(im['width'])) for im in gt_json['images']}
+        anns = defaultdict(list)
+        for a in gt_json['annotations']:
+            anns[int(a['image_id'])].append(a)
+        return image_ids, sizes, anns, [int(c['id']) for c in gt_json['categories']]
+
+    def _evaluate_detections(self, all_boxes, all_segms, output_dir, iou_type):
+        """The reference's evaluate_boxes / evaluate_masks: results JSON written as the reference writes it, COCOeval on the device
+        (dataset/coco_eval.py), the metrics logged and the summary lines written to detection_results.txt."""
+        from .coco_eval import DetectionEvaluator, EvalResult, detection_metrics_lines
+        from ..bbox.bbox_transform import xyxy_to_xywh
+        image_ids, sizes, anns, cat_ids = self.load_instances_gt()
+        name = getattr(self, 'name', 'instances')
+        results = []
+        n_cls = min(len(all_boxes), len(cat_ids) + 1)
+        for c in range(1, n_cls):
+            if len(all_boxes[c]) != len(image_ids) or (all_segms is not None and len(all_segms[c]) != len(image_ids)):
+                raise ValueError("class %d: results for %d images, the GT has %d" % (c, len(all_boxes[c]), len(image_ids)))
+            for i, image_id in enumerate(image_ids):
+                dets = all_boxes[c][i]
+                if isinstance(dets, list) and len(dets) == 0:
+                    continue
+                dets = np.asarray(dets).astype(np.float64)
+                xywh = xyxy_to_xywh(dets[:, 0:4])
+                for k in range(dets.shape[0]):
+                    r = {'image_id': image_id, 'category_id': cat_ids[c - 1], 'score': float(dets[k, -1])}
+                    if all_segms is None:
+                        r['bbox'] = [float(v) for v in xywh[k]]
+                    else:
+                        r['segmentation'] = all_segms[c][i][k]
+                    results.append(r)
+        res_file = os.path.join(output_dir, ('bbox_' if all_segms is None else 'segmentations_') + name + '_results.json')
+        logger.info('Writing %s results json to: %s', iou_type, os.path.abspath(res_file))
+        with open(res_file, 'w') as fid:
+            json.dump(results, fid)
+        ev = DetectionEvaluator(cat_ids, iou_type)
+        for i, image_id in enumerate(image_ids):
+            dets = [[]] + [all_boxes[c][i] for c in range(1, n_cls)]
+            rles = None if all_segms is None else [[]] + [all_segms[c][i] for c in range(1, n_cls)]
+            ev.add_rle(image_id, anns.get(image_id, []), dets, rles, image_size=sizes[image_id])
+        res = ev.accumulate()
+        for line in detection_metrics_lines(res)[:-12]:
+            logger.info(line)
+        with open(os.path.join(output_dir, 'detection_results.txt'), 'w') as f:
+            for line in res['summary_lines']:
+                print(line)
+                f.write(line + '\n')
+        return EvalResult(res)
+
+    def evaluate_boxes(self, all_boxes, output_dir):
+        """COCO box AP of all_boxes[class][image] ([n,5] x1 y1 x2 y2 score, images in ascending id) against
+        self.instances_json_file; returns the 12 summary stats. Writes bbox_<name>_results.json and detection_results.txt."""
+        return self._evaluate_detections(all_boxes, None, output_dir, 'bbox').stats
+
+    def evaluate_masks(self, all_boxes, all_segms, output_dir):
+        """COCO mask AP of all_segms[class][image] (im_post's RLE dicts) scored by all_boxes; returns an object with .stats and
+        .eval (precision / recall / scores). Writes segmentations_<name>_results.json and detection_results.txt. Polygon GT
+        segmentations are refused (ValueError, dataset/coco_eval.py)."""
+        return self._evaluate_detections(all_boxes, all_segms, output_dir, 'segm')
+
+    def evaluate_all(self, all_boxes, all_segms, output_dir):
+        all_results = self.evaluate_boxes(all_boxes, output_dir)
+        self.evaluate_masks(all_boxes, all_segms, output_dir)
+        return all_results
 
     def get_confusion_matrix(self, gt_label, pred_label, class_num):
         """Confusion matrix [class_num, class_num] float64 (numpy) of two label arrays of one shape, counted on the device: cell
