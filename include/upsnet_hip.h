@@ -683,6 +683,17 @@ int upsnet_im_post_rle(void *stream, const float *pred_boxes, const float *mask_
                        int num_mask_channels, int mask_size, int im_height, int im_width, int cap, unsigned *transitions,
                        int *transition_count);
 
+/* The semantic and panoptic label maps of one image restored to another resolution by a nearest-neighbour gather (the reference's
+ * crop + astype('uint8') + cv2.resize(fx = 1 / im_scale, INTER_NEAREST), upsnet/upsnet_end2end_test.py:258-272; also PIL's NEAREST
+ * resize in evaluate_ssegs): out[y][x] = (uint8) src[y_ofs[y]][x_ofs[x]], the low byte kept (numpy's astype('uint8') wrap).
+ *   sseg, pano int64 [src_height][src_stride] (row stride in elements, src_stride >= src_width); pano may be NULL (then out_pano too);
+ *   y_ofs int32 [out_height], x_ofs int32 [out_width]: source row / column of every output row / column (the host builds them;
+ *     entries outside the source are clamped to it); out_sseg, out_pano uint8 [out_height][out_width], row-major.
+ * Both maps in one launch, no host synchronisation. */
+int upsnet_restore_label_maps(void *stream, const int64_t *sseg, const int64_t *pano, long src_stride, int src_height, int src_width,
+                              const int *y_ofs, int out_height, const int *x_ofs, int out_width, unsigned char *out_sseg,
+                              unsigned char *out_pano);
+
 /* ============================== Evaluation: panoptic quality and semantic confusion matrix ============================== */
 
 /* BaseDataset.evaluate_panoptic -> _pq_compute_single_core (upsnet/dataset/base_dataset.py:209-330,514-610) for one image, on the

@@ -1,0 +1,2 @@
+from .cityscapes import Cityscapes
+from .coco import coco

@@ -1,0 +1,205 @@
+"""Run and score a checkpoint over a Cityscapes or COCO evaluation set: the reference's test command over a real image list
+(upsnet/upsnet_end2end_test.py:155-314).
+
+    python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N]
+
+The dataset is `config.dataset.dataset` (Cityscapes or coco) on `config.dataset.test_image_set`. Every image and every GT file the
+configured heads need is checked before the first launch. Images are decoded by a bounded host thread pool ahead of the device;
+the network runs through forward_async with up to N images in flight (its own graph policy: one fixed input shape replays HIP
+graphs, a new shape / im_info runs eagerly). Per image, as the reference's im_detect / im_post / loop (:55-152, 222-274): boxes
+scaled by 1 / im_scale in float32, masks run-length encoded by dataset/rle.im_post, the semantic and panoptic maps restored to the
+original resolution by one gather launch (csrc/restore.hip, cv2 INTER_NEAREST tables). The results pickle has the reference's
+path, keys and nesting (numpy objects only); evaluation follows the reference's order: boxes, masks, panoptic, semantic.
+`--eval_only` re-scores the pickle without building the model. One rank only (WORLD_SIZE > 1 is refused)."""
+import logging
+import os
+import pickle
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from .config.config import config
+
+logger = logging.getLogger(__name__)
+
+MAX_DECODE_THREADS = 8
+
+
+def final_output_path(cfg):
+    """lib/utils/logging.py:20-40: <output_path>/<cfg name>/<test_image_set, '+' -> '_'>."""
+    return os.path.join(config.output_path, os.path.basename(cfg).split('.')[0],
+                        '_'.join(str(config.dataset.test_image_set).split('+')))
+
+
+def default_weight_path(cfg):
+    """The checkpoint the reference loads without --weight_path (upsnet_end2end_test.py:190-193): output_path / <cfg name> /
+    <image_set> / <model_prefix><test_iteration>.pth."""
+    return os.path.join(config.get('output_path', ''), os.path.basename(cfg).split('.')[0],
+                        '_'.join(str(config.dataset.get('image_set', '')).split('+')),
+                        '%s%s.pth' % (config.get('model_prefix', ''), config.test.get('test_iteration', '')))
+
+
+def build_dataset(result_path):
+    from . import dataset as datasets
+    name = config.dataset.dataset
+    cls = getattr(datasets, name, None)
+    if cls is None:
+        raise ValueError('config.dataset.dataset %r names no dataset class (Cityscapes, coco)' % (name,))
+    return cls(image_sets=str(config.dataset.test_image_set).split('+'), flip=False, result_path=result_path, phase='test')
+
+
+def scale_boxes(pred_boxes, im_info):
+    """im_detect's pred_boxes[:, 1:] / im_info[2] (float32 numpy divided by a float32 scalar)."""
+    return pred_boxes[:, 1:].float().cpu().numpy() / np.float32(im_info[2])
+
+
+def post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds):
+    """One image's share of the reference's loop after the network (upsnet_end2end_test.py:254-272): appends to the result lists."""
+    from .dataset.restore import restore_to_image
+    from .dataset.rle import im_post
+    net = config.network
+    if net.has_rcnn:
+        boxes = scale_boxes(out['pred_boxes'], im_info)
+        cls_inds = out['cls_inds']
+        if net.has_mask_head:
+            im_size = np.round(im_info[:2] / im_info[2]).astype(np.int32)
+            im_post(all_boxes, all_masks, out['cls_probs'], torch.from_numpy(boxes).to(out['mask_probs'].device), out['mask_probs'],
+                    cls_inds, num_classes, im_size)
+        else:
+            cls_np, scores = cls_inds.cpu().numpy(), out['cls_probs'].cpu().numpy().reshape(-1, 1)
+            for idx in range(1, num_classes):
+                sel = cls_np == idx
+                all_boxes[idx].append(np.hstack([boxes[sel], scores[sel]]))
+    if net.has_fcn_head or net.has_panoptic_head:
+        sseg, pano = restore_to_image(out['fcn_outputs'], out['panoptic_outputs'] if net.has_panoptic_head else None, im_info)
+        if net.has_fcn_head:
+            all_ssegs.append(sseg.cpu().numpy())
+        if net.has_panoptic_head:
+            all_panos.append(pano.cpu().numpy())
+            all_pano_cls_inds.append(out['panoptic_cls_inds'].cpu().numpy())
+
+
+def run_inference(model, dataset, in_flight=1, device=None):
+    """The test loop over the whole image list. Returns (results dict as pickled, per-image timings)."""
+    from .dataset.blob import get_image_blob
+    net = config.network
+    n, num_classes = len(dataset), dataset.num_classes
+    all_boxes = [[] for _ in range(num_classes)]
+    all_masks = [[] for _ in range(num_classes)] if net.has_mask_head else None
+    all_ssegs = [] if net.has_fcn_head else None
+    all_panos, all_pano_cls_inds = ([], []) if net.has_panoptic_head else (None, None)
+    depth = max(1, min(int(in_flight), getattr(model, 'graph_slots', 1))) if hasattr(model, 'forward_async') else 1
+    launch = model.forward_async if depth > 1 else model
+    workers = max(1, min(MAX_DECODE_THREADS, n))     # (never sized from the host's CPU count)
+    ahead = 2 * workers                               # images decoded ahead of the device
+    times = {'data_time': [], 'net_time': [], 'post_time': []}
+    pending = []
+
+    def finish(i, handle, im_info, data_time, t_launch):
+        t0 = time.perf_counter()
+        out = handle.result() if hasattr(handle, 'result') else handle
+        if device is not None and device.type == 'cuda':
+            torch.cuda.synchronize(device)
+        t1 = time.perf_counter()
+        post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds)
+        post_time = time.perf_counter() - t1
+        # net_time: host time blocked on the network for this image (launch + wait); with one image in flight that is the
+        # reference's forward + synchronize
+        times['data_time'].append(data_time)
+        times['net_time'].append(t_launch + t1 - t0)
+        times['post_time'].append(post_time)
+        logger.info('Batch %d/%d, data_time:%.3f, net_time:%.3f, post_time:%.3f', i + 1, n, data_time, times['net_time'][-1], post_time)
+
+    with ThreadPoolExecutor(max_workers=workers) as pool, torch.no_grad():
+        decoded = {j: pool.submit(dataset.load_image, j) for j in range(min(ahead, n))}
+        for i in range(n):
+            if i + ahead < n:
+                decoded[i + ahead] = pool.submit(dataset.load_image, i + ahead)
+            t0 = time.perf_counter()
+            data = get_image_blob(decoded.pop(i).result(), device=device)
+            t1 = time.perf_counter()
+            handle = launch({'data': data['data'], 'im_info': data['im_info']})
+            pending.append((i, handle, data['im_info'][0], t1 - t0, time.perf_counter() - t1))
+            if len(pending) >= depth:
+                finish(*pending.pop(0))
+        while pending:
+            finish(*pending.pop(0))
+    results = {'all_boxes': all_boxes, 'all_masks': all_masks, 'all_ssegs': all_ssegs, 'all_panos': all_panos,
+               'all_pano_cls_inds': all_pano_cls_inds}
+    return results, times
+
+
+def evaluate_results(dataset, results, results_dir):
+    """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
+    {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran)."""
+    net = config.network
+    metrics = {}
+    if not dataset.has_gt:
+        logger.info('%s has no annotations (%s): evaluation skipped', dataset.name, os.path.basename(dataset.instances_json_file))
+        return metrics
+    os.makedirs(results_dir, exist_ok=True)
+    if net.has_rcnn:
+        metrics['box_ap'] = dataset.evaluate_boxes(results['all_boxes'], results_dir)
+    if net.has_rcnn and net.has_mask_head:
+        metrics['mask_ap'] = dataset.evaluate_masks(results['all_boxes'], results['all_masks'], results_dir).stats
+    if net.has_panoptic_head:
+        logger.info('unified pano result:')
+        order = dataset.panoptic_order()
+        pans = dataset.get_unified_pan_result([results['all_ssegs'][k] for k in order], [results['all_panos'][k] for k in order],
+                                              [results['all_pano_cls_inds'][k] for k in order],
+                                              stuff_area_limit=config.test.panoptic_stuff_area_limit)
+        metrics['panoptic'] = dataset.evaluate_panoptic(pans, os.path.join(results_dir, 'pans_unified'))
+    if net.has_fcn_head:
+        metrics['sseg'] = dataset.evaluate_ssegs(results['all_ssegs'], os.path.join(results_dir, 'ssegs'))
+    return metrics
+
+
+def main(argv=None):
+    """Returns {'metrics': ..., 'results_file': path, 'times': per-image timings (None with --eval_only)}."""
+    from .config.parse_args import parse_args
+    args = parse_args('UPSNet: run and score a checkpoint over an evaluation set', argv)
+    logging.basicConfig(level=logging.INFO, format='%(asctime)-15s | %(message)s')
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    if world > 1:
+        raise SystemExit('upsnet_amd.evaluate runs on one rank; WORLD_SIZE=%d is refused (sharding the image list across ranks is '
+                         'not implemented)' % world)
+    if not args.cfg:
+        raise SystemExit('--cfg <experiment yaml> is required: it names the dataset, the image set and the output path')
+    if args.weight_path and args.synthetic_weights:
+        raise SystemExit('--weight_path and --synthetic_weights exclude each other')
+    out_dir = final_output_path(args.cfg)
+    results_dir = os.path.join(out_dir, 'results')
+    results_file = os.path.join(results_dir, 'results_list.pkl')
+    if args.eval_only:
+        if not os.path.isfile(results_file):
+            raise SystemExit('--eval_only: no results to evaluate at %s (run without --eval_only first)' % results_file)
+        dataset = build_dataset(out_dir)
+        dataset.check_files(images=False)
+        with open(results_file, 'rb') as f:
+            results = pickle.load(f)
+        return {'metrics': evaluate_results(dataset, results, results_dir), 'results_file': results_file, 'times': None}
+
+    dataset = build_dataset(out_dir)
+    dataset.check_files()       # every image and GT file, before the first launch
+    from .upsnet_end2end_test import init_distributed, load_checkpoint_model
+    _, _, device = init_distributed()
+    if args.synthetic_weights:
+        from .synthetic import build_model
+        logging.warning('seeded SYNTHETIC weights (upsnet_amd.synthetic, seed 235): the metrics are not those of a trained model')
+        model = build_model(device=device)
+    else:
+        weight_path = args.weight_path or default_weight_path(args.cfg)
+        model = load_checkpoint_model(weight_path, device)
+        logging.info('loaded %s into %s (resume=True)', weight_path, config.symbol)
+    results, times = run_inference(model, dataset, in_flight=args.in_flight, device=device)
+    os.makedirs(results_dir, exist_ok=True)
+    with open(results_file, 'wb') as f:
+        pickle.dump(results, f, protocol=2)
+    logging.info('%d images, results written to %s', len(dataset), results_file)
+    return {'metrics': evaluate_results(dataset, results, results_dir), 'results_file': results_file, 'times': times}
+
+
+if __name__ == '__main__':
+    main()

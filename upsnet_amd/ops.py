@@ -1181,6 +1181,36 @@ def prep_image_u8(image_hwc, pixel_means, im_scale, resized_hw, padded_hw, nhwc4
     return out
 
 
+def restore_label_maps(sseg, pano, y_ofs, x_ofs):
+    """Nearest-neighbour gather of one image's label maps (include/upsnet_hip.h: upsnet_restore_label_maps): sseg / pano int64 [H,W]
+    or [1,H,W] device tensors (pano may be None; rows may be strided, columns contiguous), y_ofs / x_ofs int32 index tables (host
+    or device; dataset/restore.py builds them). Returns (uint8 [len(y_ofs), len(x_ofs)] for sseg, the same for pano or None);
+    out[y, x] = low byte of src[y_ofs[y], x_ofs[x]]. Both maps come out of one launch."""
+    require_cuda(sseg, pano)
+    maps = [m.reshape(m.shape[-2], m.shape[-1]) if m is not None else None for m in (sseg, pano)]
+    for m in maps:
+        if m is not None and (m.dtype != torch.int64 or m.stride(1) != 1):
+            raise ValueError("restore_label_maps: int64 maps with contiguous rows required, got %s stride %s" % (m.dtype, m.stride()))
+    s, p = maps
+    if p is not None and (p.shape != s.shape or p.stride() != s.stride()):
+        s, p = s.contiguous(), p.contiguous()
+    H, W = s.shape
+    ys = torch.as_tensor(y_ofs, dtype=torch.int32).reshape(-1)
+    xs = torch.as_tensor(x_ofs, dtype=torch.int32).reshape(-1)
+    for name, t, n in (("y_ofs", ys, H), ("x_ofs", xs, W)):
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise ValueError("restore_label_maps: %s outside 0..%d" % (name, n - 1))
+    ys, xs = ys.to(s.device).contiguous(), xs.to(s.device).contiguous()
+    H0, W0 = ys.numel(), xs.numel()
+    out_s = torch.empty((H0, W0), dtype=torch.uint8, device=s.device)
+    out_p = torch.empty((H0, W0), dtype=torch.uint8, device=s.device) if p is not None else None
+    if H0 == 0 or W0 == 0:
+        return out_s, out_p
+    check(lib().upsnet_restore_label_maps(stream(), ptr(s), ptr(p), int(s.stride(0)), H, W, ptr(ys), H0, ptr(xs), W0, ptr(out_s),
+                                          ptr(out_p)), "restore_label_maps")
+    return out_s, out_p
+
+
 def unified_pan_result(pan, seg, cls_inds, id_last_stuff, num_seg_classes, stuff_area_limit=4 * 64 * 64):
     """get_unified_pan_result of ONE image on the device: pan / seg int64 [H,W] (or [1,H,W]), cls_inds int64 [k] -> uint8 [H,W,3]."""
     require_cuda(pan, seg)
