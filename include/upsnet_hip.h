@@ -672,6 +672,25 @@ int upsnet_unified_pan_result(void *stream, const int64_t *pan, const int64_t *s
                               int height, int width, int id_last_stuff, int num_seg_classes, int stuff_area_limit,
                               void *workspace, unsigned char *pan_2ch);
 
+/* BaseDataset.get_combined_pan_result (upsnet/dataset/base_dataset.py:373-449) for a chunk of images in one call, on the device:
+ * the instance masks pasted greedily in merge order, then merged with the semantic map.
+ *   images int64 [num_images][8]: height, width, seg (device address of a uint8 [height][width] semantic map), out (device address
+ *     of a uint8 [height][width][3] result), first candidate, end of candidates, occupancy word offset (sum of ceil(h * w / 64)
+ *     over the earlier images), pixel offset (sum of h * w over the earlier images); every image has 1..2^24 pixels;
+ *   cand int32 [n][4]: (class 1..num_classes-1, pixel count > 0, first segment, end of segments), each image's candidates in merge
+ *     order (score descending), at most 255 per class; segments int32 [m][2]: column-major pixel ranges [a, b) (p = x * h + y) of
+ *     the mask's ones, ascending, none crossing a multiple of 4096; cand / segments may be NULL when there are no candidates.
+ * A candidate is accepted iff (float)(remain / area) >= fraction_threshold compared in double (remain = its pixels no earlier
+ * accepted candidate claimed); accepted ones are numbered per class from 1 and claim their remaining pixels. out: channel 0 =
+ * id_last_stuff + class on claimed pixels, else 255 where seg > id_last_stuff or seg is a stuff label with fewer than
+ * stuff_area_limit pixels, else seg; channel 1 = instance number (0 if unclaimed); channel 2 = 0.
+ * workspace: upsnet_combined_pan_workspace_bytes(num_images, total_pixels) bytes (total_pixels = sum of h * w), 256-byte aligned.
+ * Four launches on `stream` (one memset), no host synchronisation. */
+size_t upsnet_combined_pan_workspace_bytes(int num_images, long total_pixels);
+int upsnet_combined_pan_result(void *stream, int num_images, const int64_t *images, int max_height, int max_width, long total_pixels,
+                               const int *cand, const int *segments, int id_last_stuff, int num_classes, int stuff_area_limit,
+                               double fraction_threshold, void *workspace);
+
 /* im_post (upsnet/upsnet_end2end_test.py:95-152) without the full-image pass per detection: for detection d the mask
  * probability of its class (mask_prob [n, C, M, M]; C == 1: class-agnostic) is zero-padded to (M+2)^2, resized (cv2
  * INTER_LINEAR) to the box expanded by (M+2)/M and truncated to int32 (expand_boxes, bbox_transform.py:365-381), thresholded

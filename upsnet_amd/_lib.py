@@ -98,6 +98,8 @@ _SIGNATURES = {
     "upsnet_image_to_nhwc4": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "upsnet_unified_pan_workspace_bytes": (c_size_t, []),
     "upsnet_unified_pan_result": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "upsnet_combined_pan_workspace_bytes": (c_size_t, [c_int, c_long]),
+    "upsnet_combined_pan_result": (c_int, [P, c_int, P, c_int, c_int, c_long, P, P, c_int, c_int, c_int, c_double, P]),
     "upsnet_mask_roi_dedup": (c_int, [P, P, P, P, c_int, P, P, P, P, c_int, P, P, P]),
     "upsnet_conv2d_winograd_nhwc_f32": (c_int, [P, c_int, P, P, P, P, P, P, c_int, P, c_int, P, c_int, c_int]),
     "upsnet_conv2d_winograd_nhwc_f32_splitk": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P]),

@@ -18,6 +18,8 @@ def parse_args(description='', argv=None):
     parser.add_argument('--steps', type=int, default=20)
     parser.add_argument('--warmup', type=int, default=10)
     parser.add_argument('--in-flight', type=int, default=1, help='images in flight per rank (1 = the reference loop)')
+    parser.add_argument('--pan_combined', action='store_true',
+                        help='also score the combined (heuristic merge) panoptic result of the detections and the semantic map')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)

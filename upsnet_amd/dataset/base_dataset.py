@@ -1,5 +1,6 @@
 """Post-processing and evaluation of the network outputs -- host mirror of the reference's BaseDataset methods after the inference
-path: get_unified_pan_result (upsnet/dataset/base_dataset.py:332-371, csrc/postprocess.hip), evaluate_panoptic (:209-330, PQ through
+path: get_unified_pan_result (upsnet/dataset/base_dataset.py:332-371, csrc/postprocess.hip), get_combined_pan_result (:373-449,
+csrc/pan_combine.hip), evaluate_panoptic (:209-330, PQ through
 dataset/pq.py and csrc/pq_eval.hip) with its PQStat / PQStatCat host classes (:44-96), and get_confusion_matrix (:806-824) plus the
 mIoU of evaluate_ssegs (cityscapes.py:445-492), all counting on the device."""
 import json
@@ -107,6 +108,24 @@ class BaseDataset(object):
             seg, pan, cls_ind = (torch.as_tensor(t).to(dev) for t in (seg, pan, cls_ind))
             out.append(ops.unified_pan_result(pan, seg, cls_ind, id_last_stuff, config.dataset.num_seg_classes, stuff_area_limit))
         return out
+
+    def get_combined_pan_result(self, segs, boxes, masks, score_threshold=0.6, fraction_threshold=0.7, stuff_area_limit=4 * 64 * 64):
+        """The heuristic panoptic merge (reference :373-449) on the device, all images in one call (ops.combined_pan_result,
+        csrc/pan_combine.hip). segs: per-image semantic maps [H,W] (numpy or tensor, uint8 or int64 in 0..255); boxes[c][i]: [n,5]
+        arrays and masks[c][i]: lists of RLE dicts for c = 1..num_classes-1. Returns a list of uint8 [H,W,3] device tensors
+        (channel 0 category, channel 1 instance id), like get_unified_pan_result. Pinned where the reference is ambiguous:
+          - merge order: classes 1..C-1 concatenated, np.argsort(score, kind='stable')[::-1] (ties: the later candidate first);
+          - a candidate is skipped iff float(score) < score_threshold (double: numpy 1.x promotion);
+          - zero-area masks are skipped and use no instance number; otherwise a mask is rejected iff the float32 quotient
+            remain / area is < fraction_threshold compared in double (numpy 1.x; numpy 2 compares in float32 and accepts
+            remain / area == fl32(fraction_threshold), e.g. 7 / 10 against 0.7);
+          - instances are numbered per class from 1 in acceptance order.
+        ValueError before any launch: more than 255 candidates of one class at or above the score threshold, an image of more
+        than 2^24 pixels, a mask size or RLE counts sum that does not match its semantic map, boxes / masks of different lengths.
+        Images may differ in size; the inputs are never modified."""
+        id_last_stuff = config.dataset.num_seg_classes - config.dataset.num_classes
+        return ops.combined_pan_result(segs, boxes, masks, id_last_stuff, score_threshold=score_threshold,
+                                       fraction_threshold=fraction_threshold, stuff_area_limit=stuff_area_limit)
 
     def load_panoptic_gt(self):
         """(images, annotations, categories) of self.panoptic_json_file; images yields the uint8 [H,W,3] GT PNGs of

@@ -74,3 +74,41 @@ def im_post(boxes_all, masks_all, scores, pred_boxes, pred_masks, cls_inds, num_
         segms = [{'size': [im_h, im_w], 'counts': rle_to_string(counts_from_transitions(trans[d], im_h * im_w))} for d in sel]
         boxes_all[idx].append(np.hstack([boxes_np[sel], scores_np[sel]]))
         masks_all[idx].append(segms)
+
+
+def _segmented_cumsum(v, starts):
+    """Cumulative sums of v restarted at every index where `starts` is set (starts[0] must be set)."""
+    cs = np.cumsum(v)
+    first = np.flatnonzero(starts)
+    return cs - (cs[first] - v[first])[np.cumsum(starts) - 1]
+
+
+def decode_rle_strings(strings):
+    """pycocotools' compressed RLE strings -> (counts int64, code offsets int64 [n + 1]): counts[off[j]:off[j+1]] are the counts of
+    strings[j], as dataset.coco_eval.rle_from_string returns them (rleFrString of maskApi.c), decoded for all strings at once with
+    array operations. A string whose last character continues a code raises ValueError."""
+    enc = [s if isinstance(s, bytes) else s.encode('ascii') for s in strings]
+    n = len(enc)
+    lens = np.fromiter((len(s) for s in enc), np.int64, n)
+    c = np.frombuffer(b''.join(enc), np.uint8).astype(np.int64) - 48
+    end = (c & 0x20) == 0                                   # the character ends a code
+    char_end = np.cumsum(lens)
+    if np.any(lens > 0) and not np.all(end[char_end[lens > 0] - 1]):
+        raise ValueError("RLE string ends inside a code")
+    code_first = np.flatnonzero(np.concatenate([[True], end[:-1]])) if c.size else np.zeros(0, np.int64)
+    code_of = np.cumsum(end) - end                          # code index of every character
+    k = np.arange(c.size) - code_first[code_of]             # position of the character in its code
+    x = np.add.reduceat((c & 0x1f) << (5 * k), code_first) if c.size else np.zeros(0, np.int64)
+    ln = np.diff(np.concatenate([code_first, [c.size]]))
+    neg = (c[code_first + ln - 1] & 0x10) != 0
+    x[neg] -= np.left_shift(1, 5 * ln[neg])                 # x |= -1 << 5 k on the (non-negative) value
+    off = np.concatenate([[0], np.cumsum(end)])[np.concatenate([[0], char_end])].astype(np.int64)
+    codes_per = np.diff(off)
+    j = np.arange(x.size) - np.repeat(off[:-1], codes_per)  # index of the code in its string
+    counts = x.copy()
+    # counts[j] = x[j] + counts[j - 2] for j > 2: per string, cumulative sums over j = 1, 3, 5, ... and over j = 2, 4, 6, ...
+    for sel, starts in (((j & 1) == 1, j == 1), ((j & 1) == 0, (j == 0) | (j == 2))):
+        idx = np.flatnonzero(sel)
+        if idx.size:
+            counts[idx] = _segmented_cumsum(x[idx], starts[idx])
+    return counts, off

@@ -1,7 +1,7 @@
 """Run and score a checkpoint over a Cityscapes or COCO evaluation set: the reference's test command over a real image list
 (upsnet/upsnet_end2end_test.py:155-314).
 
-    python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N]
+    python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
 
 The dataset is `config.dataset.dataset` (Cityscapes or coco) on `config.dataset.test_image_set`. Every image and every GT file the
 configured heads need is checked before the first launch. Images are decoded by a bounded host thread pool ahead of the device;
@@ -10,7 +10,8 @@ graphs, a new shape / im_info runs eagerly). Per image, as the reference's im_de
 scaled by 1 / im_scale in float32, masks run-length encoded by dataset/rle.im_post, the semantic and panoptic maps restored to the
 original resolution by one gather launch (csrc/restore.hip, cv2 INTER_NEAREST tables). The results pickle has the reference's
 path, keys and nesting (numpy objects only); evaluation follows the reference's order: boxes, masks, panoptic, semantic.
-`--eval_only` re-scores the pickle without building the model. One rank only (WORLD_SIZE > 1 is refused)."""
+`--eval_only` re-scores the pickle without building the model. `--pan_combined` also scores get_combined_pan_result (the
+heuristic merge of the detections and the semantic map) next to the unified result. One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
 import pickle
@@ -131,9 +132,10 @@ def run_inference(model, dataset, in_flight=1, device=None):
     return results, times
 
 
-def evaluate_results(dataset, results, results_dir):
+def evaluate_results(dataset, results, results_dir, pan_combined=False):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
-    {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran)."""
+    {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
+    'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined."""
     net = config.network
     metrics = {}
     if not dataset.has_gt:
@@ -151,6 +153,14 @@ def evaluate_results(dataset, results, results_dir):
                                               [results['all_pano_cls_inds'][k] for k in order],
                                               stuff_area_limit=config.test.panoptic_stuff_area_limit)
         metrics['panoptic'] = dataset.evaluate_panoptic(pans, os.path.join(results_dir, 'pans_unified'))
+    if pan_combined:
+        logger.info('combined pano result:')
+        order = dataset.panoptic_order()
+        def ordered(per_class):
+            return [[v[k] for k in order] if c else v for c, v in enumerate(per_class)]
+        pans = dataset.get_combined_pan_result([results['all_ssegs'][k] for k in order], ordered(results['all_boxes']),
+                                               ordered(results['all_masks']), stuff_area_limit=config.test.panoptic_stuff_area_limit)
+        metrics['panoptic_combined'] = dataset.evaluate_panoptic(pans, os.path.join(results_dir, 'pans_combined'))
     if net.has_fcn_head:
         metrics['sseg'] = dataset.evaluate_ssegs(results['all_ssegs'], os.path.join(results_dir, 'ssegs'))
     return metrics
@@ -169,6 +179,11 @@ def main(argv=None):
         raise SystemExit('--cfg <experiment yaml> is required: it names the dataset, the image set and the output path')
     if args.weight_path and args.synthetic_weights:
         raise SystemExit('--weight_path and --synthetic_weights exclude each other')
+    net = config.network
+    if args.pan_combined and not (net.has_rcnn and net.has_mask_head and net.has_fcn_head):
+        raise SystemExit('--pan_combined merges detections, instance masks and the semantic map: it needs network.has_rcnn, '
+                         'has_mask_head and has_fcn_head (has_rcnn=%s, has_mask_head=%s, has_fcn_head=%s)'
+                         % (net.has_rcnn, net.has_mask_head, net.has_fcn_head))
     out_dir = final_output_path(args.cfg)
     results_dir = os.path.join(out_dir, 'results')
     results_file = os.path.join(results_dir, 'results_list.pkl')
@@ -179,7 +194,7 @@ def main(argv=None):
         dataset.check_files(images=False)
         with open(results_file, 'rb') as f:
             results = pickle.load(f)
-        return {'metrics': evaluate_results(dataset, results, results_dir), 'results_file': results_file, 'times': None}
+        return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined), 'results_file': results_file, 'times': None}
 
     dataset = build_dataset(out_dir)
     dataset.check_files()       # every image and GT file, before the first launch
@@ -198,7 +213,7 @@ def main(argv=None):
     with open(results_file, 'wb') as f:
         pickle.dump(results, f, protocol=2)
     logging.info('%d images, results written to %s', len(dataset), results_file)
-    return {'metrics': evaluate_results(dataset, results, results_dir), 'results_file': results_file, 'times': times}
+    return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined), 'results_file': results_file, 'times': times}
 
 
 if __name__ == '__main__':

@@ -1228,6 +1228,171 @@ def unified_pan_result(pan, seg, cls_inds, id_last_stuff, num_seg_classes, stuff
     return out
 
 
+COMBINED_PAN_CHUNK_IMAGES = 256          # images per launch (one workgroup each in the greedy kernel)
+COMBINED_PAN_CHUNK_PIXELS = 1 << 28      # pixels per launch: bounds the workspace (2.1 bytes per pixel)
+_SEG_BLOCK = 4096                        # segments of a run never cross a multiple of this (csrc/pan_combine.hip)
+
+
+def _combined_seg_u8(seg, dev):
+    """One semantic map -> (uint8 [H,W] tensor on dev, or None with a pending (min, max) range check); never modifies the input."""
+    if isinstance(seg, torch.Tensor):
+        t = seg
+    else:
+        a = np.asarray(seg)
+        if a.ndim == 2 and a.dtype != np.uint8 and a.size:
+            if not np.issubdtype(a.dtype, np.integer) or int(a.min()) < 0 or int(a.max()) > 255:
+                raise ValueError("combined_pan_result: semantic labels must be integers in 0..255")
+            a = a.astype(np.uint8)
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dim() != 2:
+        raise ValueError("combined_pan_result: semantic maps must be [H,W], got %s" % (tuple(t.shape),))
+    if t.dtype != torch.uint8 and (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool):
+        raise ValueError("combined_pan_result: semantic maps must be uint8 or int64, got %s" % t.dtype)
+    return t.to(dev)
+
+
+def combined_pan_result(segs, boxes, masks, id_last_stuff, score_threshold=0.6, fraction_threshold=0.7, stuff_area_limit=4 * 64 * 64):
+    """BaseDataset.get_combined_pan_result on the device (csrc/pan_combine.hip; DESIGN 4.7 for the pinned semantics).
+
+    segs: per-image semantic maps [H,W] (numpy or tensor, uint8 or int64 with values 0..255); boxes[c][i]: [n,5] (x1 y1 x2 y2 score)
+    and masks[c][i]: n RLE dicts {'size': [H, W], 'counts': str | bytes} for classes c = 1..len(boxes)-1 (entry 0 is ignored).
+    Candidates: classes concatenated in order, np.argsort(score, kind='stable')[::-1], those with float(score) < score_threshold
+    dropped. Returns a list of uint8 [H,W,3] device tensors. Every ValueError is raised before the first launch; inputs are never
+    modified."""
+    from .dataset.rle import _segmented_cumsum, decode_rle_strings
+    n = len(segs)
+    if len(boxes) != len(masks):
+        raise ValueError("combined_pan_result: %d classes of boxes, %d of masks" % (len(boxes), len(masks)))
+    num_classes = len(boxes)
+    if num_classes < 2 or id_last_stuff < 0 or id_last_stuff + num_classes - 1 >= 255:
+        raise ValueError("combined_pan_result: %d classes after id_last_stuff %d do not fit the uint8 labels" % (num_classes, id_last_stuff))
+    for c in range(1, num_classes):
+        if len(boxes[c]) != n or len(masks[c]) != n:
+            raise ValueError("combined_pan_result: class %d has boxes for %d and masks for %d of %d images" % (c, len(boxes[c]), len(masks[c]), n))
+    if n == 0:
+        return []
+    dev = next((s.device for s in segs if isinstance(s, torch.Tensor) and s.is_cuda), None) or torch.device('cuda', torch.cuda.current_device())
+    seg_t = [_combined_seg_u8(s, dev) for s in segs]
+    wide = [t for t in seg_t if t.dtype != torch.uint8 and t.numel()]
+    if wide:   # one host synchronisation for all non-uint8 maps of the call
+        r = torch.stack([torch.stack([t.min(), t.max()]).to(torch.int64) for t in wide]).cpu()
+        if int(r[:, 0].min()) < 0 or int(r[:, 1].max()) > 255:
+            raise ValueError("combined_pan_result: semantic labels must be integers in 0..255")
+    seg_t = [t.to(torch.uint8).contiguous() for t in seg_t]
+    thr = float(score_threshold)
+    strings, cls_of, npix_of, img_ncand = [], [], [], []
+    for i, t in enumerate(seg_t):
+        H, W = int(t.shape[0]), int(t.shape[1])
+        if H * W > (1 << 24):
+            raise ValueError("combined_pan_result: image %d has %d x %d pixels; the pixel counts are exact only up to 2^24" % (i, H, W))
+        sc, cl, rl = [], [], []
+        for c in range(1, num_classes):
+            b, m = boxes[c][i], masks[c][i]
+            b = np.asarray(b)
+            nb = b.shape[0] if b.size else 0
+            if nb != len(m):
+                raise ValueError("combined_pan_result: image %d class %d: %d boxes, %d masks" % (i, c, nb, len(m)))
+            if nb:
+                if b.ndim != 2 or b.shape[1] < 5:
+                    raise ValueError("combined_pan_result: image %d class %d: boxes must be [n,5], got %s" % (i, c, b.shape))
+                sc.append(b[:, 4].astype(np.float64))
+                cl.append(np.full(nb, c, np.int32))
+                rl.extend(m)
+        for r in rl:
+            if not isinstance(r, dict) or [int(v) for v in r.get('size', ())] != [H, W]:
+                raise ValueError("combined_pan_result: image %d: mask size %s differs from the semantic map's %s" %
+                                 (i, r.get('size') if isinstance(r, dict) else type(r), [H, W]))
+        if sc:
+            s = np.concatenate(sc)
+            order = np.argsort(s, kind='stable')[::-1]
+            order = order[~(s[order] < thr)]
+            cls = np.concatenate(cl)[order]
+            per = np.bincount(cls, minlength=num_classes)
+            if per.max(initial=0) > 255:
+                raise ValueError("combined_pan_result: image %d class %d has %d candidates at or above the score threshold; the "
+                                 "instance ids are uint8" % (i, int(per.argmax()), int(per.max())))
+            for k in order:
+                cnt = rl[k]['counts']
+                if not isinstance(cnt, (str, bytes)):
+                    raise ValueError("combined_pan_result: image %d: RLE counts must be a compressed string" % i)
+                strings.append(cnt)
+            cls_of.append(cls)
+        npix_of.append(np.full(len(order) if sc else 0, H * W, np.int64))
+        img_ncand.append(len(order) if sc else 0)
+    cls_all = np.concatenate(cls_of) if cls_of else np.zeros(0, np.int32)
+    npix_all = np.concatenate(npix_of)
+    counts, off = decode_rle_strings(strings)
+    ncodes = np.diff(off)
+    str_of = np.repeat(np.arange(len(strings)), ncodes)
+    if counts.size and counts.min() < 0:
+        raise ValueError("combined_pan_result: negative RLE count (string %d)" % int(str_of[np.argmax(counts < 0)]))
+    total = np.bincount(str_of, weights=counts.astype(np.float64), minlength=len(strings))   # exact: sums below 2^53
+    bad = np.flatnonzero(total != npix_all)
+    if bad.size:
+        raise ValueError("combined_pan_result: RLE counts of candidate %d sum to %d, not H * W = %d" %
+                         (int(bad[0]), int(total[bad[0]]), int(npix_all[bad[0]])))
+    # runs of ones: [end of count j-1, end of count j) for odd j in each string
+    first = np.zeros(counts.size, bool)
+    first[off[:-1][ncodes > 0]] = True
+    pos = _segmented_cumsum(counts, first) if counts.size else counts
+    j = np.arange(counts.size) - np.repeat(off[:-1], ncodes)
+    odd = np.flatnonzero(((j & 1) == 1) & (counts > 0))
+    run_b = pos[odd]
+    run_a = run_b - counts[odd]
+    run_str = str_of[odd]
+    area = np.bincount(run_str, weights=(run_b - run_a).astype(np.float64), minlength=len(strings)).astype(np.int64)
+    # cut runs at multiples of _SEG_BLOCK
+    blk_a, blk_b = run_a // _SEG_BLOCK, (run_b - 1) // _SEG_BLOCK
+    nseg = blk_b - blk_a + 1
+    run_idx = np.repeat(np.arange(run_a.size), nseg)
+    blk = blk_a[run_idx] + (np.arange(run_idx.size) - np.repeat(np.cumsum(nseg) - nseg, nseg))
+    seg_a = np.maximum(run_a[run_idx], blk * _SEG_BLOCK)
+    seg_b = np.minimum(run_b[run_idx], (blk + 1) * _SEG_BLOCK)
+    seg_str = run_str[run_idx]
+    seg_cnt = np.bincount(seg_str, minlength=len(strings))
+    keep = area > 0                          # zero-area candidates are skipped and use no instance number
+    cand_img = np.repeat(np.arange(n), img_ncand)
+    out = [torch.empty((int(t.shape[0]), int(t.shape[1]), 3), dtype=torch.uint8, device=dev) for t in seg_t]
+    # chunks of images (all with pixels): one workspace, four launches per chunk
+    live = [i for i in range(n) if seg_t[i].numel()]
+    chunks, cur, cur_pix = [], [], 0
+    for i in live:
+        p = seg_t[i].numel()
+        if cur and (len(cur) >= COMBINED_PAN_CHUNK_IMAGES or cur_pix + p > COMBINED_PAN_CHUNK_PIXELS):
+            chunks.append(cur)
+            cur, cur_pix = [], 0
+        cur.append(i)
+        cur_pix += p
+    if cur:
+        chunks.append(cur)
+    for ch in chunks:
+        in_chunk = keep & np.isin(cand_img, ch)
+        sel = np.flatnonzero(in_chunk)                          # candidates of the chunk, in image then merge order
+        cbeg = np.concatenate([[0], np.cumsum(np.bincount(np.searchsorted(ch, cand_img[sel]), minlength=len(ch)))])
+        segs_sel = np.flatnonzero(in_chunk[seg_str])           # their segments, in the same order
+        c_seg_end = np.cumsum(seg_cnt[sel])
+        cand = np.stack([cls_all[sel], area[sel], c_seg_end - seg_cnt[sel], c_seg_end], 1).astype(np.int32) if sel.size else None
+        segs_np = np.stack([seg_a[segs_sel], seg_b[segs_sel]], 1).astype(np.int32) if segs_sel.size else None
+        hw = np.array([[int(seg_t[i].shape[0]), int(seg_t[i].shape[1])] for i in ch], np.int64)
+        npx = hw[:, 0] * hw[:, 1]
+        img = np.zeros((len(ch), 8), np.int64)
+        img[:, 0:2] = hw
+        img[:, 2] = [seg_t[i].data_ptr() for i in ch]
+        img[:, 3] = [out[i].data_ptr() for i in ch]
+        img[:, 4], img[:, 5] = cbeg[:-1], cbeg[1:]
+        img[:, 6] = np.concatenate([[0], np.cumsum((npx + 63) // 64)[:-1]])
+        img[:, 7] = np.concatenate([[0], np.cumsum(npx)[:-1]])
+        total_pix = int(npx.sum())
+        img_d = torch.from_numpy(img).to(dev)
+        cand_d = torch.from_numpy(cand).to(dev) if cand is not None else None
+        segs_d = torch.from_numpy(segs_np).to(dev) if segs_np is not None else None
+        ws = torch.empty((int(lib().upsnet_combined_pan_workspace_bytes(len(ch), total_pix)),), dtype=torch.uint8, device=dev)
+        check(lib().upsnet_combined_pan_result(stream(), len(ch), ptr(img_d), int(hw[:, 0].max()), int(hw[:, 1].max()), total_pix,
+                                               ptr(cand_d), ptr(segs_d), int(id_last_stuff), num_classes, int(stuff_area_limit),
+                                               float(fraction_threshold), ptr(ws)), "combined_pan_result")
+    return out
+
+
 def pq_workspace(max_gt, device):
     """Zeroed workspace of pq_accumulate for images of at most max_gt GT segments (0..4096); every call leaves it zeroed again."""
     nbytes = int(lib().upsnet_pq_workspace_bytes(int(max_gt)))
