@@ -73,6 +73,25 @@ def check_taps(taps, enable_void=True):
     return res
 
 
+def softmax_fuse_non_ties(fcn, s_stuff, seg_inst, mask_energy, pan, pan_ref):
+    """The softmax branch of the panoptic fusion (resnet_upsnet.py:242-243, enable_void=False) may differ from torch's
+    argmax(softmax(cat([seg, inst + energy]))) only where torch's fp32 probabilities of the two labels are bit-identical (an argmax
+    over an exact tie). fcn [1,S,H,W], seg_inst / mask_energy [1,k,H,W], pan / pan_ref [1,H,W] or [H,W] (pan_ref: torch's labels).
+    Recomputes torch's softmax on the host with the fixture generator's own expression and returns every differing pixel that is NOT
+    such a tie as (y, x, label, ref_label, p[label], p[ref_label])."""
+    fcn, inst, energy = (torch.as_tensor(np.asarray(a, np.float32)) for a in (fcn, seg_inst, mask_energy))
+    p = torch.softmax(torch.cat([fcn[:, :s_stuff], inst + energy], dim=1), dim=1)[0]
+    pan, pan_ref = np.asarray(pan).reshape(p.shape[1:]), np.asarray(pan_ref).reshape(p.shape[1:])
+    bad = []
+    for y, x in np.argwhere(pan != pan_ref):
+        a, b = int(pan[y, x]), int(pan_ref[y, x])
+        pa = float(p[a, y, x]) if 0 <= a < p.shape[0] else float('nan')
+        pb = float(p[b, y, x])
+        if not pa == pb:
+            bad.append((int(y), int(x), a, b, pa, pb))
+    return bad
+
+
 # ----------------------------------------------------------------------------- pure CPU forward
 def _dcn_cpu(layer, x, relu=True):
     """DeformConvWithOffset on the host: torch-CPU offset conv + oracle im2col + GEMM."""

@@ -103,6 +103,30 @@ def test_panoptic_head():
     pan2, _ = oracle.panoptic_fuse(g["fcn"][0], 11, inst[0], energy[0], False)
     # argmax(softmax(x)) through torch's own softmax: allow the (rare) rounding-tie pixels, report them
     assert (pan2 != g["pan_softmax"][0]).mean() < 1e-3
+    # ... and every one of them an exact tie of torch's fp32 probabilities
+    from oracle.forward import softmax_fuse_non_ties
+    assert softmax_fuse_non_ties(g["fcn"], 11, inst, energy, pan2, g["pan_softmax"]) == []
+
+
+def test_softmax_fuse_tie_check_rejects_a_non_tie():
+    """The tie check of test_panoptic_head fails on one pixel moved to a label whose probability is not bit-identical."""
+    import torch
+    from oracle.forward import softmax_fuse_non_ties
+    g = load("panoptic_head")
+    p = torch.softmax(torch.cat([torch.from_numpy(g["fcn"][:, :11]), torch.from_numpy(g["seg_inst"] + g["energy"])], dim=1), dim=1)[0]
+    top2 = p.topk(2, dim=0)
+    ref = g["pan_softmax"]
+    assert np.array_equal(top2.indices[0].numpy(), ref[0])
+    args = (g["fcn"], 11, g["seg_inst"], g["energy"])
+    assert softmax_fuse_non_ties(*args, ref.copy(), ref) == []
+    y, x = 37, 59
+    assert top2.values[0, y, x] != top2.values[1, y, x]
+    pan = ref.copy()
+    pan[0, y, x] = int(top2.indices[1, y, x])
+    assert softmax_fuse_non_ties(*args, pan, ref) == [(y, x, int(pan[0, y, x]), int(ref[0, y, x]), float(top2.values[1, y, x]),
+                                                       float(top2.values[0, y, x]))]
+    # still under the 1e-3 share the older assertion allows: that one alone would not have seen it
+    assert (pan != ref).mean() < 1e-3
 
 
 def test_input_blob_golden_from_reference_python():

@@ -96,3 +96,6 @@ def test_panoptic_head_golden():
     assert np.array_equal(pan.cpu().numpy(), g["pan_void"])
     pan_sm, _ = ops.panoptic_fuse(fcn, 11, rois5, logit, cls, k, n, r, cmap, False)
     assert (pan_sm.cpu().numpy() != g["pan_softmax"]).mean() < 1e-3
+    # every differing pixel an exact tie of torch's fp32 probabilities (its own labels: an argmax over equal values)
+    from oracle.forward import softmax_fuse_non_ties
+    assert softmax_fuse_non_ties(g["fcn"], 11, g["seg_inst"], g["energy"], pan_sm.cpu().numpy(), g["pan_softmax"]) == []

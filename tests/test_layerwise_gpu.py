@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from oracle.draws import DRAWS, fit_cls_gain
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
@@ -53,7 +55,7 @@ def _describe(rec):
                                          tuple(x.shape), rec['form'])
 
 
-def _check_model(preset, h, w, seed, need_forms, min_shapes, precision='fp32', wino36=True):
+def _check_model(preset, h, w, seed, need_forms, min_shapes, precision='fp32', wino36=True, weight_seed=235, cls_gain='default'):
     from upsnet_amd.config.config import update_config_dict, CITYSCAPES_R50
     from upsnet_amd.models import hipconv
     update_config_dict(preset)
@@ -61,7 +63,7 @@ def _check_model(preset, h, w, seed, need_forms, min_shapes, precision='fp32', w
     saved_w36, hipconv.WINO36 = hipconv.WINO36, wino36
     try:
         from upsnet_amd.synthetic import build_model, make_image
-        model = build_model()
+        model = build_model(seed=weight_seed, cls_gain=cls_gain)
         data = make_image(h, w, seed=seed, device='cuda')
         hipconv.TRACE, n_fallbacks = [], len(hipconv.FALLBACKS)
         try:
@@ -95,6 +97,7 @@ def _check_model(preset, h, w, seed, need_forms, min_shapes, precision='fp32', w
         assert len(hipconv.FALLBACKS) == n_fallbacks, hipconv.FALLBACKS[n_fallbacks:]
         print("%s%d launches, %d distinct layer shapes, forms %s, worst error / bound %.3f" %
               ('' if precision == 'fp32' else precision + ': ', len(trace), len(shapes), sorted(forms), worst_all))
+        return worst_all
     finally:
         hipconv.WINO36 = saved_w36
         hipconv.PRECISION = saved_precision
@@ -129,6 +132,26 @@ def test_every_convolution_launch_vs_fp64_on_identical_inputs_upsnet101_dcn(h, w
     # (r13) at 800x1333 the small-tile kernels carry the bottlenecks' conv1 layers / the P5 lateral (conv1x1 ksw) and the offset predictors of res4 / res5
     # (conv3x3 ksw): each of those launches is replayed in float64 like every other one
     _check_model(COCO_R101_DCN, h, w, seed=4, need_forms=['stem', 'deconv2x2', 'dcn_fused'] + (['conv1x1 ksw', 'conv3x3 ksw'] if h >= 800 else []), min_shapes=30)
+
+
+@pytest.mark.parametrize("weight_seed,image_seed", DRAWS)
+def test_every_convolution_launch_vs_fp64_upsnet50_other_draws(weight_seed, image_seed):
+    """The 1024x2048 replay above on the draws of oracle.draws.DRAWS (classifier gain oracle.draws.fit_cls_gain): other weights, other
+    activations, other ROI counts -- so other mask-head batches and tails of the F(4x4) ROI launches; every C1 form still required."""
+    from upsnet_amd.config.config import CITYSCAPES_R50
+    worst = _check_model(CITYSCAPES_R50, 1024, 2048, seed=image_seed, need_forms=_C1_FORMS, min_shapes=35, weight_seed=weight_seed,
+                         cls_gain=fit_cls_gain)
+    print('margins {"tag": "upsnet50 1024x2048 draw (%d, %d)", "layerwise_worst": %.3f}' % (weight_seed, image_seed, worst))
+
+
+@pytest.mark.parametrize("weight_seed,image_seed", DRAWS)
+def test_every_convolution_launch_vs_fp64_upsnet101_dcn_other_draws(weight_seed, image_seed):
+    """UPSNet-101-DCN at 800x1333 on the draws of oracle.draws.DRAWS: every launch, the 30 deformable bottlenecks at their recorded
+    offsets included, strictly within 1e-4 of its float64 replay."""
+    from upsnet_amd.config.config import COCO_R101_DCN
+    worst = _check_model(COCO_R101_DCN, 800, 1333, seed=image_seed, need_forms=['stem', 'deconv2x2', 'dcn_fused', 'conv1x1 ksw', 'conv3x3 ksw'],
+                         min_shapes=30, weight_seed=weight_seed, cls_gain=fit_cls_gain)
+    print('margins {"tag": "upsnet101dcn 800x1333 draw (%d, %d)", "layerwise_worst": %.3f}' % (weight_seed, image_seed, worst))
 
 
 # ----------------------------------------------------------------------------- bf16 mode (BASELINE.json configs[2]) and configs[4]

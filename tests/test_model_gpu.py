@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from oracle.draws import DRAWS, fit_cls_gain
+
 pytestmark = pytest.mark.gpu
 
 
@@ -206,6 +208,32 @@ def test_coco_r101_dcn_at_1024x2048_stagewise_parity():
         assert all(res.values()), (res, counts)
         assert counts['label_mismatch'] == 0 and counts['n_rois'] <= 300 and counts['n_det'] >= 1, counts
         assert out['panoptic_outputs'].shape == (1, 1024, 2048)
+    finally:
+        update_config_dict(CITYSCAPES_R50)
+
+
+@pytest.mark.parametrize("weight_seed,image_seed", DRAWS)
+@pytest.mark.parametrize("preset,h,w", [('CITYSCAPES_R50', 1024, 2048), ('COCO_R101_DCN', 800, 1333)])
+def test_stagewise_parity_on_other_draws(preset, h, w, weight_seed, image_seed):
+    """Both benchmark configurations on the draws of oracle.draws.DRAWS (classifier gain oracle.draws.fit_cls_gain): other proposals, NMS
+    ties, MaskROI outputs, mask-removal keeps and panoptic counts than the seed-235 network of the tests above -- every custom-op
+    stage bit-identical to the oracle, label map included, with at least 5 instances in the panoptic output."""
+    from oracle.forward import check_taps
+    from upsnet_amd.config import config as cfgmod
+    from upsnet_amd.config.config import update_config_dict, CITYSCAPES_R50
+    update_config_dict(getattr(cfgmod, preset))
+    try:
+        from upsnet_amd.synthetic import build_model, make_image
+        model = build_model(seed=weight_seed, cls_gain=fit_cls_gain)
+        data = make_image(h, w, seed=image_seed, device='cuda')
+        model.taps = {}
+        with torch.no_grad():
+            model(data)
+        res = check_taps(model.taps, enable_void=True)
+        counts = res.pop('counts')
+        assert all(res.values()), (res, counts)
+        assert counts['label_mismatch'] == 0 and counts['n_inst'] >= 5, counts
+        print('%s %dx%d draw (%d, %d), cls_gain %.2f: %s' % (preset, h, w, weight_seed, image_seed, model.cls_gain, counts))
     finally:
         update_config_dict(CITYSCAPES_R50)
 

@@ -115,7 +115,9 @@ def calibrate_statistics(model, seed, offset_px=DEFAULT_OFFSET_PX, size=(128, 25
 def build_unprepared(symbol=None, seed=235, offset_px=DEFAULT_OFFSET_PX, cls_gain='default', pipeline='fused', calibrate=True, **calib_kw):
     """The seeded synthetic model as a CHECKPOINT would hold it: on the CPU, frozen BNs unfolded, the reference's state-dict keys
     (resnet.py:221-299). `state_dict()` of this object is what tests save as a stand-in for a trained .pth; build_model() =
-    build_unprepared() -> .to(device) -> prepare_inference()."""
+    build_unprepared() -> .to(device) -> prepare_inference(). cls_gain: 'default' (DEFAULT_CLS_GAIN, fitted to seed 235), a number,
+    None (no rescaling), or a rule f(model, seed) -> gain called on the calibrated, unscaled model (the tests' oracle.draws.fit_cls_gain:
+    the same criterion for any seed). The gain used is kept as model.cls_gain."""
     from .models.resnet_upsnet import resnet_50_upsnet, resnet_101_upsnet
     ctor = {'resnet_50_upsnet': resnet_50_upsnet, 'resnet_101_upsnet': resnet_101_upsnet}[symbol or config.symbol]
     torch.manual_seed(seed)
@@ -132,8 +134,11 @@ def build_unprepared(symbol=None, seed=235, offset_px=DEFAULT_OFFSET_PX, cls_gai
                     m.weight.copy_(torch.randn(m.weight.shape, generator=g) * 0.01)
         if cls_gain == 'default':
             cls_gain = DEFAULT_CLS_GAIN.get(config.dataset.num_classes, 5.4) if calibrate else 0.3
+        elif callable(cls_gain):
+            cls_gain = cls_gain(model, seed)
         if cls_gain is not None:
             model.rcnn.cls_score.weight.mul_(cls_gain)
+    model.cls_gain = cls_gain
     return model
 
 
