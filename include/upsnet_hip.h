@@ -71,7 +71,8 @@ int upsnet_fpn_roi_align_forward(void *stream, const float *const feat_nhwc[4], 
  * ROIs bucketed by (pyramid level, 1/16 stripe of the image, 1/8 column cell; image_height x image_width = the extent the ROIs live in):
  * neighbouring ROIs share an L2 instead of every L2 fetching its own
  * copy of the shared pyramid cells (FPNRoIAlign.forward, upsnet/operators/modules/fpn_roi_align.py:32-62, processes level by level too).
- * num_rois <= 2048 for the table; caller-allocated int[num_rois]. */
+ * num_rois <= 2048 for the table; caller-allocated int[num_rois]. The table is a permutation of 0..num_rois-1 and each bucket's range
+ * of positions is fixed, but the order of the ROIs inside one bucket is unspecified (slots are taken with atomics). */
 int upsnet_fpn_roi_order(void *stream, const float *rois, int num_rois, const int *num_rois_dev, int image_height, int image_width,
                          int *order_out);
 int upsnet_fpn_roi_align_forward_ordered(void *stream, const float *const feat_nhwc[4], const int feat_h[4], const int feat_w[4],
@@ -471,7 +472,7 @@ int upsnet_nms_host(int *keep_out_host, int *num_out_host, const float *boxes_ho
  * (score desc, index desc), the pinned meaning of scores.argsort()[::-1].
  *   boxes [P,nmax,4], scores [P,nmax], counts [P] (device int32, counts[p] <= nmax <= 8192)
  *   pre_removed (optional) [P,nmax] uint8: boxes dropped before NMS (min-size filter)
- *   keep_idx [P,nmax] int32 out (original indices, visiting order), keep_cnt [P] int32 out
+ *   keep_idx [P,nmax] int32 out (original indices, visiting order; rows >= keep_cnt[p] unspecified), keep_cnt [P] int32 out
  *   workspace: upsnet_nms_workspace_bytes(P, nmax) bytes. */
 size_t upsnet_nms_workspace_bytes(int num_problems, int nmax);
 int upsnet_nms_batched(void *stream, const float *boxes, const float *scores, const int *counts,
@@ -492,7 +493,7 @@ int upsnet_cpu_nms_batched(void *stream, const float *boxes, const float *scores
  * launch, one workgroup each, state resident in LDS for nmax <= 4096. Bit-compatible with the compiled reference on the
  * returned prefix (pinned: tests/test_ref_cpu_nms.py):
  *   boxes [P,nmax,5] in/out (x1,y1,x2,y2,score; rows >= n_out[p] unspecified), inds [P,nmax] int64 out (original index of each
- *   surviving row), counts [P] device int32 (valid rows per problem; NULL = nmax everywhere), n_out [P] device int32.
+ *   surviving row; rows >= n_out[p] unspecified), counts [P] device int32 (valid rows per problem; NULL = nmax everywhere), n_out [P] device int32.
  *   method: 0 hard, 1 linear, 2 gaussian. workspace: upsnet_soft_nms_batched_workspace_bytes(P, nmax) (may be NULL when
  *   nmax <= 4096). */
 size_t upsnet_soft_nms_batched_workspace_bytes(int num_problems, int nmax);
@@ -563,7 +564,8 @@ int upsnet_pyramid_proposals_joint_strided(void *stream, int nlev, const float *
  * class-agnostic) score threshold, NMS, global top-max_det; dummy ROI when nothing survives.
  *   rois [N,5], bbox_delta [N,4*C], cls_prob [N,C], num_rois_dev optional device count
  *   boxes_out [cap,5], scores_out [cap], cls_out [cap] int64, src_out [cap] int32 (ROI row of each det),
- *   num_out device int32; cap = upsnet_mask_roi_capacity(N, C, class_agnostic). */
+ *   num_out device int32; cap = upsnet_mask_roi_capacity(N, C, class_agnostic). Rows >= *num_out of the four outputs are
+ *   unspecified (consumers read the first *num_out). */
 int upsnet_mask_roi_capacity(int num_rois, int num_classes, int class_agnostic);
 size_t upsnet_mask_roi_workspace_bytes(int num_rois, int num_classes, int class_agnostic);
 int upsnet_mask_roi(void *stream, const float *rois, const float *bbox_delta, const float *cls_prob, int num_rois,
@@ -584,7 +586,8 @@ int upsnet_mask_roi_ex(void *stream, const float *rois, const float *bbox_delta,
  * through the mask head independently, so a panoptic detection that is also a per-class detection gets bit-identical
  * logits. Given the src/cls outputs of two upsnet_mask_roi calls (set A, set B) this entry writes, for every b in B,
  * map_out[b] = its row in the concatenation [A ; unmatched of B], compacts the unmatched boxes of B (in order) into
- * extra_boxes [cap_b,5] and their count into num_extra (device int). One mask-head pass over [A ; extra] then serves both. */
+ * extra_boxes [cap_b,5] and their count into num_extra (device int). One mask-head pass over [A ; extra] then serves both.
+ * map_out rows >= *num_b and extra_boxes rows >= *num_extra are unspecified. */
 int upsnet_mask_roi_dedup(void *stream, const int *a_src, const int64_t *a_cls, const int *num_a, int cap_a, const int *b_src,
                           const int64_t *b_cls, const float *b_boxes, const int *num_b, int cap_b, int *map_out,
                           float *extra_boxes, int *num_extra);

@@ -902,6 +902,9 @@ def test_conv1x1_balanced_main_plus_tail():
     ([(4, 3, 6)], 64, 64, True, False),             #   of most tiles
     ([(2, 70, 93)], 32, 64, True, True),            # 2 x 432 tiles: 25 of the 27 workgroups on the scalar-offset loads (border tiles zeroed after
                                                     # the load, image 0's bottom patches read into image 1), the last two on the bounds-flagged form
+    ([(1, 130, 2)], 32, 64, True, True),            # W = 2: a row-only `risky` rule let the last scalar-offset workgroup reach pixel N H W
+    ([(3, 5, 1)], 32, 64, False, True),             # W = 1, several images
+    ([(2, 9, 2)], 32, 64, True, False),             # W = 2, several images
 ])
 def test_winograd36_vs_fp64(segs, Cin, Cout, relu, bias):
     """csrc/conv_wino36.hip (Winograd F(4x4,3x3), points {0, +-3/4, +-3/2, inf}, r12) vs torch float64 at rtol = atol = 1e-4 -- the bar of

@@ -152,15 +152,17 @@ __global__ void __launch_bounds__(512, 1) conv_wino36_f32_kernel(const ConvParam
         tbase = (unsigned)(hrow0 * sg.W + wcol0) * (4u * (unsigned)p.Cin) + 4u * (unsigned)lch;
     }
     const bool fix = __builtin_amdgcn_ballot_w64(lane_fix) != 0ull;
-    // workgroup-uniform, from the real extent (r13; the r12 rule "last two tile rows of the last image" assumed H > 3): the FAST loads of a
-    // tile (n, ty, tx) reach pixel (4 ty + 4, 4 tx + 4) of image n -- up to 4 pixels into map row n H + 4 ty + 5 -- and tiles are ordered
-    // by (n, ty, tx), so the workgroup's LAST tile decides: that row must exist inside the tensor
+    // workgroup-uniform, from the linear pixel extent of the FAST loads: the farthest of a tile (n, ty, tx) is origin (h0 + 1, w0 + 1) plus
+    // the scalar offset of patch element (5, 5), 4 rows + 4 pixels on, i.e. linear pixel (n H + 4 ty + 4) W + 4 tx + 4 of the tensor. That
+    // grows with (n, ty, tx), the order of the tiles, so the workgroup's LAST tile decides, with tx bounded by Wo - 1: the FAST form is
+    // allowed only while (nl H + 4 tyl + 4) W + 4 Wo < N H W. (A rule on the row alone -- "row n H + 4 ty + 5 exists" -- misses the 4 Wo
+    // pixels of the column reach when W <= 2: N = 1, H = 130, W = 2 reached pixel 260 = N H W.)
     bool risky;
     {
         const long plast = min(p0 + (long)W36_TM, sg.M) - 1;
         const long nl = plast / HoWo;
         const long tyl = (plast - nl * HoWo) / sg.Wo;
-        risky = nl * sg.H + 4 * tyl + 5 >= (long)sg.N * sg.H;
+        risky = (nl * sg.H + 4 * tyl + 4) * (long)sg.W + 4L * sg.Wo >= (long)sg.N * sg.H * sg.W;
     }
     const unsigned cin4 = 4u * (unsigned)p.Cin;
     const unsigned rowpitch = (unsigned)sg.W * cin4;
