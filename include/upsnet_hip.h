@@ -780,6 +780,24 @@ int upsnet_det_eval_accumulate(void *stream, long num_records, const double *rec
                                const int64_t *npig, const double *rec_thrs, void *workspace, double *precision, double *recall,
                                double *scores);
 
+/* ============================== Evaluation: RPN proposal recall (Detectron's AR, evaluate_box_proposals) ============================== */
+
+/* BaseDataset.evaluate_box_proposals (upsnet/dataset/base_dataset.py:723-805), the greedy matching of each (image, area, limit) problem,
+ * on the device: repeatedly take the alive GT column with the largest max IoU over the alive proposal rows (the first column among
+ * equal maxima), record that IoU, delete the column and its argmax row (the first row among equal IoUs). IoU = bbox_overlaps_c of
+ * upsnet/bbox/bbox.pyx in fp32, same operation order (bit-identical).
+ *   problems int64 [num_problems][6]: proposal offset (rows of `proposals`), P (proposals of the problem, in rank order), GT offset
+ *     (rows of `gt_boxes`), G (0..max_gt), output offset (floats of `out`), workspace word offset (uint32 words; the problems' ranges
+ *     of ceil(P / 32) words are disjoint and inside the workspace);
+ *   proposals / gt_boxes float [.][4] x1 y1 x2 y2, 16-byte aligned, finite.
+ * out float [G] per problem at its offset (fully written): the IoU recorded at step j (j < min(P, G)), then zeros. A row with P < 0,
+ * G < 0 or G > 4096 breaks the contract: the kernel skips it (nothing read or written for it).
+ * max_gt <= 4096; total_proposals = sum of P over the problems (< 2^31). workspace: upsnet_proposal_recall_workspace_bytes(num_problems,
+ * total_proposals) bytes, 256-byte aligned; no zeroing. One launch on `stream`, no host synchronisation. */
+size_t upsnet_proposal_recall_workspace_bytes(int num_problems, long total_proposals);
+int upsnet_proposal_recall(void *stream, int num_problems, const int64_t *problems, const float *proposals, const float *gt_boxes,
+                           int max_gt, long total_proposals, void *workspace, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,7 @@ config.train.use_horovod = False
 config.train.rpn_individual_proposals = True
 config.train.panoptic_box_keep_fraction = 0.7
 config.train.fcn_with_roi_loss = False
+config.train.gt_min_area = -1             # JsonDataset._add_gt_annotations: GTs of a smaller JSON area are dropped
 
 config.test = AttrDict()
 config.test.rpn_nms_thresh = 0.7

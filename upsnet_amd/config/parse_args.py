@@ -20,6 +20,8 @@ def parse_args(description='', argv=None):
     parser.add_argument('--in-flight', type=int, default=1, help='images in flight per rank (1 = the reference loop)')
     parser.add_argument('--pan_combined', action='store_true',
                         help='also score the combined (heuristic merge) panoptic result of the detections and the semantic map')
+    parser.add_argument('--eval_proposals', action='store_true',
+                        help='also keep the RPN proposals of every image and score their recall (AR@100/300/1000, all/small/medium/large)')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)

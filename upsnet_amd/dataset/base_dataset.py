@@ -218,6 +218,57 @@ class BaseDataset(object):
         segmentations are refused (ValueError, dataset/coco_eval.py)."""
         return self._evaluate_detections(all_boxes, all_segms, output_dir, 'segm')
 
+    # ---------------------------------------------------------------------------------------------- RPN proposal recall (AR)
+    def evaluate_box_proposals(self, roidb, thresholds=None, area='all', limit=None):
+        """The reference's evaluate_box_proposals (upsnet/dataset/base_dataset.py:723-805): roidb = dicts with 'boxes' (GT rows and
+        proposal rows), 'gt_classes' (0 = proposal), 'is_crowd' and 'seg_areas'. Returns {'ar', 'recalls', 'thresholds',
+        'gt_overlaps', 'num_pos'}, bit-identical to the reference; the greedy matching runs on the device
+        (dataset/proposal_eval.py, csrc/prop_eval.hip)."""
+        from .proposal_eval import ProposalRecallEvaluator
+        ev = ProposalRecallEvaluator(areas=(area,), limits=(limit,))
+        for entry in roidb:
+            ev.add_entry(entry)
+        return ev.summary(thresholds)[(area, ev.limits[0])]
+
+    def load_proposal_gt(self):
+        """(image_ids ascending, {image_id: dict(boxes float32 [G,4], gt_classes int32 [G], is_crowd bool [G], seg_areas float32 [G])})
+        built from the instances JSON by the rules of the reference's JsonDataset._add_gt_annotations (json_dataset.py:164-230):
+        area < config.train.gt_min_area and ignore == 1 dropped; x2 = x1 + max(0, w - 1) clipped to the image; a box is kept iff
+        area > 0, x2 > x1 and y2 > y1. Classes are 1-based in the order of the JSON's categories."""
+        from .proposal_eval import gt_entry
+        with open(self.instances_json_file, 'r') as f:
+            gt_json = json.load(f)
+        image_ids = sorted(int(im['id']) for im in gt_json['images'])
+        sizes = {int(im['id']): (int(im['height']), int(im['width'])) for im in gt_json['images']}
+        cls_of = {int(c['id']): i + 1 for i, c in enumerate(gt_json['categories'])}
+        anns = defaultdict(list)
+        for a in gt_json['annotations']:
+            anns[int(a['image_id'])].append(a)
+        min_area = config.train.get('gt_min_area', -1)
+        return image_ids, {i: gt_entry(anns.get(i, []), sizes[i], cls_of, min_area) for i in image_ids}
+
+    def evaluate_proposals(self, all_proposals, output_dir):
+        """Proposal recall of all_proposals (per image in ascending image id, float32 [n, 4] x1 y1 x2 y2 in rank order, original image
+        scale) against self.instances_json_file: limits (100, 300, 1000) x areas (all, small, medium, large) in one device pass.
+        Returns {'AR@100', 'ARs@100', 'ARm@100', 'ARl@100', ..., 'ARl@1000'}, logged and written to proposal_recall.txt."""
+        from .proposal_eval import AR_AREAS, AR_LIMITS, ProposalRecallEvaluator, ar_metrics
+        image_ids, gts = self.load_proposal_gt()
+        if len(all_proposals) != len(image_ids):
+            raise ValueError("proposals for %d images, the GT has %d" % (len(all_proposals), len(image_ids)))
+        ev = ProposalRecallEvaluator(areas=[a for a, _ in AR_AREAS], limits=AR_LIMITS)
+        for i, image_id in enumerate(image_ids):
+            g = gts[image_id]
+            ev.add(all_proposals[i], g['boxes'], g['gt_classes'], g['is_crowd'], g['seg_areas'])
+        metrics = ar_metrics(ev.summary())
+        lines = ['%s: %.4f' % (k, v) for k, v in metrics.items()]
+        for line in lines:
+            logger.info(line)
+        os.makedirs(output_dir, exist_ok=True)
+        with open(os.path.join(output_dir, 'proposal_recall.txt'), 'w') as f:
+            for line in lines:
+                f.write(line + '\n')
+        return metrics
+
     def evaluate_all(self, all_boxes, all_segms, output_dir):
         all_results = self.evaluate_boxes(all_boxes, output_dir)
         self.evaluate_masks(all_boxes, all_segms, output_dir)

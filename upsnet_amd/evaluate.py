@@ -2,6 +2,7 @@
 (upsnet/upsnet_end2end_test.py:155-314).
 
     python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
+                                  [--eval_proposals]
 
 The dataset is `config.dataset.dataset` (Cityscapes or coco) on `config.dataset.test_image_set`. Every image and every GT file the
 configured heads need is checked before the first launch. Images are decoded by a bounded host thread pool ahead of the device;
@@ -11,7 +12,8 @@ scaled by 1 / im_scale in float32, masks run-length encoded by dataset/rle.im_po
 original resolution by one gather launch (csrc/restore.hip, cv2 INTER_NEAREST tables). The results pickle has the reference's
 path, keys and nesting (numpy objects only); evaluation follows the reference's order: boxes, masks, panoptic, semantic.
 `--eval_only` re-scores the pickle without building the model. `--pan_combined` also scores get_combined_pan_result (the
-heuristic merge of the detections and the semantic map) next to the unified result. One rank only (WORLD_SIZE > 1 is refused)."""
+heuristic merge of the detections and the semantic map) next to the unified result. `--eval_proposals` keeps the RPN proposals
+of every image (results['all_proposals'], original image scale) and scores their recall (metrics['proposal_ar']). One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
 import pickle
@@ -56,8 +58,11 @@ def scale_boxes(pred_boxes, im_info):
     return pred_boxes[:, 1:].float().cpu().numpy() / np.float32(im_info[2])
 
 
-def post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds):
-    """One image's share of the reference's loop after the network (upsnet_end2end_test.py:254-272): appends to the result lists."""
+def post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds, all_proposals=None):
+    """One image's share of the reference's loop after the network (upsnet_end2end_test.py:254-272): appends to the result lists;
+    with all_proposals (a list), also the box head's proposals at the original image scale (scale_boxes' rule), float32 [n, 4]."""
+    if all_proposals is not None:
+        all_proposals.append(scale_boxes(out['proposals'], im_info))
     from .dataset.restore import restore_to_image
     from .dataset.rle import im_post
     net = config.network
@@ -82,8 +87,9 @@ def post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_p
             all_pano_cls_inds.append(out['panoptic_cls_inds'].cpu().numpy())
 
 
-def run_inference(model, dataset, in_flight=1, device=None):
-    """The test loop over the whole image list. Returns (results dict as pickled, per-image timings)."""
+def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False):
+    """The test loop over the whole image list. Returns (results dict as pickled, per-image timings). keep_proposals: also
+    results['all_proposals'] (model.keep_proposals is set for the run)."""
     from .dataset.blob import get_image_blob
     net = config.network
     n, num_classes = len(dataset), dataset.num_classes
@@ -91,6 +97,9 @@ def run_inference(model, dataset, in_flight=1, device=None):
     all_masks = [[] for _ in range(num_classes)] if net.has_mask_head else None
     all_ssegs = [] if net.has_fcn_head else None
     all_panos, all_pano_cls_inds = ([], []) if net.has_panoptic_head else (None, None)
+    all_proposals = [] if keep_proposals else None
+    if keep_proposals:
+        model.keep_proposals = True
     depth = max(1, min(int(in_flight), getattr(model, 'graph_slots', 1))) if hasattr(model, 'forward_async') else 1
     launch = model.forward_async if depth > 1 else model
     workers = max(1, min(MAX_DECODE_THREADS, n))     # (never sized from the host's CPU count)
@@ -104,7 +113,9 @@ def run_inference(model, dataset, in_flight=1, device=None):
         if device is not None and device.type == 'cuda':
             torch.cuda.synchronize(device)
         t1 = time.perf_counter()
-        post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds)
+        # (with keep_proposals, out['proposals'] may be a view of a graph slot's buffer: it is read here, after the synchronise
+        # above and before that slot's next replay -- the next image of the slot is launched only after this finish())
+        post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds, all_proposals)
         post_time = time.perf_counter() - t1
         # net_time: host time blocked on the network for this image (launch + wait); with one image in flight that is the
         # reference's forward + synchronize
@@ -129,13 +140,16 @@ def run_inference(model, dataset, in_flight=1, device=None):
             finish(*pending.pop(0))
     results = {'all_boxes': all_boxes, 'all_masks': all_masks, 'all_ssegs': all_ssegs, 'all_panos': all_panos,
                'all_pano_cls_inds': all_pano_cls_inds}
+    if keep_proposals:
+        results['all_proposals'] = all_proposals
     return results, times
 
 
-def evaluate_results(dataset, results, results_dir, pan_combined=False):
+def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
-    'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined."""
+    'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
+    results['all_proposals']) with eval_proposals."""
     net = config.network
     metrics = {}
     if not dataset.has_gt:
@@ -163,6 +177,10 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False):
         metrics['panoptic_combined'] = dataset.evaluate_panoptic(pans, os.path.join(results_dir, 'pans_combined'))
     if net.has_fcn_head:
         metrics['sseg'] = dataset.evaluate_ssegs(results['all_ssegs'], os.path.join(results_dir, 'ssegs'))
+    if eval_proposals:
+        logger.info('proposal recall:')
+        # (the roidb, and so the results lists, are in ascending image id, the order evaluate_proposals takes)
+        metrics['proposal_ar'] = dataset.evaluate_proposals(results['all_proposals'], results_dir)
     return metrics
 
 
@@ -190,11 +208,15 @@ def main(argv=None):
     if args.eval_only:
         if not os.path.isfile(results_file):
             raise SystemExit('--eval_only: no results to evaluate at %s (run without --eval_only first)' % results_file)
-        dataset = build_dataset(out_dir)
-        dataset.check_files(images=False)
         with open(results_file, 'rb') as f:
             results = pickle.load(f)
-        return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined), 'results_file': results_file, 'times': None}
+        if args.eval_proposals and 'all_proposals' not in results:
+            raise SystemExit('--eval_only --eval_proposals: %s holds no proposals (all_proposals); run with --eval_proposals without '
+                             '--eval_only first' % results_file)
+        dataset = build_dataset(out_dir)
+        dataset.check_files(images=False)
+        return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals),
+                'results_file': results_file, 'times': None}
 
     dataset = build_dataset(out_dir)
     dataset.check_files()       # every image and GT file, before the first launch
@@ -208,12 +230,13 @@ def main(argv=None):
         weight_path = args.weight_path or default_weight_path(args.cfg)
         model = load_checkpoint_model(weight_path, device)
         logging.info('loaded %s into %s (resume=True)', weight_path, config.symbol)
-    results, times = run_inference(model, dataset, in_flight=args.in_flight, device=device)
+    results, times = run_inference(model, dataset, in_flight=args.in_flight, device=device, keep_proposals=args.eval_proposals)
     os.makedirs(results_dir, exist_ok=True)
     with open(results_file, 'wb') as f:
         pickle.dump(results, f, protocol=2)
     logging.info('%d images, results written to %s', len(dataset), results_file)
-    return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined), 'results_file': results_file, 'times': times}
+    return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals),
+            'results_file': results_file, 'times': times}
 
 
 if __name__ == '__main__':

@@ -75,6 +75,9 @@ class resnet_upsnet(resnet_rcnn):
         self.graph_outputs_alias = os.environ.get('UPSNET_GRAPH_ALIAS', '1') != '0'
         self.early_mask_head = os.environ.get('UPSNET_EARLY_MASK', '1') != '0'
         self.taps = None  # set to a dict to record the inputs/outputs of every custom-op stage (parity tests)
+        # opt-in: the output dict also carries the box head's proposals ('rois' buffer, device count 'n_rois', the ranked rows
+        # 'proposals' = rois[:n_rois]; proposal recall, evaluate.py --eval_proposals). Off: outputs, launches and graphs unchanged.
+        self.keep_proposals = False
         self.num_classes = config.dataset.num_classes
         self.num_seg_classes = config.dataset.num_seg_classes
         self.num_reg_classes = (2 if config.network.cls_agnostic_bbox_reg else config.dataset.num_classes)
@@ -285,7 +288,7 @@ class resnet_upsnet(resnet_rcnn):
             nums = torch.cat([det_num, pan_num, extra_num])
         return dict(feats=feats, fcn=fcn, fuse_up=fuse_up, tail=tail_out, det_boxes=det_boxes, det_scores=det_scores, det_cls=det_cls,
                     pan_boxes=pan_boxes, pan_scores=pan_scores, pan_cls=pan_cls, pan_row=pan_row, extra_boxes=extra_boxes, nums=nums,
-                    mask_det=mask_det, max_det=max_det, _events=(ev_fork, ev_join))
+                    mask_det=mask_det, max_det=max_det, rois=rois, n_rois=n_rois, _events=(ev_fork, ev_join))
 
     def _phase1_graphed(self, x, im_info_host, wait=True):
         """HIP-graph replay of _phase1 for this input shape / im_info: the ~150 launches of the trunk, the semantic head (side
@@ -376,6 +379,7 @@ class resnet_upsnet(resnet_rcnn):
                     'fcn_outputs': t['sem'], 'cls_inds': st['det_cls'][:n_det], 'panoptic_cls_inds': t['kept_cls'][:k],
                     'panoptic_cls_probs': t['kept_scores'][:k], 'panoptic_outputs': t['panoptic'],
                 }
+                self._keep_proposals(out, st['rois'], st['n_rois'])
                 return out if self.graph_outputs_alias else {key: v.clone() for key, v in out.items()}
         else:
             n_det, n_pan, n_extra = st['nums'].tolist()
@@ -418,11 +422,27 @@ class resnet_upsnet(resnet_rcnn):
         k = int(num_keep.item())
         keep = keep[:k]
         self._tap(keep=keep, panoptic=panoptic, sem=sem)
-        return {
+        out = {
             'cls_probs': det_scores, 'pred_boxes': det_boxes, 'mask_probs': mask_prob, 'fcn_outputs': sem,
             'cls_inds': det_cls, 'panoptic_cls_inds': pan_cls[keep], 'panoptic_cls_probs': pan_scores[keep],
             'panoptic_outputs': panoptic,
         }
+        if graphed:   # (the graph's buffers are overwritten by its next replay)
+            self._keep_proposals(out, st['rois'].clone(), st['n_rois'].clone())
+        else:
+            self._keep_proposals(out, st['rois'], st['n_rois'])
+        return out
+
+    def _keep_proposals(self, out, rois, n_rois):
+        """keep_proposals: add the box head's proposals to `out` -- the padded rois buffer [capacity, 5] (batch index, x1 y1 x2 y2
+        at the network's input scale), its device count n_rois (int32 [1]) and the rows the box head reads, proposals =
+        rois[:n_rois] in rank order. One host read of the count; the graph's outputs are complete when this runs (forward() and
+        _Pending.result() have read the counters). On the graph path the buffers belong to the graph slot: read them before that
+        slot's next replay."""
+        if self.keep_proposals:
+            n = int(n_rois.item())
+            out.update(rois=rois, n_rois=n_rois, proposals=rois[:n])
+        return out
 
     def _materialised_head(self, fcn_output, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep):
         H, W = fcn_output.shape[2:]
@@ -473,6 +493,8 @@ class resnet_upsnet(resnet_rcnn):
         results['panoptic_outputs'] = ops.panoptic_argmax(fcn_output['fcn_output'], num_stuff, seg_inst_logits,
                                                           mask_logits, self.enable_void)
         self._tap(keep=keep_inds, panoptic=results['panoptic_outputs'], sem=results['fcn_outputs'])
+        if self.keep_proposals:   # (rois is already the ranked list)
+            results.update(rois=rois, n_rois=torch.full((1,), rois.shape[0], dtype=torch.int32, device=rois.device), proposals=rois)
         return results
 
 

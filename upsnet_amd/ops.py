@@ -1810,3 +1810,35 @@ def conv2d_nhwc_splitk(x, wpack, ldw, bias, cout, ksize, stride, pad, ksplit, re
                                   4.0 * (C * N * H * W + cout * npix * (2 if res is not None else 1) + cout * C * ksize * ksize),
                                   "split-K x%d %dx%d/%d %d->%d %s" % (ksplit, ksize, ksize, stride, C, cout, (N, H, W))))
     return out
+
+
+# ----------------------------------------------------------------------------- proposal recall (evaluate_box_proposals)
+PROPOSAL_RECALL_MAX_GT = 4096   # GT boxes per problem (csrc/prop_eval.hip keeps one LDS key per GT column)
+
+
+def proposal_recall_workspace_bytes(num_problems, total_proposals):
+    return int(lib().upsnet_proposal_recall_workspace_bytes(int(num_problems), int(total_proposals)))
+
+
+def proposal_recall(problems, proposals, gt_boxes, max_gt, total_proposals, workspace, out):
+    """The greedy matching of evaluate_box_proposals for a batch of (image, area, limit) problems, one launch (csrc/prop_eval.hip;
+    include/upsnet_hip.h: upsnet_proposal_recall for the table layout). problems int64 [n, 6], proposals / gt_boxes float32 [., 4],
+    workspace uint8 of proposal_recall_workspace_bytes(n, total_proposals) bytes and out float32: caller-owned device tensors (the
+    evaluator, dataset/proposal_eval.py, sizes and owns them); out is fully written. No host synchronisation."""
+    require_cuda(problems, proposals, gt_boxes, workspace, out)
+    if problems.dtype != torch.int64 or problems.dim() != 2 or problems.shape[1] != 6 or not problems.is_contiguous():
+        raise ValueError("proposal_recall: problems must be a contiguous int64 [n, 6] table, got %s %s" % (problems.dtype, tuple(problems.shape)))
+    for name, b in (('proposals', proposals), ('gt_boxes', gt_boxes)):
+        if b.dtype != torch.float32 or b.dim() != 2 or b.shape[1] != 4 or not b.is_contiguous():
+            raise ValueError("proposal_recall: %s must be contiguous float32 [., 4], got %s %s" % (name, b.dtype, tuple(b.shape)))
+    if not 0 <= int(max_gt) <= PROPOSAL_RECALL_MAX_GT:
+        raise ValueError("proposal_recall: %d GT boxes in a problem (at most %d)" % (int(max_gt), PROPOSAL_RECALL_MAX_GT))
+    n = int(problems.shape[0])
+    if workspace.numel() * workspace.element_size() < proposal_recall_workspace_bytes(n, total_proposals):
+        raise ValueError("proposal_recall: workspace of %d bytes, %d needed" % (workspace.numel() * workspace.element_size(),
+                                                                             proposal_recall_workspace_bytes(n, total_proposals)))
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("proposal_recall: out must be contiguous float32")
+    check(lib().upsnet_proposal_recall(stream(), n, ptr(problems), ptr(proposals), ptr(gt_boxes), int(max_gt), int(total_proposals),
+                                       ptr(workspace), ptr(out)), "proposal_recall")
+    return out
