@@ -123,6 +123,39 @@ def test_fc6_weight_relayout_matches_nchw_flatten():
     torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5)
 
 
+def test_packed_weight_cache_rebuild_rules(monkeypatch):
+    """ops.cached_pack: one entry per owner and slot, rebuilt exactly when a tensor's address / version / shape or an extra field changes
+    (captured graphs hold the addresses of the packs); hipconv.clear_cache drops it. With profiling off no timing event is created."""
+    from upsnet_amd import ops
+    from upsnet_amd.models import hipconv
+    m, other = torch.nn.Conv2d(4, 8, 1), torch.nn.Conv2d(4, 8, 1)
+    builds = []
+
+    def get(owner, *extra):
+        return ops.cached_pack(owner, 'slot', (owner.weight, owner.bias), lambda: builds.append(owner) or len(builds), *extra)
+
+    assert get(m) == 1 and get(m) == 1 and len(builds) == 1
+    with torch.no_grad():
+        m.weight.mul_(2)
+    assert get(m) == 2
+    with torch.no_grad():
+        m.bias.add_(1)
+    assert get(m) == 3 and get(m) == 3
+    assert get(m, 'bf16') == 4 and get(m, 'bf16') == 4
+    assert get(other, 'bf16') == 5 and get(m, 'bf16') == 4
+    w_pack = ops.cached_pack(m.weight, 'dcn', (m.weight,), lambda: 'dcn pack')
+    assert w_pack == 'dcn pack' and '_hip_plans' in m.weight.__dict__
+    hipconv.clear_cache(torch.nn.Sequential(m))
+    assert '_hip_plans' not in m.__dict__ and '_hip_plans' not in m.weight.__dict__ and '_hip_plans' in other.__dict__
+    assert get(m, 'bf16') == 6 and len(builds) == 6
+
+    def no_event(*a, **k):
+        raise AssertionError("timing event created with profiling off")
+    monkeypatch.setattr(torch.cuda, 'Event', no_event)
+    monkeypatch.setitem(ops.PROFILE, 'enabled', False)
+    assert ops._prof_begin() is None
+
+
 def test_blob_geometry_host_mirror_equals_oracle():
     """dataset/blob.py restates prep_im_for_blob's scale rule + im_list_to_blob's padding exactly like the oracle (base_dataset.py:155-170, 909-913)."""
     import oracle

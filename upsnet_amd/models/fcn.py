@@ -33,7 +33,6 @@ class FCNSubNet(nn.Module):
                 conv.append(DeformConvWithOffset(in_channels, in_channels, kernel_size=3, stride=1, padding=dilation, dilation=dilation))
             conv.append(nn.ReLU(inplace=True))
             self.conv.append(nn.Sequential(*conv))
-        self._packed = {}
         self.taps = None   # parity tests: set to a dict to record every layer's predicted offsets (tests/test_trunk_gpu.py)
         self.initialize()
 
@@ -52,12 +51,6 @@ class FCNSubNet(nn.Module):
             x = self.conv[i](x)
         return x
 
-    def _wpack(self, i, dc):
-        key = (dc.weight.data_ptr(), dc.weight._version, ops.dcn_precision())
-        if i not in self._packed or self._packed[i][0] != key:
-            self._packed[i] = (key, ops.pack_dcn_weight(dc.weight.detach()))
-        return self._packed[i][1]
-
     def forward_levels(self, feats):
         """All FPN levels through the shared subnet: one fused DCN launch per layer."""
         xs = list(feats)
@@ -70,7 +63,7 @@ class FCNSubNet(nn.Module):
             offsets = hipconv.conv_multi(layer.conv_offset, xs)
             if self.taps is not None:
                 self.taps.setdefault('offsets', []).append([o.detach().clone() for o in offsets])
-            ys = ops.deform_conv_fused(xs, offsets, self._wpack(i, dc), dc.bias, dc.in_channels, dc.out_channels,
+            ys = ops.deform_conv_fused(xs, offsets, ops.cached_dcn_pack(dc.weight), dc.bias, dc.in_channels, dc.out_channels,
                                        dc.kernel_size, dc.stride, dc.padding, dc.dilation, relu=True)
             hipconv._trace('dcn', module=dc, xs=xs, offsets=offsets, outs=ys, relu=True, form='dcn_fused multi' + (' bf16' if ops.dcn_precision() == 'bf16' else ''))
             xs = ys
@@ -95,11 +88,8 @@ class FCNHead(nn.Module):
     def _score_parts(self):
         """Per-level column blocks of the 1x1 score weight, packed for the MFMA conv kernel (cached)."""
         w = self.score.weight
-        key = (w.data_ptr(), w._version)
-        if getattr(self, '_score_pack', None) is None or self._score_pack[0] != key:
-            c = w.shape[1] // 4
-            self._score_pack = (key, [ops.pack_conv_weight(w.detach()[:, l * c:(l + 1) * c].contiguous()) for l in range(4)])
-        return self._score_pack[1]
+        c = w.shape[1] // 4
+        return ops.cached_pack(self, 'score_parts', (w,), lambda: [ops.pack_conv_weight(w.detach()[:, l * c:(l + 1) * c].contiguous()) for l in range(4)])
 
     def forward_score(self, fpn_p2, fpn_p3, fpn_p4, fpn_p5, commute=True):
         """fcn_score only ([1,S,H/4,W/4]); the x4 upsampling is fused into the panoptic kernel by the caller.

@@ -83,36 +83,17 @@ def act_dtype():
     return torch.bfloat16 if (PRECISION == 'bf16' and BF16_ACT) else torch.float32
 
 
-def _plans(m):
-    """Packed-weight cache of ONE module, stored on the module itself. (A process-wide dict keyed by id(module) is unsafe: the id
-    -- and with the caching allocator even the weight's address -- of a freed model's layer can be reused by a different layer
-    of a later model, and a stale pack of another shape makes the kernel read out of bounds.)"""
-    d = m.__dict__.get('_hip_plans')
-    if d is None:
-        d = m.__dict__['_hip_plans'] = {}
-    return d
-
+def _pack(m, slot, pack, *extra):
+    """pack(weight) of one module, cached on the module (ops.cached_pack: re-packed when its weight or bias changes)."""
+    return ops.cached_pack(m, slot, (m.weight, m.bias), lambda: pack(m.weight.detach()), *extra)
 
 
 def _plan(m):
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-    ent = _plans(m).get('direct')
-    if ent is None or ent[0] != key:
-        wp, ldw = ops.pack_conv_weight(w.detach())
-        ent = (key, wp, ldw)
-        _plans(m)['direct'] = ent
-    return ent[1], ent[2]
+    return _pack(m, 'direct', ops.pack_conv_weight)
 
 
 def _conv1x1_plan(m):
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-    ent = _plans(m).get('c1x1')
-    if ent is None or ent[0] != key:
-        ent = (key, ops.pack_conv1x1_weight(w.detach()))
-        _plans(m)['c1x1'] = ent
-    return ent[1]
+    return _pack(m, 'c1x1', ops.pack_conv1x1_weight)
 
 
 def _use_conv1x1(m, x, always=False):
@@ -229,13 +210,7 @@ KSW_TILE = (16, 64)
 
 
 def _ksw_plan(m):
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-    ent = _plans(m).get('ksw')
-    if ent is None or ent[0] != key:
-        ent = (key, ops.pack_conv1x1_ksw_weight(w.detach()))
-        _plans(m)['ksw'] = ent
-    return ent[1]
+    return _pack(m, 'ksw', ops.pack_conv1x1_ksw_weight)
 
 
 def _use_ksw(m, x, cus=None):
@@ -259,13 +234,7 @@ KSW3 = os.environ.get('UPSNET_CONV3X3_KSW', '1') != '0'
 
 
 def _ksw3_plan(m):
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-    ent = _plans(m).get('ksw3')
-    if ent is None or ent[0] != key:
-        ent = (key, ops.pack_conv3x3_ksw_weight(w.detach()))
-        _plans(m)['ksw3'] = ent
-    return ent[1]
+    return _pack(m, 'ksw3', ops.pack_conv3x3_ksw_weight)
 
 
 def _use_ksw3(m, x):
@@ -331,14 +300,10 @@ def use_siblings(ma, mb, x):
 
 def conv_siblings(ma, mb, x, relu_a=True, relu_b=False):
     """(relu_a?(ma(x)), relu_b?(mb(x))) in one launch -- see use_siblings. Bit-identical to the two launches."""
-    key = tuple((m.weight.data_ptr(), m.weight._version, tuple(m.weight.shape), None if m.bias is None else m.bias._version) for m in (ma, mb))
-    ent = _plans(ma).get('siblings')
-    if ent is None or ent[0] != key:
-        wp = ops.pack_conv1x1_weight(torch.cat([ma.weight.detach(), mb.weight.detach()], 0))
-        b = None if ma.bias is None else torch.cat([ma.bias.detach(), mb.bias.detach()], 0).contiguous()
-        ent = (key, wp, b)
-        _plans(ma)['siblings'] = ent
-    ya, yb = ops.conv1x1_siblings(x, ent[1], ent[2], ma.out_channels, mb.out_channels, ma.stride[0], relu_a=relu_a, relu_b=relu_b)
+    wp, b = ops.cached_pack(ma, 'siblings', (ma.weight, ma.bias, mb.weight, mb.bias), lambda: (
+        ops.pack_conv1x1_weight(torch.cat([ma.weight.detach(), mb.weight.detach()], 0)),
+        None if ma.bias is None else torch.cat([ma.bias.detach(), mb.bias.detach()], 0).contiguous()))
+    ya, yb = ops.conv1x1_siblings(x, wp, b, ma.out_channels, mb.out_channels, ma.stride[0], relu_a=relu_a, relu_b=relu_b)
     _trace('conv', module=ma, x=x, out=ya, relu=relu_a, residual=None, residual_up=False, form='conv1x1 siblings(a)')
     _trace('conv', module=mb, x=x, out=yb, relu=relu_b, residual=None, residual_up=False, form='conv1x1 siblings(b)')
     return ya, yb
@@ -378,13 +343,7 @@ def _bf16_form():
 
 
 def _bf16_plan(m):
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version, PRECISION)
-    ent = _plans(m).get('bf16')
-    if ent is None or ent[0] != key:
-        ent = (key,) + ops.pack_conv_weight_bf16(w.detach(), split=(PRECISION == 'bf16x3'))
-        _plans(m)['bf16'] = ent
-    return ent[1], ent[2], ent[3]
+    return _pack(m, 'bf16', lambda w: ops.pack_conv_weight_bf16(w, split=(PRECISION == 'bf16x3')), PRECISION)
 
 
 # bf16 mode: an identity bottleneck (three layers + shortcut) as one launch whose intermediates stay in the LDS
@@ -423,29 +382,18 @@ def use_block(blk, x):
 def block(blk, x):
     """relu(conv3(relu(conv2(relu(conv1(x))))) + shortcut(x)) -- see use_block."""
     ms = (blk.conv1, blk.conv2, blk.conv3) + (() if blk.downsample is None else (blk.downsample[0],))
-    key = tuple((m.weight.data_ptr(), m.weight._version, None if m.bias is None else m.bias._version) for m in ms)
-    ent = _plans(blk.conv1).get('block16')
-    if ent is None or ent[0] != key:
-        pack = ops.pack_bottleneck_bf16 if blk.downsample is None else ops.pack_bottleneck_proj_bf16
-        ent = (key, pack(*(m.weight for m in ms), *(m.bias for m in ms)))
-        _plans(blk.conv1)['block16'] = ent
+    pack = ops.pack_bottleneck_bf16 if blk.downsample is None else ops.pack_bottleneck_proj_bf16
+    p = ops.cached_pack(blk.conv1, 'block16', [t for m in ms for t in (m.weight, m.bias)], lambda: pack(*(m.weight for m in ms), *(m.bias for m in ms)))
     if blk.downsample is None:
-        y = ops.bottleneck_bf16(x, ent[1])
+        y = ops.bottleneck_bf16(x, p)
     else:
-        y = ops.bottleneck_proj_bf16(x, ent[1], blk.conv1.stride[0])
+        y = ops.bottleneck_proj_bf16(x, p, blk.conv1.stride[0])
     _trace('block', module=blk, x=x, out=y, form='bottleneck_bf16' if blk.downsample is None else 'bottleneck_proj_bf16')
     return y
 
 
 def _winograd_plan(m, tn32=False):
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-    name = 'wino32' if tn32 else 'wino'
-    ent = _plans(m).get(name)
-    if ent is None or ent[0] != key:
-        ent = (key,) + ops.pack_winograd_weight(w.detach(), tn32=tn32)
-        _plans(m)[name] = ent
-    return ent[1], ent[2]
+    return _pack(m, 'wino32' if tn32 else 'wino', lambda w: ops.pack_winograd_weight(w, tn32=tn32))
 
 
 WINO_TAIL_SPLIT = os.environ.get('UPSNET_WINO_TAIL_SPLIT', '1') != '0'   # r10: the mask head's last partial round on half-size workgroups IN the
@@ -493,13 +441,7 @@ def _wino_split_launch(m, x, n_main, relu):
 
 
 def _winograd36_plan(m):
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-    ent = _plans(m).get('wino36')
-    if ent is None or ent[0] != key:
-        ent = (key,) + ops.pack_winograd36_weight(w.detach())
-        _plans(m)['wino36'] = ent
-    return ent[1], ent[2]
+    return _pack(m, 'wino36', ops.pack_winograd36_weight)
 
 
 def _winograd36_shape_ok(m):
@@ -740,15 +682,10 @@ def conv_stem(m, x, relu=False):
         _library(m, x, 'hipconv.stem_supported() is false')
         y = m(x[:, :m.in_channels] if x.shape[1] != m.in_channels else x)
         return F.relu(y, inplace=True) if relu else y
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-    ent = _plans(m).get('stem')
-    if ent is None or ent[0] != key:
-        ent = (key,) + ops.pack_stem_weight(w.detach())
-        _plans(m)['stem'] = ent
+    wp, ldw = _pack(m, 'stem', ops.pack_stem_weight)
     is_nhwc4 = x.shape[1] == 4 and x.is_contiguous(memory_format=torch.channels_last)
     x4 = x if is_nhwc4 else ops.image_to_nhwc4(x)
-    y = ops.conv2d_stem(x4, ent[1], ent[2], m.bias, m.out_channels, m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0], relu=relu)
+    y = ops.conv2d_stem(x4, wp, ldw, m.bias, m.out_channels, m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0], relu=relu)
     _trace('conv', module=m, x=x4[:, :m.in_channels], out=y, relu=relu, residual=None, residual_up=False, form='stem')
     return y
 
@@ -776,15 +713,10 @@ def use_stem_pool(m, x):
 def stem_pool(m, x):
     """max_pool2d(relu(m(x)), 3, 2, 1) of the 7x7/2 stem in one launch -- see use_stem_pool. bf16 mode: returns bf16."""
     kind = use_stem_pool(m, x)
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-    ent = _plans(m).get('stem_pool_' + kind)
-    if ent is None or ent[0] != key:
-        ent = (key, ops.pack_stem_pool_weight_bf16(w.detach()) if kind == 'bf16' else ops.pack_stem_pool_weight_f32(w.detach()))
-        _plans(m)['stem_pool_' + kind] = ent
+    wp = _pack(m, 'stem_pool_' + kind, ops.pack_stem_pool_weight_bf16 if kind == 'bf16' else ops.pack_stem_pool_weight_f32)
     is_nhwc4 = x.shape[1] == 4 and x.is_contiguous(memory_format=torch.channels_last)
     x4 = x if is_nhwc4 else ops.image_to_nhwc4(x)
-    y = ops.stem_pool_bf16(x4, ent[1], m.bias) if kind == 'bf16' else ops.stem_pool_f32(x4, ent[1], m.bias)
+    y = ops.stem_pool_bf16(x4, wp, m.bias) if kind == 'bf16' else ops.stem_pool_f32(x4, wp, m.bias)
     _trace('stem_pool', module=m, x=x4[:, :m.in_channels], out=y, form='stem + pool bf16' if kind == 'bf16' else 'stem + pool')
     return y
 
@@ -798,13 +730,9 @@ def deconv2x2(m, x, relu=False):
             tuple(m.stride) == (2, 2) and tuple(m.padding) == (0, 0) and tuple(m.output_padding) == (0, 0) and m.groups == 1 and
             tuple(m.dilation) == (1, 1) and m.in_channels % 32 == 0)
     if geom and x.dtype == torch.bfloat16 and PRECISION == 'bf16' and m.in_channels % 64 == 0 and m.out_channels % 32 == 0:
-        w = m.weight       # bf16 mode, bf16 activations (the mask head): bf16 MFMA GEMM with the same scatter epilogue
-        key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
-        ent = _plans(m).get('deconv16')
-        if ent is None or ent[0] != key:
-            ent = (key,) + ops.pack_deconv2x2_weight_bf16(w.detach())
-            _plans(m)['deconv16'] = ent
-        y = ops.deconv2x2_bf16(x, ent[1], ent[2], m.bias, m.out_channels, relu=relu)
+        # bf16 mode, bf16 activations (the mask head): bf16 MFMA GEMM with the same scatter epilogue
+        whi, ldw = _pack(m, 'deconv16', ops.pack_deconv2x2_weight_bf16)
+        y = ops.deconv2x2_bf16(x, whi, ldw, m.bias, m.out_channels, relu=relu)
         _trace('deconv', module=m, x=x, out=y, relu=relu, form='deconv2x2 bf16')
         return y
     if x.dtype == torch.bfloat16:
@@ -814,23 +742,15 @@ def deconv2x2(m, x, relu=False):
         _library(m, x, 'not a 2x2 / stride-2 transposed convolution with Cin % 32 == 0')
         y = m(x)
         return F.relu(y, inplace=True) if relu else y
-    w = m.weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), None if m.bias is None else m.bias._version)
     if DECONV_FRAG and m.out_channels % 32 == 0:
         # the lean 1x1 GEMM kernel with a scatter epilogue (csrc/conv1x1.hip MODE 2): A fragments as one ds_read_b128 per 8 MFMAs, B from
         # L2 -- the general kernel (csrc/conv.hip) reads two LDS words per MFMA
-        ent = _plans(m).get('deconv_frag')
-        if ent is None or ent[0] != key:
-            ent = (key,) + ops.pack_deconv2x2_weight_frag(w.detach(), m.bias)
-            _plans(m)['deconv_frag'] = ent
-        y = ops.deconv2x2_frag(x, ent[1], ent[2], m.out_channels, relu=relu)
+        wp, bias4 = _pack(m, 'deconv_frag', lambda w: ops.pack_deconv2x2_weight_frag(w, m.bias))
+        y = ops.deconv2x2_frag(x, wp, bias4, m.out_channels, relu=relu)
         _trace('deconv', module=m, x=x, out=y, relu=relu, form='deconv2x2 frag')
         return y
-    ent = _plans(m).get('deconv')
-    if ent is None or ent[0] != key:
-        ent = (key,) + ops.pack_deconv2x2_weight(w.detach())
-        _plans(m)['deconv'] = ent
-    y = ops.deconv2x2(x, ent[1], ent[2], m.bias, m.out_channels, relu=relu)
+    wp, ldw = _pack(m, 'deconv', ops.pack_deconv2x2_weight)
+    y = ops.deconv2x2(x, wp, ldw, m.bias, m.out_channels, relu=relu)
     _trace('deconv', module=m, x=x, out=y, relu=relu, form='deconv2x2')
     return y
 
@@ -848,10 +768,13 @@ def dcn(m, x, offset, relu=False):
 
 
 def clear_cache(model=None):
-    """Drop the packed weights of every layer of `model` (they are rebuilt on next use)."""
+    """Drop the packed weights of every layer of `model` (they are rebuilt on next use): ops.cached_pack keeps them on the modules and,
+    for the deformable convolutions, on the weight tensors."""
     if model is not None:
         for m in model.modules():
             m.__dict__.pop('_hip_plans', None)
+            for p in m.parameters(recurse=False):
+                p.__dict__.pop('_hip_plans', None)
 
 
 def conv_multi_cat(ms, xs, return_flat=False):
@@ -871,15 +794,9 @@ def conv_multi_cat(ms, xs, return_flat=False):
             (sum(couts) + 31) // 32 != 1 or _use_winograd(m0, xs)):
         res = [conv_multi(m, xs) for m in ms]
         return (res, None, None) if return_flat else res
-    key = tuple((m.weight.data_ptr(), m.weight._version, tuple(m.weight.shape), None if m.bias is None else m.bias._version) for m in ms)
-    ent = _plans(m0).get('cat')
-    if ent is None or ent[0] != key:
-        w = torch.cat([m.weight.detach() for m in ms], 0)
-        b = None if m0.bias is None else torch.cat([m.bias.detach() for m in ms], 0)
-        wp, ldw = ops.pack_conv_weight(w)
-        ent = (key, wp, ldw, b)
-        _plans(m0)['cat'] = ent
-    _, wp, ldw, b = ent
+    (wp, ldw), b = ops.cached_pack(m0, 'cat', [t for m in ms for t in (m.weight, m.bias)], lambda: (
+        ops.pack_conv_weight(torch.cat([m.weight.detach() for m in ms], 0)),
+        None if m0.bias is None else torch.cat([m.bias.detach() for m in ms], 0)))
     outs = ops.conv2d_nhwc_multi(xs, wp, ldw, b, sum(couts), m0.kernel_size[0], m0.stride[0], m0.padding[0], relu=False)
     res, c0 = [], 0
     for m, c in zip(ms, couts):

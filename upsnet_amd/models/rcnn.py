@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import ops
 from ..config.config import config
 from . import hipconv
 from ..operators.modules.fpn_roi_align import FPNRoIAlign
@@ -71,7 +72,6 @@ class RCNN(nn.Module):
         self.fc7 = nn.Sequential(nn.Linear(dim_hidden, dim_hidden), nn.ReLU(inplace=True))
         self.cls_score = nn.Linear(dim_hidden, num_classes)
         self.bbox_pred = nn.Linear(dim_hidden, num_reg_classes * 4)
-        self._fc6_nhwc = None
         self.initialize()
 
     def initialize(self):
@@ -86,13 +86,9 @@ class RCNN(nn.Module):
         self.bbox_pred.bias.data.fill_(0)
 
     def _fc6_weight_nhwc(self, dtype=torch.float32):
-        w = self.fc6[0].weight
-        key = (w.data_ptr(), w._version, dtype)
-        if self._fc6_nhwc is None or self._fc6_nhwc[0] != key:
-            p = self.pool_size
-            wp = w.detach().view(-1, self.dim_in, p, p).permute(0, 2, 3, 1).reshape(w.shape[0], -1).to(dtype).contiguous()
-            self._fc6_nhwc = (key, wp)
-        return self._fc6_nhwc[1]
+        w, p = self.fc6[0].weight, self.pool_size
+        relayout = lambda: w.detach().view(-1, self.dim_in, p, p).permute(0, 2, 3, 1).reshape(w.shape[0], -1).to(dtype).contiguous()
+        return ops.cached_pack(self, 'fc6_nhwc', (w,), relayout, dtype)
 
     def forward(self, feat, rois, num_rois_dev=None):
         pool_feat = self.roi_pooling(feat, rois, num_rois_dev)            # channels_last [N,C,7,7]

@@ -17,6 +17,36 @@ from ._lib import check, f32c, float_array, int_array, lib, nhwc, ptr, ptr_array
 PROFILE = {'enabled': False, 'events': []}
 
 
+def _prof_begin():
+    """Start event of one profiled launch, recorded on the launch stream; None (and nothing else done) while profiling is off."""
+    if not PROFILE['enabled']:
+        return None
+    ev0 = torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    return ev0
+
+
+def _prof_end(ev0, kind, flops, nbytes, label=None):
+    """Record the end event and append (kind, ev0, ev1, algorithmic flops, algorithmic bytes[, label]) to PROFILE['events']."""
+    ev1 = torch.cuda.Event(enable_timing=True)
+    ev1.record()
+    PROFILE['events'].append((kind, ev0, ev1, flops, nbytes) if label is None else (kind, ev0, ev1, flops, nbytes, label))
+
+
+def cached_pack(owner, slot, tensors, build, *extra):
+    """build() cached in owner.__dict__['_hip_plans'][slot], rebuilt when the key changes: (data_ptr, _version, shape) of every tensor
+    in `tensors` that is not None, then `extra`. The cache lives on its owner (a module, or the weight tensor itself), never in a
+    process-wide dict keyed by id(): the id -- and with the caching allocator even the weight's address -- of a freed model's layer can
+    be reused by a different layer of a later model, and a stale pack of another shape makes the kernel read out of bounds. Captured
+    HIP graphs hold the addresses of the packs of capture time, so a key must never change between warm-up and replay."""
+    key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in tensors if t is not None) + extra
+    plans = owner.__dict__.setdefault('_hip_plans', {})
+    ent = plans.get(slot)
+    if ent is None or ent[0] != key:
+        ent = plans[slot] = (key, build())
+    return ent[1]
+
+
 def last_kernel_form():
     """Test introspection (include/upsnet_hip.h: upsnet_last_kernel_form): the kernel instance this thread's last library-dispatched
     convolution launch took."""
@@ -115,18 +145,14 @@ def fpn_roi_align(feats, rois, pooled_h, pooled_w, spatial_scale, sampling_ratio
         # (the kernel trusts the table: a table that is not a permutation of 0..N-1 would leave output rows unwritten)
         if not (isinstance(order, torch.Tensor) and order.dtype == torch.int32 and order.numel() == N and order.device == rois.device and order.is_contiguous()):
             raise RuntimeError("fpn_roi_align: order must be a contiguous int32 tensor of %d entries on %s (from fpn_roi_order / pyramid_proposals)" % (N, rois.device))
-    if PROFILE['enabled']:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_fpn_roi_align_forward_ordered(stream(), ptr_array(feats), int_array([f.shape[2] for f in feats]),
                                                      int_array([f.shape[3] for f in feats]), float_array(spatial_scale), C,
                                                      ptr(rois), N, ptr(num_rois_dev), int(pooled_h), int(pooled_w),
                                                      int(sampling_ratio), ptr(out), ptr(levels), ptr(order)), "fpn_roi_align_forward_ordered")
-    if PROFILE['enabled']:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
-        PROFILE['events'].append(('roialign', ev0, ev1, 0.0, roi_align_algorithmic_bytes(feats, N, C, pooled_h, pooled_w),
-                                  'roialign %dx%dx%dx%d' % (N, C, pooled_h, pooled_w)))
+    if ev0 is not None:
+        _prof_end(ev0, 'roialign', 0.0, roi_align_algorithmic_bytes(feats, N, C, pooled_h, pooled_w),
+                  'roialign %dx%dx%dx%d' % (N, C, pooled_h, pooled_w))
     return (out, levels[:N]) if return_levels else out
 
 
@@ -267,12 +293,7 @@ def pack_dcn_weight(weight, kind=None):
 
 def cached_dcn_pack(weight):
     """Packed deformable-convolution weight cached ON the weight tensor (re-packed when it changes or moves)."""
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape), DCN_KERNEL, dcn_precision())
-    ent = weight.__dict__.get('_ups_dcn_pack')
-    if ent is None or ent[0] != key:
-        ent = (key, pack_dcn_weight(weight.detach()))
-        weight.__dict__['_ups_dcn_pack'] = ent
-    return ent[1]
+    return cached_pack(weight, 'dcn', (weight,), lambda: pack_dcn_weight(weight.detach()), DCN_KERNEL, dcn_precision())
 
 
 def fused_dcn_supported(cin, cout, deformable_groups, groups, pad=(0, 0), stride=(1, 1), dil=(1, 1)):
@@ -305,16 +326,6 @@ def dcn_ksplit(outs, cin, cout, taps):
     return ks
 
 
-def _dcn_event(ev0, xs, outs, cin, cout, ksize, kind='dcn_fused'):
-    ev1 = torch.cuda.Event(enable_timing=True)
-    ev1.record()
-    npix = sum(o.shape[2] * o.shape[3] for o in outs)
-    taps = ksize[0] * ksize[1]
-    PROFILE['events'].append((kind, ev0, ev1, 2.0 * cout * cin * taps * npix,
-                              4.0 * (sum(x.shape[2] * x.shape[3] for x in xs) * cin + npix * (2 * taps + cout) + cout * cin * taps),
-                              "dcn %d->%d %s" % (cin, cout, [tuple(x.shape[2:]) for x in xs])))
-
-
 def deform_conv_fused(xs, offsets, wpack, bias, cin, cout, ksize, stride, pad, dil, masks=None, relu=False):
     """Fused deformable conv over up to 4 maps sharing weights. xs/offsets/masks: lists of logical NCHW
     tensors with batch 1; wpack = (packed weight, ldw) from pack_dcn_weight; returns channels_last outputs."""
@@ -335,9 +346,7 @@ def deform_conv_fused(xs, offsets, wpack, bias, cin, cout, ksize, stride, pad, d
             raise RuntimeError("deform_conv_fused: offset shape %s != %s" % (tuple(o.shape), (1, 2 * ksize[0] * ksize[1], Ho, Wo)))
         outs.append(_nhwc_out(1, cout, Ho, Wo, x.device))
     b = None if bias is None else f32c(bias)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     if wp == 'frag_bf16':   # bf16 matrix cores (BASELINE configs[2])
         if not (pad[0] == pad[1] and stride[0] == stride[1] and dil[0] == dil[1]):
             raise RuntimeError("deform_conv_fused: square pad / stride / dilation only")
@@ -346,10 +355,7 @@ def deform_conv_fused(xs, offsets, wpack, bias, cin, cout, ksize, stride, pad, d
                                                        int_array([x.shape[2] for x in xs]), int_array([x.shape[3] for x in xs]),
                                                        int(cin), int(cout), ksize[0], ksize[1], pad[0], stride[0], dil[0], ptr(ldw), ptr(b),
                                                        int(bool(relu))), "deform_conv_fused_nhwc_bf16")
-        if PROFILE['enabled']:
-            _dcn_event(ev0, xs, outs, cin, cout, ksize, 'dcn_fused_bf16')
-        return outs
-    if wp == 'frag':   # (kind, packed) from pack_dcn_weight: second-generation kernel
+    elif wp == 'frag':   # (kind, packed) from pack_dcn_weight: second-generation kernel
         if not (pad[0] == pad[1] and stride[0] == stride[1] and dil[0] == dil[1]):
             raise RuntimeError("deform_conv_fused: square pad / stride / dilation only")
         ks = dcn_ksplit(outs, cin, cout, ksize[0] * ksize[1]) if n == 1 else 1
@@ -361,14 +367,12 @@ def deform_conv_fused(xs, offsets, wpack, bias, cin, cout, ksize, stride, pad, d
                                                              ptr(outs[0]), xs[0].shape[2], xs[0].shape[3], int(cin), int(cout), ksize[0],
                                                              ksize[1], pad[0], stride[0], dil[0], ptr(ldw), ptr(b), int(bool(relu)), ks, ptr(ws)),
                   "deform_conv_fused_nhwc_splitk")
-            if PROFILE['enabled']:
-                _dcn_event(ev0, xs, outs, cin, cout, ksize)
-            return outs
-        check(lib().upsnet_deform_conv_fused_nhwc(stream(), n, ptr_array(xs), ptr_array(offsets),
-                                                  ptr_array(masks) if masks is not None else None, ptr_array(outs),
-                                                  int_array([x.shape[2] for x in xs]), int_array([x.shape[3] for x in xs]),
-                                                  int(cin), int(cout), ksize[0], ksize[1], pad[0], stride[0], dil[0], ptr(ldw), ptr(b),
-                                                  int(bool(relu))), "deform_conv_fused_nhwc")
+        else:
+            check(lib().upsnet_deform_conv_fused_nhwc(stream(), n, ptr_array(xs), ptr_array(offsets),
+                                                      ptr_array(masks) if masks is not None else None, ptr_array(outs),
+                                                      int_array([x.shape[2] for x in xs]), int_array([x.shape[3] for x in xs]),
+                                                      int(cin), int(cout), ksize[0], ksize[1], pad[0], stride[0], dil[0], ptr(ldw), ptr(b),
+                                                      int(bool(relu))), "deform_conv_fused_nhwc")
     else:
         check(lib().upsnet_deform_conv_forward_nhwc(stream(), n, ptr_array(xs), ptr_array(offsets),
                                                     ptr_array(masks) if masks is not None else None, ptr_array(outs),
@@ -376,8 +380,12 @@ def deform_conv_fused(xs, offsets, wpack, bias, cin, cout, ksize, stride, pad, d
                                                     int(cin), int(cout), ksize[0], ksize[1], pad[0], pad[1], stride[0], stride[1],
                                                     dil[0], dil[1], 1, ptr(wp), int(ldw), ptr(b), int(bool(relu))),
               "deform_conv_forward_nhwc")
-    if PROFILE['enabled']:
-        _dcn_event(ev0, xs, outs, cin, cout, ksize)
+    if ev0 is not None:
+        npix = sum(o.shape[2] * o.shape[3] for o in outs)
+        taps = ksize[0] * ksize[1]
+        _prof_end(ev0, 'dcn_fused_bf16' if wp == 'frag_bf16' else 'dcn_fused', 2.0 * cout * cin * taps * npix,
+                  4.0 * (sum(x.shape[2] * x.shape[3] for x in xs) * cin + npix * (2 * taps + cout) + cout * cin * taps),
+                  "dcn %d->%d %s" % (cin, cout, [tuple(x.shape[2:]) for x in xs]))
     return outs
 
 
@@ -695,22 +703,19 @@ def conv2d_nhwc_multi(xs, wpack, ldw, bias, cout, ksize, stride, pad, relu=False
             want = (o.shape[0], o.shape[1], o.shape[2] // 2, o.shape[3] // 2) if residual_up else tuple(o.shape)
             if tuple(r.shape) != want or (residual_up and (o.shape[2] % 2 or o.shape[3] % 2)):
                 raise RuntimeError("conv2d_nhwc: residual shape %s != %s" % (tuple(r.shape), want))
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_nhwc_f32(stream(), len(xs), ptr_array(xs), ptr_array(ress) if ress is not None else None,
                                        ptr_array(outs), int_array([x.shape[0] for x in xs]), int_array([x.shape[2] for x in xs]),
                                        int_array([x.shape[3] for x in xs]), int(cin), ptr(wpack), int(ldw),
                                        ptr(None if bias is None else f32c(bias)), int(cout), int(ksize), int(ksize), int(stride),
                                        int(pad), int(bool(relu)), int(bool(residual_up and ress is not None))), "conv2d_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = sum(o.shape[0] * o.shape[2] * o.shape[3] for o in outs)
         nin = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xs)
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * ksize * ksize * npix,
-                                  4.0 * (cin * nin + cout * npix * (2 if ress is not None else 1) + cout * cin * ksize * ksize),
-                                  "direct %dx%d/%d %d->%d %s%s" % (ksize, ksize, stride, cin, cout, [tuple(x.shape[0:1] + x.shape[2:]) for x in xs],
-                                                                    " +res" if ress is not None else "")))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * ksize * ksize * npix,
+                  4.0 * (cin * nin + cout * npix * (2 if ress is not None else 1) + cout * cin * ksize * ksize),
+                  "direct %dx%d/%d %d->%d %s%s" % (ksize, ksize, stride, cin, cout, [tuple(x.shape[0:1] + x.shape[2:]) for x in xs],
+                                                    " +res" if ress is not None else ""))
     return outs
 
 
@@ -722,20 +727,16 @@ def conv2d_nhwc_multiw(xs, wpacks, ldw, cout, ksize, stride, pad, relu=False):
     cin = xs[0].shape[1]
     outs = [_nhwc_out(x.shape[0], cout, (x.shape[2] + 2 * pad - ksize) // stride + 1, (x.shape[3] + 2 * pad - ksize) // stride + 1, x.device)
             for x in xs]
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_nhwc_f32_multiw(stream(), len(xs), ptr_array(xs), ptr_array(outs), int_array([x.shape[0] for x in xs]),
                                               int_array([x.shape[2] for x in xs]), int_array([x.shape[3] for x in xs]), int(cin),
                                               ptr_array(wpacks), int(ldw), int(cout), int(ksize), int(ksize), int(stride), int(pad),
                                               int(bool(relu))), "conv2d_nhwc_f32_multiw")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = sum(o.shape[0] * o.shape[2] * o.shape[3] for o in outs)
         nin = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xs)
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * ksize * ksize * npix,
-                                  4.0 * (cin * nin + cout * npix + len(xs) * cout * cin * ksize * ksize),
-                                  "direct %dx%d/%d %d->%d %s per-map weights" % (ksize, ksize, stride, cin, cout, [tuple(x.shape[2:]) for x in xs])))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * ksize * ksize * npix, 4.0 * (cin * nin + cout * npix + len(xs) * cout * cin * ksize * ksize),
+                  "direct %dx%d/%d %d->%d %s per-map weights" % (ksize, ksize, stride, cin, cout, [tuple(x.shape[2:]) for x in xs]))
     return outs
 
 
@@ -775,9 +776,7 @@ def conv1x1_frag(x, wpack, bias, cout, stride=1, relu=False, residual=None, resi
         want = (N, cout, out.shape[2] // 2, out.shape[3] // 2) if residual_up else tuple(out.shape)
         if tuple(res.shape) != want or (residual_up and (out.shape[2] % 2 or out.shape[3] % 2)):
             raise RuntimeError("conv1x1_frag: residual shape %s != %s" % (tuple(res.shape), want))
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     if ksplit > 1:
         if residual_up:
             raise RuntimeError("conv1x1_frag: split-K has no upsampled-residual epilogue")
@@ -789,13 +788,11 @@ def conv1x1_frag(x, wpack, bias, cout, stride=1, relu=False, residual=None, resi
         check(lib().upsnet_conv1x1_frag_nhwc_f32(stream(), ptr(x), ptr(res), ptr(out), N, H, W, int(cin), ptr(wpack),
                                                  ptr(None if bias is None else f32c(bias)), int(cout), int(stride), int(bool(relu)),
                                                  int(bool(residual_up and res is not None))), "conv1x1_frag_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = out.shape[0] * out.shape[2] * out.shape[3]
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * npix,
-                                  4.0 * (cin * npix + cout * npix * (2 if res is not None else 1) + cout * cin),
-                                  "direct 1x1/%d %d->%d [%s]%s%s (gemm)" % (stride, cin, cout, tuple(x.shape[0:1] + x.shape[2:]), " +res" if res is not None else "",
-                                                                            " split-K x%d" % ksplit if ksplit > 1 else "")))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * npix, 4.0 * (cin * npix + cout * npix * (2 if res is not None else 1) + cout * cin),
+                  "direct 1x1/%d %d->%d [%s]%s%s (gemm)" % (stride, cin, cout, tuple(x.shape[0:1] + x.shape[2:]), " +res" if res is not None else "",
+                                                            " split-K x%d" % ksplit if ksplit > 1 else ""))
     return out
 
 
@@ -827,19 +824,15 @@ def conv1x1_ksw(x, wpack, bias, cout, tile, stride=1, relu=False, residual=None,
         res = nhwc(residual.float())
         if tuple(res.shape) != tuple(out.shape):
             raise RuntimeError("conv1x1_ksw: residual shape %s != %s" % (tuple(res.shape), tuple(out.shape)))
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv1x1_ksw_nhwc_f32(stream(), ptr(x), ptr(res), ptr(out), N, H, W, int(cin), ptr(wpack),
                                             ptr(None if bias is None else f32c(bias)), int(cout), int(stride), int(bool(relu)),
                                             int(tile[0]), int(tile[1]), int(bool(split_n))), "conv1x1_ksw_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = out.shape[0] * out.shape[2] * out.shape[3]
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * npix,
-                                  4.0 * (cin * npix + cout * npix * (2 if res is not None else 1) + cout * cin),
-                                  "direct 1x1/%d %d->%d [%s]%s (gemm ksw %dx%d%s)" % (stride, cin, cout, tuple(x.shape[0:1] + x.shape[2:]),
-                                                                                     " +res" if res is not None else "", tile[0], tile[1], "n" if split_n else "k")))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * npix, 4.0 * (cin * npix + cout * npix * (2 if res is not None else 1) + cout * cin),
+                  "direct 1x1/%d %d->%d [%s]%s (gemm ksw %dx%d%s)" % (stride, cin, cout, tuple(x.shape[0:1] + x.shape[2:]),
+                                                                     " +res" if res is not None else "", tile[0], tile[1], "n" if split_n else "k"))
     return out
 
 
@@ -860,16 +853,13 @@ def conv3x3_ksw(x, wpack, bias, cout, relu=False):
     x = nhwc(x.float())
     N, cin, H, W = x.shape
     out = _nhwc_out(N, cout, H, W, x.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv3x3_ksw_nhwc_f32(stream(), ptr(x), ptr(out), N, H, W, int(cin), ptr(wpack), ptr(None if bias is None else f32c(bias)),
                                             int(cout), int(bool(relu))), "conv3x3_ksw_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = N * H * W
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * 9 * npix, 4.0 * (cin * npix + cout * npix + cout * cin * 9),
-                                  "direct 3x3/1 %d->%d [%s] (ksw 16x32)" % (cin, cout, (N, H, W))))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * 9 * npix, 4.0 * (cin * npix + cout * npix + cout * cin * 9),
+                  "direct 3x3/1 %d->%d [%s] (ksw 16x32)" % (cin, cout, (N, H, W)))
     return out
 
 
@@ -882,17 +872,14 @@ def conv1x1_siblings(x, wpack, bias, cout_a, cout_b, stride=1, relu_a=True, relu
     N, cin, H, W = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     out_a, out_b = _nhwc_out(N, cout_a, Ho, Wo, x.device), _nhwc_out(N, cout_b, Ho, Wo, x.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv1x1_siblings_nhwc_f32(stream(), ptr(x), ptr(out_a), ptr(out_b), N, H, W, int(cin), ptr(wpack),
                                                  ptr(None if bias is None else f32c(bias)), int(cout_a), int(cout_b), int(stride),
                                                  int(bool(relu_a)), int(bool(relu_b))), "conv1x1_siblings_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix, cout = N * Ho * Wo, cout_a + cout_b
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * npix, 4.0 * (cin * npix + cout * npix + cout * cin),
-                                  "direct 1x1/%d siblings %d->%d+%d [%s] (gemm)" % (stride, cin, cout_a, cout_b, (N, H, W))))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * npix, 4.0 * (cin * npix + cout * npix + cout * cin),
+                  "direct 1x1/%d siblings %d->%d+%d [%s] (gemm)" % (stride, cin, cout_a, cout_b, (N, H, W)))
     return out_a, out_b
 
 
@@ -913,18 +900,14 @@ def conv1x1_pair(x, residual, w3pack, bias3, c1, w1pack, bias1, c2):
     if _pair32_waves_set[0] != PAIR32_WAVES:
         lib().upsnet_conv1x1_pair32_tuning(PAIR32_WAVES)
         _pair32_waves_set[0] = PAIR32_WAVES
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv1x1_pair_nhwc_f32(stream(), ptr(x), ptr(res), ptr(out1), ptr(out2), N * H * W, int(c0), ptr(w3pack),
                                              ptr(None if bias3 is None else f32c(bias3)), int(c1), ptr(w1pack),
                                              ptr(None if bias1 is None else f32c(bias1)), int(c2)), "conv1x1_pair_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = N * H * W
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * (c1 * c0 + c2 * c1) * npix,
-                                  4.0 * (c0 * npix + 2 * c1 * npix + c2 * npix + c1 * c0 + c2 * c1),
-                                  "direct 1x1 pair %d->%d->%d [%s] +res (gemm)" % (c0, c1, c2, (N, H, W))))
+        _prof_end(ev0, 'conv', 2.0 * (c1 * c0 + c2 * c1) * npix, 4.0 * (c0 * npix + 2 * c1 * npix + c2 * npix + c1 * c0 + c2 * c1),
+                  "direct 1x1 pair %d->%d->%d [%s] +res (gemm)" % (c0, c1, c2, (N, H, W)))
     return out1, out2
 
 
@@ -1000,13 +983,10 @@ def stem_pool_f32(x4, wpack, bias):
     Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
     out = _nhwc_out(N, 64, Hp, Wp, x4.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_stem_pool_f32(stream(), ptr(x4), N, H, W, ptr(wpack), ptr(None if bias is None else f32c(bias)), ptr(out)), "stem_pool_f32")
-    if PROFILE['enabled']:
-        ev1.record()
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * 64 * 147 * N * Hc * Wc, 16.0 * N * H * W + 4.0 * 64 * N * Hp * Wp + 4.0 * 64 * 147, 'stem + pool'))
+    if ev0 is not None:
+        _prof_end(ev0, 'conv', 2.0 * 64 * 147 * N * Hc * Wc, 16.0 * N * H * W + 4.0 * 64 * N * Hp * Wp + 4.0 * 64 * 147, 'stem + pool')
     return out
 
 
@@ -1032,13 +1012,10 @@ def stem_pool_bf16(x4, wpack, bias):
     Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
     out = torch.empty((N, Hp, Wp, 64), dtype=torch.bfloat16, device=x4.device).permute(0, 3, 1, 2)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_stem_pool_bf16(stream(), ptr(x4), N, H, W, ptr(wpack), ptr(None if bias is None else f32c(bias)), ptr(out)), "stem_pool_bf16")
-    if PROFILE['enabled']:
-        ev1.record()
-        PROFILE['events'].append(('conv_bf16', ev0, ev1, 2.0 * 64 * 147 * N * Hc * Wc, 16.0 * N * H * W + 2.0 * 64 * N * Hp * Wp))
+    if ev0 is not None:
+        _prof_end(ev0, 'conv_bf16', 2.0 * 64 * 147 * N * Hc * Wc, 16.0 * N * H * W + 2.0 * 64 * N * Hp * Wp)
     return out
 
 
@@ -1061,15 +1038,12 @@ def conv2d_stem(x4, wpack, ldw, bias, cout, kh, kw, stride, pad, relu=False):
         raise RuntimeError("conv2d_stem: input must have 4 channels (RGB + zero), got %d" % C)
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     out = _nhwc_out(N, cout, Ho, Wo, x4.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_stem_nhwc4_f32(stream(), ptr(x4), N, H, W, ptr(wpack), int(ldw), ptr(None if bias is None else f32c(bias)),
                                              int(cout), int(kh), int(kw), int(stride), int(pad), int(bool(relu)), ptr(out)),
           "conv2d_stem_nhwc4_f32")
-    if PROFILE['enabled']:
-        ev1.record()
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * 3 * kh * kw * N * Ho * Wo, 4.0 * (4 * N * H * W + cout * N * Ho * Wo + cout * 3 * kh * kw)))
+    if ev0 is not None:
+        _prof_end(ev0, 'conv', 2.0 * cout * 3 * kh * kw * N * Ho * Wo, 4.0 * (4 * N * H * W + cout * N * Ho * Wo + cout * 3 * kh * kw))
     return out
 
 
@@ -1092,14 +1066,11 @@ def deconv2x2(x, wpack, ldw, bias, cout, relu=False):
     x = nhwc(x.float())
     N, C, H, W = x.shape
     out = _nhwc_out(N, cout, 2 * H, 2 * W, x.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_deconv2x2_nhwc_f32(stream(), ptr(x), N, H, W, C, ptr(wpack), int(ldw), ptr(None if bias is None else f32c(bias)),
                                           int(cout), int(bool(relu)), ptr(out)), "deconv2x2_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * 4 * cout * C * N * H * W, 4.0 * (C * N * H * W + 4 * cout * N * H * W + 4 * cout * C)))
+    if ev0 is not None:
+        _prof_end(ev0, 'conv', 2.0 * 4 * cout * C * N * H * W, 4.0 * (C * N * H * W + 4 * cout * N * H * W + 4 * cout * C))
     return out
 
 
@@ -1120,15 +1091,12 @@ def deconv2x2_frag(x, wpack, bias4, cout, relu=False):
     x = nhwc(x.float())
     N, C, H, W = x.shape
     out = _nhwc_out(N, cout, 2 * H, 2 * W, x.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_deconv2x2_frag_nhwc_f32(stream(), ptr(x), ptr(out), N, H, W, C, ptr(wpack), ptr(bias4), int(cout), int(bool(relu))),
           "deconv2x2_frag_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * 4 * cout * C * N * H * W, 4.0 * (C * N * H * W + 4 * cout * N * H * W + 4 * cout * C),
-                                  "deconv 2x2/2 %d->%d [%s] (gemm)" % (C, cout, (N, H, W))))
+    if ev0 is not None:
+        _prof_end(ev0, 'conv', 2.0 * 4 * cout * C * N * H * W, 4.0 * (C * N * H * W + 4 * cout * N * H * W + 4 * cout * C),
+                  "deconv 2x2/2 %d->%d [%s] (gemm)" % (C, cout, (N, H, W)))
     return out
 
 
@@ -1153,15 +1121,12 @@ def deconv2x2_bf16(x, whi, ldw, bias, cout, relu=False, out_dtype=torch.float32)
     out16 = out_dtype == torch.bfloat16
     out = (torch.empty((N, 2 * H, 2 * W, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2) if out16
            else _nhwc_out(N, cout, 2 * H, 2 * W, x.device))
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_deconv2x2_nhwc_bf16(stream(), ptr(x), N, H, W, C, ptr(whi), int(ldw), ptr(None if bias is None else f32c(bias)),
                                            int(cout), int(bool(relu)), ptr(out), int(out16)), "deconv2x2_nhwc_bf16")
-    if PROFILE['enabled']:
-        ev1.record()
-        PROFILE['events'].append(('conv_bf16', ev0, ev1, 2.0 * 4 * cout * C * N * H * W,
-                                  2.0 * C * N * H * W + (2.0 if out16 else 4.0) * 4 * cout * N * H * W + 2.0 * 4 * cout * C))
+    if ev0 is not None:
+        _prof_end(ev0, 'conv_bf16', 2.0 * 4 * cout * C * N * H * W,
+                  2.0 * C * N * H * W + (2.0 if out16 else 4.0) * 4 * cout * N * H * W + 2.0 * 4 * cout * C)
     return out
 
 
@@ -1485,18 +1450,14 @@ def conv2d_winograd_splitk(x, wpack, ldw, bias, cout, ksplit, relu=False, residu
         if tuple(res.shape) != tuple(out.shape):
             raise RuntimeError("conv2d_winograd_splitk: residual shape %s != %s" % (tuple(res.shape), tuple(out.shape)))
     ws = _ws(lib().upsnet_conv2d_splitk_workspace_bytes(N, H, W, int(cout), 3, 3, 1, 1, int(ksplit)), x.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_winograd_nhwc_f32_splitk(stream(), ptr(x), ptr(res), ptr(out), N, H, W, C, ptr(wpack), int(ldw),
                                                        ptr(None if bias is None else f32c(bias)), int(cout), int(bool(relu)), int(ksplit),
                                                        ptr(ws)), "conv2d_winograd_nhwc_f32_splitk")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = N * H * W
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * C * 9 * npix,
-                                  4.0 * (C * npix + cout * npix * (2 if res is not None else 1) + cout * C * 9),
-                                  "winograd split-K x%d 3x3/1 %d->%d %s" % (ksplit, C, cout, (N, H, W))))
+        _prof_end(ev0, 'conv', 2.0 * cout * C * 9 * npix, 4.0 * (C * npix + cout * npix * (2 if res is not None else 1) + cout * C * 9),
+                  "winograd split-K x%d 3x3/1 %d->%d %s" % (ksplit, C, cout, (N, H, W)))
     return out
 
 
@@ -1508,17 +1469,14 @@ def conv2d_winograd_tail(x, wpack, ldw, wpack32, ldw32, bias, cout, n_main, relu
     x = nhwc(x.float())
     N, C, H, W = x.shape
     out = _nhwc_out(N, cout, H, W, x.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_winograd_nhwc_f32_tail(stream(), ptr(x), ptr(out), int(N), int(n_main), int(H), int(W), int(C), ptr(wpack), int(ldw),
                                                      ptr(wpack32), int(ldw32), ptr(None if bias is None else f32c(bias)), int(cout),
                                                      int(bool(relu))), "conv2d_winograd_nhwc_f32_tail")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = N * H * W
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * C * 9 * npix, 4.0 * (C * npix + cout * npix + cout * C * 9),
-                                  "winograd 3x3/1 %d->%d [%s] tail %d" % (C, cout, (N, H, W), N - n_main)))
+        _prof_end(ev0, 'conv', 2.0 * cout * C * 9 * npix, 4.0 * (C * npix + cout * npix + cout * C * 9),
+                  "winograd 3x3/1 %d->%d [%s] tail %d" % (C, cout, (N, H, W), N - n_main))
     return out
 
 
@@ -1547,23 +1505,19 @@ def conv2d_winograd_multi(xs, wpack, ldw, bias, cout, relu=False, residuals=None
         for r, o in zip(ress, outs):
             if tuple(r.shape) != tuple(o.shape):
                 raise RuntimeError("conv2d_winograd: residual shape %s != %s" % (tuple(r.shape), tuple(o.shape)))
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     fn = lib().upsnet_conv2d_winograd_nhwc_f32_tn32 if tn32 else lib().upsnet_conv2d_winograd_nhwc_f32
     check(fn(stream(), len(xs), ptr_array(xs), ptr_array(ress) if ress is not None else None,
              ptr_array(outs), int_array([x.shape[0] for x in xs]), int_array([x.shape[2] for x in xs]),
              int_array([x.shape[3] for x in xs]), int(cin), ptr(wpack), int(ldw),
              ptr(None if bias is None else f32c(bias)), int(cout), int(bool(relu))),
           "conv2d_winograd_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = sum(o.shape[0] * o.shape[2] * o.shape[3] for o in outs)
         # algorithmic work of the convolution (direct-form flops), as for the direct kernel
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * 9 * npix,
-                                  4.0 * (cin * npix + cout * npix * (2 if ress is not None else 1) + cout * cin * 9),
-                                  "winograd 3x3/1 %d->%d %s%s%s" % (cin, cout, [tuple(x.shape[0:1] + x.shape[2:]) for x in xs],
-                                                                    " +res" if ress is not None else "", " tn32" if tn32 else "")))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * 9 * npix, 4.0 * (cin * npix + cout * npix * (2 if ress is not None else 1) + cout * cin * 9),
+                  "winograd 3x3/1 %d->%d %s%s%s" % (cin, cout, [tuple(x.shape[0:1] + x.shape[2:]) for x in xs],
+                                                    " +res" if ress is not None else "", " tn32" if tn32 else ""))
     return outs
 
 
@@ -1599,18 +1553,15 @@ def conv2d_winograd36_multi(xs, wpack, ldw, bias, cout, relu=False, outs=None):
             outs.append(o)
         else:
             outs.append(_nhwc_out(N, cout, H, W, x.device))
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_winograd36_nhwc_f32(stream(), len(xs), ptr_array(xs), ptr_array(outs), int_array([x.shape[0] for x in xs]),
                                                   int_array([x.shape[2] for x in xs]), int_array([x.shape[3] for x in xs]), int(cin), ptr(wpack),
                                                   int(ldw), ptr(None if bias is None else f32c(bias)), int(cout), int(bool(relu))),
           "conv2d_winograd36_nhwc_f32")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = sum(o.shape[0] * o.shape[2] * o.shape[3] for o in outs)
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * 9 * npix, 4.0 * (cin * npix + cout * npix + cout * cin * 9),
-                                  "winograd36 3x3/1 %d->%d %s" % (cin, cout, [tuple(x.shape[0:1] + x.shape[2:]) for x in xs])))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * 9 * npix, 4.0 * (cin * npix + cout * npix + cout * cin * 9),
+                  "winograd36 3x3/1 %d->%d %s" % (cin, cout, [tuple(x.shape[0:1] + x.shape[2:]) for x in xs]))
     return outs
 
 
@@ -1622,17 +1573,14 @@ def conv2d_winograd36_splitk(x, wpack, ldw, bias, cout, ksplit, relu=False):
     N, cin, H, W = x.shape
     out = _nhwc_out(N, cout, H, W, x.device)
     ws = _ws(lib().upsnet_conv2d_winograd36_splitk_workspace_bytes(N, H, W, int(cout), int(ksplit)), x.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_winograd36_nhwc_f32_splitk(stream(), ptr(x), ptr(out), N, H, W, int(cin), ptr(wpack), int(ldw),
                                                          ptr(None if bias is None else f32c(bias)), int(cout), int(bool(relu)), int(ksplit), ptr(ws)),
           "conv2d_winograd36_nhwc_f32_splitk")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = N * H * W
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * cin * 9 * npix, 4.0 * (cin * npix + cout * npix + cout * cin * 9),
-                                  "winograd36 split-K x%d 3x3/1 %d->%d %s" % (ksplit, cin, cout, (N, H, W))))
+        _prof_end(ev0, 'conv', 2.0 * cout * cin * 9 * npix, 4.0 * (cin * npix + cout * npix + cout * cin * 9),
+                  "winograd36 split-K x%d 3x3/1 %d->%d %s" % (ksplit, cin, cout, (N, H, W)))
     return out
 
 
@@ -1685,23 +1633,20 @@ def conv2d_nhwc_bf16_multi(xs, whi, wlo, ldw, bias, cout, ksize, stride, pad, re
             want = (o.shape[0], o.shape[1], o.shape[2] // 2, o.shape[3] // 2) if residual_up else tuple(o.shape)
             if tuple(r.shape) != want:
                 raise RuntimeError("conv2d_nhwc_bf16: residual shape %s != %s" % (tuple(r.shape), want))
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_nhwc_bf16(stream(), len(xs), ptr_array(xs), ptr_array(ress) if ress is not None else None, ptr_array(outs),
                                         int_array([x.shape[0] for x in xs]), int_array([x.shape[2] for x in xs]),
                                         int_array([x.shape[3] for x in xs]), int(cin), ptr(whi), ptr(wlo), int(ldw),
                                         ptr(None if bias is None else f32c(bias)), int(cout), int(ksize), int(ksize), int(stride), int(pad),
                                         int(bool(relu)) | (2 if (residual_up and ress is not None) else 0) | (4 if in16 else 0) |
                                         (8 if out16 else 0) | (16 if res16 else 0)), "conv2d_nhwc_bf16")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = sum(o.shape[0] * o.shape[2] * o.shape[3] for o in outs)
         nin = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xs)
-        PROFILE['events'].append(('conv_bf16', ev0, ev1, 2.0 * cout * cin * ksize * ksize * npix,
-                                  (2.0 if in16 else 4.0) * cin * nin + (2.0 if out16 else 4.0) * cout * npix +
-                                  ((2.0 if res16 else 4.0) * cout * npix * (0.25 if residual_up else 1.0) if ress is not None else 0.0) +
-                                  2.0 * cout * cin * ksize * ksize))
+        _prof_end(ev0, 'conv_bf16', 2.0 * cout * cin * ksize * ksize * npix,
+                  (2.0 if in16 else 4.0) * cin * nin + (2.0 if out16 else 4.0) * cout * npix +
+                  ((2.0 if res16 else 4.0) * cout * npix * (0.25 if residual_up else 1.0) if ress is not None else 0.0) +
+                  2.0 * cout * cin * ksize * ksize)
     return outs
 
 
@@ -1752,15 +1697,12 @@ def bottleneck_proj_bf16(x, pack, stride):
     N, C, H, W = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     out = torch.empty((N, Ho, Wo, 4 * cm), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_bottleneck_proj_bf16(stream(), ptr(x), ptr(out), N, H, W, int(cin), int(cm), int(stride), ptr(w1), ptr(w2), ptr(w3d),
                                             ptr(b1), ptr(b2), ptr(b3d)), "bottleneck_proj_bf16")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         k = cm * cin + 9 * cm * cm + 4 * cm * (cm + cin)
-        PROFILE['events'].append(('bottleneck_bf16', ev0, ev1, 2.0 * k * N * Ho * Wo, 2.0 * C * N * Ho * Wo + 2.0 * 4 * cm * N * Ho * Wo + 2.0 * k))
+        _prof_end(ev0, 'bottleneck_bf16', 2.0 * k * N * Ho * Wo, 2.0 * C * N * Ho * Wo + 2.0 * 4 * cm * N * Ho * Wo + 2.0 * k)
     return out
 
 
@@ -1773,14 +1715,11 @@ def bottleneck_bf16(x, pack):
     x = nhwc(x)
     N, C, H, W = x.shape
     out = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_bottleneck_bf16(stream(), ptr(x), ptr(out), N, H, W, cm, ptr(w1), ptr(w2), ptr(w3), ptr(b1), ptr(b2), ptr(b3)),
           "bottleneck_bf16")
-    if PROFILE['enabled']:
-        ev1.record()
-        PROFILE['events'].append(('bottleneck_bf16', ev0, ev1, 2.0 * 17 * cm * cm * N * H * W, 2.0 * 2 * C * N * H * W + 2.0 * 17 * cm * cm))
+    if ev0 is not None:
+        _prof_end(ev0, 'bottleneck_bf16', 2.0 * 17 * cm * cm * N * H * W, 2.0 * 2 * C * N * H * W + 2.0 * 17 * cm * cm)
     return out
 
 
@@ -1797,18 +1736,15 @@ def conv2d_nhwc_splitk(x, wpack, ldw, bias, cout, ksize, stride, pad, ksplit, re
         if tuple(res.shape) != tuple(out.shape):
             raise RuntimeError("conv2d_nhwc_splitk: residual shape %s != %s" % (tuple(res.shape), tuple(out.shape)))
     ws = _ws(lib().upsnet_conv2d_splitk_workspace_bytes(N, H, W, int(cout), int(ksize), int(ksize), int(stride), int(pad), int(ksplit)), x.device)
-    if PROFILE['enabled']:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _prof_begin()
     check(lib().upsnet_conv2d_nhwc_f32_splitk(stream(), ptr(x), ptr(res), ptr(out), N, H, W, C, ptr(wpack), int(ldw),
                                               ptr(None if bias is None else f32c(bias)), int(cout), int(ksize), int(ksize), int(stride),
                                               int(pad), int(bool(relu)), int(ksplit), ptr(ws)), "conv2d_nhwc_f32_splitk")
-    if PROFILE['enabled']:
-        ev1.record()
+    if ev0 is not None:
         npix = N * Ho * Wo
-        PROFILE['events'].append(('conv', ev0, ev1, 2.0 * cout * C * ksize * ksize * npix,
-                                  4.0 * (C * N * H * W + cout * npix * (2 if res is not None else 1) + cout * C * ksize * ksize),
-                                  "split-K x%d %dx%d/%d %d->%d %s" % (ksplit, ksize, ksize, stride, C, cout, (N, H, W))))
+        _prof_end(ev0, 'conv', 2.0 * cout * C * ksize * ksize * npix,
+                  4.0 * (C * N * H * W + cout * npix * (2 if res is not None else 1) + cout * C * ksize * ksize),
+                  "split-K x%d %dx%d/%d %d->%d %s" % (ksplit, ksize, ksize, stride, C, cout, (N, H, W)))
     return out
 
 
