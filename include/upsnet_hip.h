@@ -780,6 +780,25 @@ int upsnet_det_eval_accumulate(void *stream, long num_records, const double *rec
                                const int64_t *npig, const double *rec_thrs, void *workspace, double *precision, double *recall,
                                double *scores);
 
+/* Polygon GT -> run-length masks for upsnet_det_eval_image (gt_trans / gt_trans_off), all polygon objects of ONE image: pycocotools'
+ * rleFrPoly (frPyObjects of a polygon list) and merge (union) restated from the published algorithm (csrc/poly_raster.hip).
+ *   vertices double [total_vertices][2] (x, y) on the device; poly_off int [num_poly + 1]: the first vertex of each polygon;
+ *   obj_off int [num_obj + 1]: the first polygon of each object. Both tables are given twice, on the HOST (validated here: start at 0,
+ *   monotone, obj_off[num_obj] = num_poly) and as device copies (*_dev) that the kernels read.
+ *   total_points: the sum over all edges (every vertex starts one, the last vertex of a polygon back to the first) of
+ *   max(|dX|, |dY|) + 1 with X = (int)(5 * x + .5), Y likewise -- an exact upper bound of the positions emitted; at most 2^24.
+ *   The caller guarantees finite coordinates with |5 * c| < 2^30 (the vertices are device data and are not inspected).
+ * Outputs on the device: trans int [total_points] (the first trans_off[num_obj] entries are written: per object the ascending
+ *   column-major positions x * height + y in [0, H * W) where the mask changes, the first starting a run of ones), trans_off int64
+ *   [num_obj + 1] (fully written). An object without polygons, or whose polygons emit nothing, has an empty list.
+ * workspace: upsnet_poly_raster_workspace_bytes(total_vertices, total_points) bytes (0 = arguments out of range), 256-byte aligned; no
+ * zeroing. H * W < 2^31. Launches on `stream` only, no host synchronisation, no allocation; the result does not depend on how objects
+ * are grouped into calls. */
+size_t upsnet_poly_raster_workspace_bytes(long total_vertices, long total_points);
+int upsnet_poly_raster(void *stream, const double *vertices, const int *poly_off, const int *obj_off, const int *poly_off_dev,
+                       const int *obj_off_dev, int num_poly, int num_obj, long total_points, int height, int width, void *workspace,
+                       int *trans, int64_t *trans_off);
+
 /* ============================== Evaluation: RPN proposal recall (Detectron's AR, evaluate_box_proposals) ============================== */
 
 /* BaseDataset.evaluate_box_proposals (upsnet/dataset/base_dataset.py:723-805), the greedy matching of each (image, area, limit) problem,

@@ -134,6 +134,8 @@ _SIGNATURES = {
                                       P, P, P, c_int, P, P, c_int, P, c_int, P, c_int, P, P, P, P, P, P, P]),
     "upsnet_det_eval_accumulate_workspace_bytes": (c_size_t, [c_long, c_int]),
     "upsnet_det_eval_accumulate": (c_int, [P, c_long, P, P, P, P, P, P, c_int, P, P, P, P, P, P]),
+    "upsnet_poly_raster_workspace_bytes": (c_size_t, [c_long, c_long]),
+    "upsnet_poly_raster": (c_int, [P, P, P, P, P, P, c_int, c_int, c_long, c_int, c_int, P, P, P]),
     "upsnet_proposal_recall_workspace_bytes": (c_size_t, [c_int, c_long]),
     "upsnet_proposal_recall": (c_int, [P, c_int, P, P, P, c_int, c_long, P, P]),
 }

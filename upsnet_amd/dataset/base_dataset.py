@@ -197,7 +197,10 @@ class BaseDataset(object):
         for i, image_id in enumerate(image_ids):
             dets = [[]] + [all_boxes[c][i] for c in range(1, n_cls)]
             rles = None if all_segms is None else [[]] + [all_segms[c][i] for c in range(1, n_cls)]
-            ev.add_rle(image_id, anns.get(image_id, []), dets, rles, image_size=sizes[image_id])
+            gt = anns.get(image_id, [])
+            if all_segms is not None:
+                gt = self._rasterize_polygon_gt(gt, sizes[image_id])
+            ev.add_rle(image_id, gt, dets, rles, image_size=sizes[image_id])
         res = ev.accumulate()
         for line in detection_metrics_lines(res)[:-12]:
             logger.info(line)
@@ -207,6 +210,21 @@ class BaseDataset(object):
                 f.write(line + '\n')
         return EvalResult(res)
 
+    @staticmethod
+    def _rasterize_polygon_gt(gt, size):
+        """The image's annotations with every polygon segmentation (a list: all non-crowd objects of the COCO and Cityscapes instance
+        files) replaced by a view of one rasterize_polygons call (dataset/polygon.py: on the device, nothing synchronised); RLE
+        segmentations (crowds) pass as they are. The annotations themselves are not modified."""
+        from .polygon import rasterize_polygons
+        poly = [k for k, a in enumerate(gt) if isinstance(a.get('segmentation'), (list, tuple))]
+        if not poly:
+            return gt
+        rasters = rasterize_polygons([gt[k]['segmentation'] for k in poly], size[0], size[1])
+        gt = list(gt)
+        for j, k in enumerate(poly):
+            gt[k] = dict(gt[k], segmentation=rasters[j])
+        return gt
+
     def evaluate_boxes(self, all_boxes, output_dir):
         """COCO box AP of all_boxes[class][image] ([n,5] x1 y1 x2 y2 score, images in ascending id) against
         self.instances_json_file; returns the 12 summary stats. Writes bbox_<name>_results.json and detection_results.txt."""
@@ -215,7 +233,7 @@ class BaseDataset(object):
     def evaluate_masks(self, all_boxes, all_segms, output_dir):
         """COCO mask AP of all_segms[class][image] (im_post's RLE dicts) scored by all_boxes; returns an object with .stats and
         .eval (precision / recall / scores). Writes segmentations_<name>_results.json and detection_results.txt. Polygon GT
-        segmentations are refused (ValueError, dataset/coco_eval.py)."""
+        segmentations are rasterised on the device, one call per image (dataset/polygon.py)."""
         return self._evaluate_detections(all_boxes, all_segms, output_dir, 'segm')
 
     # ---------------------------------------------------------------------------------------------- RPN proposal recall (AR)

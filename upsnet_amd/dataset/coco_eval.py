@@ -9,8 +9,9 @@ bit-identical to pycocotools' for the same inputs. Category rows K are the categ
 Deliberate deviations, each refused with ValueError before any launch:
   * wrong shapes or dtypes, GT ids <= 0 (evaluateImg stores GT ids as match flags), a category id given twice, an image_id added
     twice, masks whose size differs from the image;
-  * polygon GT segmentations: their conversion to RLE (frPyObjects) has no implementation here to pin a rasterizer against, so
-    they are refused by name rather than approximated.
+  * a bare polygon list as a GT segmentation: polygons are rasterised on the device by dataset/polygon.py (csrc/poly_raster.hip,
+    frPyObjects + merge restated) and reach `add` / `add_rle` as views of its handle, `rasterize_polygons(...)[i]`; their run lists
+    go to the kernels next to the RLE rows and never visit the host. Views of one call must come from one handle, each at most once.
 Detections of classes with no category id are dropped, as pycocotools drops results of categories outside Params.catIds; so are
 GTs of other categories. Scores must not be NaN (they are device data and are not inspected). Proposal recall
 (evaluate_box_proposals) and the Cityscapes instance-level script are out of scope.
@@ -22,6 +23,7 @@ import numpy as np
 import torch
 
 from .._lib import check, lib, ptr, stream
+from .polygon import PolygonView
 
 logger = logging.getLogger(__name__)
 
@@ -59,8 +61,8 @@ def rle_from_string(s):
 def rle_counts(seg):
     """An RLE dict ({'size': [h, w], 'counts': str | bytes | list}) -> (counts int64 array, (h, w)). Polygons: ValueError."""
     if isinstance(seg, (list, tuple)):
-        raise ValueError("polygon GT segmentations are not supported (their rasterisation, frPyObjects, is not restated here); "
-                         "convert them to RLE first")
+        raise ValueError("a bare polygon list is not taken as a segmentation: rasterise the image's polygon annotations with "
+                         "dataset.polygon.rasterize_polygons and pass handle[i] (or convert one with dataset.polygon.polygons_to_rle)")
     if not isinstance(seg, dict) or 'counts' not in seg or 'size' not in seg:
         raise ValueError("segmentation must be an RLE dict with 'size' and 'counts', got %r" % type(seg))
     c = seg['counts']
@@ -225,9 +227,17 @@ class DetectionEvaluator(object):
             out['box'] = box
             return out
         H, W = size
-        trans, off, dst, u8, u8_dst = [], [0], [], [], []
+        trans, off, dst, u8, u8_dst, poly, poly_dst = [], [0], [], [], [], [], []
         for g, el in enumerate(keep):
             seg = el.get('segmentation')
+            if isinstance(seg, PolygonView):
+                if seg.size != (H, W):
+                    raise ValueError("GT %d: mask size %s differs from the image %s" % (el['id'], seg.size, (H, W)))
+                if poly and seg.rasters is not poly[0].rasters:
+                    raise ValueError("GT %d: the polygon views of one image must come from one rasterize_polygons call" % el['id'])
+                poly.append(seg)
+                poly_dst.append(g)
+                continue
             if isinstance(seg, (torch.Tensor, np.ndarray)):
                 if seg.dtype not in (torch.uint8, np.uint8) or tuple(seg.shape) != (H, W):
                     raise ValueError("GT %d: uint8 mask of shape %s expected, got %s %s" % (el['id'], (H, W), tuple(seg.shape), seg.dtype))
@@ -242,8 +252,27 @@ class DetectionEvaluator(object):
             off.append(off[-1] + len(t))
             dst.append(g)
         out.update(trans=np.concatenate(trans) if trans else np.zeros(0, np.int64), trans_off=np.array(off, np.int64),
-                   trans_dst=np.array(dst, np.int32), u8=u8, u8_dst=u8_dst)
+                   trans_dst=np.array(dst, np.int32), u8=u8, u8_dst=u8_dst, poly=poly, poly_dst=poly_dst)
+        if len(set(v.index for v in poly)) != len(poly):
+            raise ValueError("a polygon view is the segmentation of two GTs")
         return out
+
+    def _poly_rows(self, views):
+        """The run lists of the views (objects of one PolygonRasters) as (trans int32, trans_off int64 [len(views) + 1]) on the device.
+        All objects of the handle in order: its own tensors. Otherwise the chosen lists are gathered into a buffer of the handle's
+        capacity; every shape is known on the host, so nothing is synchronised."""
+        h = views[0].rasters
+        trans, off = h.trans.to(self.device), h.trans_off.to(self.device)
+        idx = [v.index for v in views]
+        if idx == list(range(len(h))):
+            return trans, off
+        idx = self._upload(np.asarray(idx), np.int64)
+        start = off[idx]
+        new_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(off[idx + 1] - start, 0)])
+        pos = torch.arange(trans.numel(), dtype=torch.int64, device=self.device)
+        row = torch.searchsorted(new_off[1:].contiguous(), pos, right=True).clamp_(max=len(views) - 1)
+        src = (start[row] + (pos - new_off[row])).clamp_(0, trans.numel() - 1)   # past the last list: any entry (never read)
+        return trans[src], new_off
 
     # ---------------------------------------------------------------------------------------------------------- add
     def add(self, image_id, gt, det_boxes, det_scores, det_cls, det_masks=None, image_size=None):
@@ -358,8 +387,15 @@ class DetectionEvaluator(object):
                 det_trans, det_off = up(trans, np.int32), up(trans_off, np.int64)
             else:
                 C, Ms = masks.shape[1], masks.shape[3]
-            gt_trans, gt_off, gt_dst = up(g['trans'], np.int32), up(g['trans_off'], np.int64), up(g['trans_dst'], np.int32)
-            n_rle = len(g['trans_dst'])
+            gt_trans, gt_off = up(g['trans'], np.int32), up(g['trans_off'], np.int64)
+            dst = g['trans_dst']
+            if g['poly']:   # the device run lists of the polygon GTs follow the host RLE rows; gt_trans_dst maps each row to its GT
+                p_trans, p_off = self._poly_rows(g['poly'])
+                gt_trans = torch.cat([gt_trans[:len(g['trans'])], p_trans])
+                gt_off = torch.cat([gt_off[:len(dst)], p_off + len(g['trans'])])
+                dst = np.concatenate([dst, np.asarray(g['poly_dst'], np.int32)])
+            gt_dst = up(dst, np.int32)
+            n_rle = len(dst)
             u8 = [torch.as_tensor(m).to(self.device).contiguous() for m in g['u8']]
             n_u8 = len(u8)
             if n_u8:
