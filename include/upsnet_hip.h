@@ -817,6 +817,37 @@ size_t upsnet_proposal_recall_workspace_bytes(int num_problems, long total_propo
 int upsnet_proposal_recall(void *stream, int num_problems, const int64_t *problems, const float *proposals, const float *gt_boxes,
                            int max_gt, long total_proposals, void *workspace, float *out);
 
+/* ============================== Evaluation: Cityscapes instance-level AP (the devkit's region AP) ============================== */
+
+/* The per-image part of the Cityscapes devkit's evalInstanceLevelSemanticLabeling (default arguments; the rules are restated in
+ * dataset/cityscapes_eval.py and DESIGN 4.10), csrc/cs_inst_eval.hip. All on `stream`, no host synchronisation, no allocation.
+ *   gt_ids uint16 [height][width]: the gtFine_instanceIds map on the device; height * width <= 2^30.
+ *   pred_cls int [num_preds] (1..8 = person rider car truck bus train motorcycle bicycle), pred_scores float [num_preds] (not NaN;
+ *   device data, not inspected). Masks either as run lengths -- trans int [trans_off[num_preds]], trans_off int [num_preds + 1]: per
+ *   prediction the ascending column-major positions x * height + y in [0, H * W) where the mask changes, the first starting a run of
+ *   ones; masks = NULL -- or dense, masks uint8 [num_preds][height][width] (non-zero = inside; trans = trans_off = NULL).
+ *   walk_strided = 0: the run lists are walked over a transposed copy of the map written to gt_t (uint16 [width][height]);
+ *   walk_strided = 1: over the row-major map itself (gt_t unused). Same counts either way.
+ *   thresholds: num_thr (1..16) doubles on the HOST, each in [0.5, 1): above 0.5 a prediction overlaps at most one region.
+ * Outputs on the device:
+ *   counts int [upsnet_cs_inst_counts_ints(num_preds)] (zeroed here): per prediction 1003 ints = area | intersection with void pixels |
+ *     intersection with slot 0..1000 of its class (slot 0 = the group region, raw value = label id; slot 1 + k = raw value 1000 * label
+ *     id + k), then int [8][1001]: the pixel count of every slot of every class;
+ *   rec_score float [num_preds] (a copy), rec_cls uint8 [num_preds] (the class; 0 = a prediction of no pixels, dropped), rec_code uint8
+ *     [num_preds][num_thr]: 1 = the entry (1, score), 2 = the entry (0, score), 0 = no entry (ignored, or matched to a group / small
+ *     region only); rows of a class outside 1..8 are not written;
+ *   state int64 [upsnet_cs_inst_state_words()], running sums the caller zeroes once: hard false negatives [8][16] (class, threshold) |
+ *     images with a valid GT region [8] | predictions of non-zero area [8].
+ * workspace: upsnet_cs_inst_workspace_bytes(num_preds) bytes, 8-byte aligned, no zeroing. num_preds = 0 (all prediction pointers may be
+ * NULL) still counts the image's GT. Both size functions return 0 for num_preds outside 0..65535. */
+size_t upsnet_cs_inst_counts_ints(int num_preds);
+size_t upsnet_cs_inst_workspace_bytes(int num_preds);
+int upsnet_cs_inst_state_words(void);
+int upsnet_cs_inst_image(void *stream, const uint16_t *gt_ids, int height, int width, int num_preds, const int *pred_cls,
+                         const float *pred_scores, const int *trans, const int *trans_off, const unsigned char *masks, int walk_strided,
+                         uint16_t *gt_t, const double *thresholds, int num_thr, int *counts, void *workspace, float *rec_score,
+                         unsigned char *rec_cls, unsigned char *rec_code, int64_t *state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,10 @@ _SIGNATURES = {
     "upsnet_poly_raster": (c_int, [P, P, P, P, P, P, c_int, c_int, c_long, c_int, c_int, P, P, P]),
     "upsnet_proposal_recall_workspace_bytes": (c_size_t, [c_int, c_long]),
     "upsnet_proposal_recall": (c_int, [P, c_int, P, P, P, c_int, c_long, P, P]),
+    "upsnet_cs_inst_counts_ints": (c_size_t, [c_int]),
+    "upsnet_cs_inst_workspace_bytes": (c_size_t, [c_int]),
+    "upsnet_cs_inst_state_words": (c_int, []),
+    "upsnet_cs_inst_image": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, c_int, P, P, c_int, P, P, P, P, P, P]),
 }
 
 _lib = None

@@ -14,7 +14,7 @@ Deliberate deviations, each refused with ValueError before any launch:
     go to the kernels next to the RLE rows and never visit the host. Views of one call must come from one handle, each at most once.
 Detections of classes with no category id are dropped, as pycocotools drops results of categories outside Params.catIds; so are
 GTs of other categories. Scores must not be NaN (they are device data and are not inspected). Proposal recall
-(evaluate_box_proposals) and the Cityscapes instance-level script are out of scope.
+(evaluate_box_proposals) is dataset/proposal_eval.py, the Cityscapes instance-level AP dataset/cityscapes_eval.py.
 """
 import ctypes
 import logging

@@ -2,7 +2,7 @@
 (upsnet/upsnet_end2end_test.py:155-314).
 
     python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
-                                  [--eval_proposals]
+                                  [--eval_proposals] [--eval_instances]
 
 The dataset is `config.dataset.dataset` (Cityscapes or coco) on `config.dataset.test_image_set`. Every image and every GT file the
 configured heads need is checked before the first launch. Images are decoded by a bounded host thread pool ahead of the device;
@@ -13,7 +13,9 @@ original resolution by one gather launch (csrc/restore.hip, cv2 INTER_NEAREST ta
 path, keys and nesting (numpy objects only); evaluation follows the reference's order: boxes, masks, panoptic, semantic.
 `--eval_only` re-scores the pickle without building the model. `--pan_combined` also scores get_combined_pan_result (the
 heuristic merge of the detections and the semantic map) next to the unified result. `--eval_proposals` keeps the RPN proposals
-of every image (results['all_proposals'], original image scale) and scores their recall (metrics['proposal_ar']). One rank only (WORLD_SIZE > 1 is refused)."""
+of every image (results['all_proposals'], original image scale) and scores their recall (metrics['proposal_ar']).
+`--eval_instances` (Cityscapes with a mask head) also scores the instance masks with the Cityscapes instance-level AP against the
+gtFine instanceIds maps (metrics['instance_ap'], dataset/cityscapes_eval.py). One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
 import pickle
@@ -145,11 +147,11 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
     return results, times
 
 
-def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False):
+def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
     'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
-    results['all_proposals']) with eval_proposals."""
+    results['all_proposals']) with eval_proposals and 'instance_ap' (Cityscapes instance-level AP summary) with eval_instances."""
     net = config.network
     metrics = {}
     if not dataset.has_gt:
@@ -181,6 +183,9 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
         logger.info('proposal recall:')
         # (the roidb, and so the results lists, are in ascending image id, the order evaluate_proposals takes)
         metrics['proposal_ar'] = dataset.evaluate_proposals(results['all_proposals'], results_dir)
+    if eval_instances:
+        logger.info('instance-level result:')
+        metrics['instance_ap'] = dataset.evaluate_instances(results['all_boxes'], results['all_masks'], results_dir)
     return metrics
 
 
@@ -202,6 +207,10 @@ def main(argv=None):
         raise SystemExit('--pan_combined merges detections, instance masks and the semantic map: it needs network.has_rcnn, '
                          'has_mask_head and has_fcn_head (has_rcnn=%s, has_mask_head=%s, has_fcn_head=%s)'
                          % (net.has_rcnn, net.has_mask_head, net.has_fcn_head))
+    if args.eval_instances and not (config.dataset.dataset == 'Cityscapes' and net.has_rcnn and net.has_mask_head):
+        raise SystemExit('--eval_instances scores instance masks against the Cityscapes gtFine instanceIds maps: it needs '
+                         'dataset.dataset = Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
+                         % (config.dataset.dataset, net.has_rcnn, net.has_mask_head))
     out_dir = final_output_path(args.cfg)
     results_dir = os.path.join(out_dir, 'results')
     results_file = os.path.join(results_dir, 'results_list.pkl')
@@ -215,11 +224,15 @@ def main(argv=None):
                              '--eval_only first' % results_file)
         dataset = build_dataset(out_dir)
         dataset.check_files(images=False)
-        return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals),
+        if args.eval_instances:
+            dataset.check_instance_files()
+        return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances),
                 'results_file': results_file, 'times': None}
 
     dataset = build_dataset(out_dir)
     dataset.check_files()       # every image and GT file, before the first launch
+    if args.eval_instances:
+        dataset.check_instance_files()
     from .upsnet_end2end_test import init_distributed, load_checkpoint_model
     _, _, device = init_distributed()
     if args.synthetic_weights:
@@ -235,7 +248,7 @@ def main(argv=None):
     with open(results_file, 'wb') as f:
         pickle.dump(results, f, protocol=2)
     logging.info('%d images, results written to %s', len(dataset), results_file)
-    return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals),
+    return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances),
             'results_file': results_file, 'times': times}
 
 
