@@ -848,6 +848,33 @@ int upsnet_cs_inst_image(void *stream, const uint16_t *gt_ids, int height, int w
                          uint16_t *gt_t, const double *thresholds, int num_thr, int *counts, void *workspace, float *rec_score,
                          unsigned char *rec_cls, unsigned char *rec_code, int64_t *state);
 
+/* ============================== COCO panoptic format: write and read back panoptic predictions ============================== */
+
+/* _converter_2ch_single_core (upsnet/dataset/base_dataset.py:463-511, without vis_panoptic) for one image, on the device:
+ *   pred_2ch uint8 [H,W,3] (channel 0 category, 255 = VOID; channel 1 instance); a segment is a key = ch0 << 8 | ch1 with ch0 != 255;
+ *   cat_table int [256]: -1 for a category that is not in the dataset's table, else R | G << 8 | B << 16 | isthing << 24;
+ *   rgb uint8 [H,W,3] (out): the segment's colour, id = R + 256 G + 65536 B; VOID pixels (0,0,0);
+ *   table int [upsnet_pan_format_table_ints()] (out): [0] = number of segments n, [1] = error (0 none, 1 = a segment's category is
+ *     not in cat_table, 2 = no free colour left around a category's base), [2] = the category of the error (the lowest for error 1),
+ *     [3..7] = 0, then n rows of 8 ints in ascending key (np.unique's order): key, area, x_min, y_min, x_max, y_max, id, ordinal of
+ *     the segment within its category. Rows past n are not written. The colour rule is documented in csrc/pan_format.hip and
+ *     DESIGN.md section 4.11; the same map and table give the same bytes on every run (integer atomics only).
+ * workspace: upsnet_pan_format_workspace_bytes() bytes, 4-byte aligned, ZEROED ONCE before its first use; every call leaves it
+ * zeroed again except for its colour table. H * W < 2^31. Three launches on `stream`, no host synchronisation. */
+size_t upsnet_pan_format_workspace_bytes(void);
+size_t upsnet_pan_format_table_ints(void);
+int upsnet_pan_format(void *stream, const unsigned char *pred_2ch, int height, int width, const int *cat_table, void *workspace,
+                      unsigned char *rgb, int *table);
+
+/* Panoptic PNG -> 2-channel map: rgb uint8 [H,W,3] (id = R + 256 G + 65536 B); table int [num_segments][3] = (id, category, instance
+ * slot 0..255), SORTED BY ID, ids unique in 1..2^24-1 (the caller validates; the kernels stay in bounds regardless);
+ * out_2ch uint8 [H,W,3] = (category, slot, 0), id 0 and ids missing from the table -> (255, 0, 0); counts int [num_segments], zeroed by
+ * the caller: pixels per table row (added). status uint64 [2], zeroed once by the caller, kept across images: [0] = 2^62 -
+ * ((image_index + 1) << 24 | id) for the smallest non-zero id of the earliest image that is in the PNG and not in the table, [1] =
+ * the same for a table row without a pixel; 0 = none. num_segments in 0..65280 (up to 4096 the table is searched in LDS). */
+int upsnet_pan_relabel(void *stream, const unsigned char *rgb, int height, int width, const int *table, int num_segments,
+                       int image_index, unsigned char *out_2ch, int *counts, uint64_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,17 @@ def parse_args(description='', argv=None):
     parser.add_argument('--eval_instances', action='store_true',
                         help='Cityscapes only: also score the instance masks with the Cityscapes instance-level AP / AP50% '
                         '(the gtFine instanceIds maps are read)')
+    parser.add_argument('--write_panoptic', action='store_true',
+                        help='write the panoptic predictions in COCO panoptic format: results/pans_unified/{pan_2ch,pan,pred.json,gt.json} '
+                        '(and results/pans_combined/... with --pan_combined); also for image sets without ground truth')
+    parser.add_argument('--panoptic_categories', type=str, default='',
+                        help='with --write_panoptic on an image set without ground truth: a panoptic JSON whose categories (ids, isthing, '
+                        'color) to use')
+    parser.add_argument('--score_panoptic', type=str, default='', metavar='PRED_JSON',
+                        help='score an existing COCO-panoptic prediction (pred.json and its PNG folder) against the panoptic ground '
+                        'truth of --cfg; no model is built')
+    parser.add_argument('--score_panoptic_folder', type=str, default='',
+                        help='the PNG folder of --score_panoptic (default: the directory beside the JSON named like it without .json)')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)

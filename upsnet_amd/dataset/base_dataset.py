@@ -139,8 +139,8 @@ class BaseDataset(object):
     def evaluate_panoptic(self, pred_pans_2ch, output_dir, max_gt_segments=4096):
         """PQ / SQ / RQ of the 2-channel predictions (get_unified_pan_result's list, at GT resolution) against the panoptic GT,
         computed on the device (dataset/pq.py: semantics, summation order and deviations). Returns the reference's dict
-        {'All', 'Things', 'Stuff', 'per_class'} and logs its tables. Unlike the reference nothing is written to output_dir (the pred
-        PNG / JSON dumps only recolour the segments; PQ does not depend on them)."""
+        {'All', 'Things', 'Stuff', 'per_class'} and logs its tables. Scoring writes nothing to output_dir (the reference's pred PNG /
+        JSON dumps only recolour the segments; PQ does not depend on them): write_panoptic(pred_pans_2ch, output_dir) writes them."""
         from .pq import PanopticEvaluator
         images, annotations, categories = self.load_panoptic_gt()
         if len(pred_pans_2ch) != len(annotations):
@@ -148,6 +148,66 @@ class BaseDataset(object):
         ev = PanopticEvaluator(categories, max_gt_segments=max_gt_segments)
         for pred, gt, ann in zip(pred_pans_2ch, images, annotations):
             ev.add(pred, gt, ann['segments_info'])
+        return ev.summary()
+
+    def write_panoptic(self, pred_pans_2ch, output_dir, categories=None, categories_json=None):
+        """The files of the reference's evaluate_panoptic (:321-327): output_dir/pan_2ch/*.png, pan/*.png, pred.json and -- with ground
+        truth -- gt.json (dataset/pan_format.write_panoptic: colours, naming, deviations). With ground truth the predictions are
+        those of evaluate_panoptic (one per annotation of self.panoptic_json_file, in its order); names come from the JSON's
+        'images', image ids from its annotations, categories from its 'categories'. A set without ground truth (has_gt false) takes
+        names and ids from the image list, and its categories from `categories` (a table as PanopticEvaluator takes it) or from the
+        'categories' of the panoptic JSON `categories_json`; ValueError if neither is given. Returns the annotations written."""
+        from .pan_format import write_panoptic
+        if getattr(self, 'has_gt', True):
+            with open(self.panoptic_json_file, 'r') as f:
+                gt_json = json.load(f)
+            images, annotations = gt_json['images'], gt_json['annotations']
+            if len(images) != len(annotations):
+                raise ValueError("%s lists %d images and %d annotations" % (self.panoptic_json_file, len(images), len(annotations)))
+            if categories is None and categories_json is None:
+                categories = gt_json['categories']
+            image_ids = [a['image_id'] for a in annotations]
+        else:
+            gt_json = None
+            images = [{'id': e['id'], 'file_name': e['file_name']} for e in self.roidb]
+            image_ids = None
+        if categories is None:
+            if categories_json is None:
+                raise ValueError("%s has no ground truth and so no category table: pass categories= or the path of a panoptic JSON "
+                                 "whose 'categories' to use (categories_json=)" % getattr(self, 'name', type(self).__name__))
+            with open(categories_json, 'r') as f:
+                categories = json.load(f)['categories']
+        os.makedirs(output_dir, exist_ok=True)
+        annotations = write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=image_ids)
+        if gt_json is not None:
+            with open(os.path.join(output_dir, 'gt.json'), 'w') as f:
+                json.dump(gt_json, f)
+        logger.info('%d panoptic predictions written to %s', len(annotations), os.path.abspath(output_dir))
+        return annotations
+
+    def evaluate_panoptic_files(self, pred_json, pred_folder, max_gt_segments=4096):
+        """PQ / SQ / RQ of a prediction in COCO panoptic format (pred_json with its PNG folder: write_panoptic's output, or any other
+        tool's) against the panoptic GT, through PanopticEvaluator.add_png. Annotations are paired with the GT by image_id;
+        ValueError if an image of the GT has no prediction, or a prediction no GT image, or an image id occurs twice."""
+        from .pq import PanopticEvaluator
+        with open(pred_json, 'r') as f:
+            pred_anns = json.load(f)['annotations']
+        images, annotations, categories = self.load_panoptic_gt()
+        preds = {}
+        for a in pred_anns:
+            if a['image_id'] in preds:
+                raise ValueError("%s: image_id %s occurs twice" % (pred_json, a['image_id']))
+            preds[a['image_id']] = a
+        gt_ids = [a['image_id'] for a in annotations]
+        missing = [i for i in gt_ids if i not in preds]
+        surplus = sorted(set(preds) - set(gt_ids), key=str)
+        if missing or surplus:
+            raise ValueError("%s does not cover the ground truth: %d GT images without a prediction (first: %s), %d predictions without "
+                             "a GT image (first: %s)" % (pred_json, len(missing), missing[:3], len(surplus), surplus[:3]))
+        ev = PanopticEvaluator(categories, max_gt_segments=max_gt_segments)
+        for gt, ann in zip(images, annotations):
+            pred = preds[ann['image_id']]
+            ev.add_png(load_panoptic_png(os.path.join(pred_folder, pred['file_name'])), pred['segments_info'], gt, ann['segments_info'])
         return ev.summary()
 
     # ---------------------------------------------------------------------------------------------- COCO box / mask AP

@@ -9,7 +9,8 @@ bit-identical to it. Deliberate deviations:
     synchronisation (pq_stat / summary), naming the image and the category. The reference's own error path raises NameError
     (`gt_ann` is undefined there);
   * the prediction must already be at GT resolution: resizing for im_scale != 1 stays with the caller;
-  * no pred PNG / JSON is produced: the reference's IdGenerator colours only relabel the pred segments and PQ does not depend on them.
+  * scoring produces no pred PNG / JSON (the reference's IdGenerator colours only relabel the pred segments and PQ does not depend on
+    them); dataset/pan_format.write_panoptic writes them, and add_png scores such files -- or any COCO-panoptic prediction -- again.
 """
 import logging
 
@@ -42,12 +43,12 @@ def segments_array(segments_info, max_gt_segments):
     return segs
 
 
-def _check_image(name, t, shape=None):
+def _check_image(name, t, shape=None, other='pred_2ch'):
     if t.dtype not in (np.uint8, torch.uint8) or len(t.shape) != 3 or t.shape[2] != 3:
         raise ValueError("%s must be uint8 [H,W,3], got %s %s" % (name, tuple(t.shape), t.dtype))
     if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError("%s %s and pred_2ch %s differ in shape (resize the prediction to GT resolution first)"
-                         % (name, tuple(t.shape), tuple(shape)))
+        raise ValueError("%s %s and %s %s differ in shape (resize the prediction to GT resolution first)"
+                         % (name, tuple(t.shape), other, tuple(shape)))
 
 
 class PanopticEvaluator(object):
@@ -80,7 +81,8 @@ class PanopticEvaluator(object):
             self._state = dict(known=torch.from_numpy(known).to(dev), ws=ops.pq_workspace(self.max_gt_segments, dev),
                                tp=torch.zeros(256, dtype=torch.int64, device=dev), fp=torch.zeros(256, dtype=torch.int64, device=dev),
                                fn=torch.zeros(256, dtype=torch.int64, device=dev), iou=torch.zeros(256, dtype=torch.float64, device=dev),
-                               status=torch.zeros(1, dtype=torch.int64, device=dev))
+                               status=torch.zeros(1, dtype=torch.int64, device=dev),
+                               png_status=torch.zeros(2, dtype=torch.int64, device=dev))
         return self._state
 
     def _upload(self, t):
@@ -104,6 +106,30 @@ class PanopticEvaluator(object):
                           st['fn'], st['iou'], st['status'])
         self.num_images += 1
 
+    def add_png(self, pred_rgb, pred_segments_info, gt_rgb, gt_segments_info):
+        """One image of a prediction in COCO panoptic format: pred_rgb uint8 [H,W,3] PNG of arbitrary ids (id = R + 256 G + 65536 B,
+        0 = VOID) with the JSON's pred_segments_info (id, category_id; its area is ignored, the reference overwrites it with the pixel
+        count). The PNG is relabelled to a 2-channel map on the device (csrc/pan_format.hip; instance slots per category in ascending
+        pred id, the order in which the reference adds several matches of one GT segment), then scored exactly like add().
+        ValueError before any launch: an id 0, outside 1..2^24-1 or used twice, a category outside 0..254, more than 256 segments of
+        one category, a shape mismatch. KeyError at the first synchronisation, naming the image index and the id: a segment that is
+        in the PNG and not in the JSON, or in the JSON without a pixel in the PNG (the reference's sanity checks, :531-542)."""
+        from .pan_format import relabel, segments_table
+        _check_image('pred_rgb', pred_rgb)
+        _check_image('gt_rgb', gt_rgb, pred_rgb.shape, 'pred_rgb')
+        table = segments_table(pred_segments_info)
+        segs = segments_array(gt_segments_info, self.max_gt_segments)
+        st = self._dev_state()
+        pred_rgb, gt_rgb = self._upload(pred_rgb), self._upload(gt_rgb)
+        pred_2ch, _ = relabel(pred_rgb, table, self.num_images, st['png_status'])
+        segs = torch.from_numpy(segs)
+        if torch.cuda.is_available():
+            segs = segs.pin_memory()
+        segs = segs.to(self.device, non_blocking=True)
+        ops.pq_accumulate(pred_2ch, gt_rgb, segs, st['known'], self.num_images, self.max_gt_segments, st['ws'], st['tp'], st['fp'],
+                          st['fn'], st['iou'], st['status'])
+        self.num_images += 1
+
     def __iadd__(self, other):
         if other._state is None:
             self.num_images += other.num_images
@@ -114,22 +140,34 @@ class PanopticEvaluator(object):
         # the first error stays first: other's image indices follow this evaluator's
         shifted = torch.where(ot['status'] != 0, ot['status'] + (self.num_images << 8), ot['status'])
         st['status'].copy_(torch.where(st['status'] != 0, st['status'], shifted))
+        # (add_png's words hold 2^62 - ((index + 1) << 24 | id): the earliest image is the maximum)
+        shifted = torch.where(ot['png_status'] != 0, ot['png_status'] - (self.num_images << 24), ot['png_status'])
+        st['png_status'].copy_(torch.maximum(st['png_status'], shifted))
         self.num_images += other.num_images
         return self
 
     def pq_stat(self):
-        """Synchronise once; return a host PQStat of everything added. KeyError if a pred category was not in `categories`."""
+        """Synchronise once; return a host PQStat of everything added. KeyError if a pred category was not in `categories`, or if an
+        image added with add_png failed one of the PNG / JSON sanity checks (the earliest image's error)."""
         from .base_dataset import PQStat
         stat = PQStat()
         if self._state is None:
             return stat
         st = self._state
-        host = torch.cat([st['tp'], st['fp'], st['fn'], st['iou'].view(torch.int64), st['status']]).cpu().numpy()
+        host = torch.cat([st['tp'], st['fp'], st['fn'], st['iou'].view(torch.int64), st['status'], st['png_status']]).cpu().numpy()
         tp, fp, fn = host[0:256], host[256:512], host[512:768]
         iou, status = host[768:1024].view(np.float64), int(host[1024])
+        errors = []   # (image index, the reference's order of checks, message)
+        for k, text in ((0, 'presented in PNG and not presented in JSON'), (1, 'presented in JSON and not presented in PNG')):
+            if int(host[1025 + k]):
+                v = (1 << 62) - int(host[1025 + k])
+                errors.append(((v >> 24) - 1, 2 * k, 'In the image with index {} (in the order added) segment with ID {} is {}.'.format(
+                    (v >> 24) - 1, v & 0xffffff, text)))
         if status:
-            raise KeyError('In the image with index {} (in the order added) a segment has unknown category_id {}.'.format(
-                (status >> 8) - 1, status & 255))
+            errors.append(((status >> 8) - 1, 1, 'In the image with index {} (in the order added) a segment has unknown category_id {}.'.format(
+                (status >> 8) - 1, status & 255)))
+        if errors:
+            raise KeyError(min(errors)[2])
         for c in np.nonzero(tp + fp + fn)[0]:
             cat = stat[int(c)]
             cat.tp, cat.fp, cat.fn, cat.iou = int(tp[c]), int(fp[c]), int(fn[c]), float(iou[c])

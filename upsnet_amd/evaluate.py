@@ -2,7 +2,8 @@
 (upsnet/upsnet_end2end_test.py:155-314).
 
     python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
-                                  [--eval_proposals] [--eval_instances]
+                                  [--eval_proposals] [--eval_instances] [--write_panoptic [--panoptic_categories <json>]]
+    python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>]
 
 The dataset is `config.dataset.dataset` (Cityscapes or coco) on `config.dataset.test_image_set`. Every image and every GT file the
 configured heads need is checked before the first launch. Images are decoded by a bounded host thread pool ahead of the device;
@@ -15,7 +16,11 @@ path, keys and nesting (numpy objects only); evaluation follows the reference's 
 heuristic merge of the detections and the semantic map) next to the unified result. `--eval_proposals` keeps the RPN proposals
 of every image (results['all_proposals'], original image scale) and scores their recall (metrics['proposal_ar']).
 `--eval_instances` (Cityscapes with a mask head) also scores the instance masks with the Cityscapes instance-level AP against the
-gtFine instanceIds maps (metrics['instance_ap'], dataset/cityscapes_eval.py). One rank only (WORLD_SIZE > 1 is refused)."""
+gtFine instanceIds maps (metrics['instance_ap'], dataset/cityscapes_eval.py). `--write_panoptic` writes the panoptic predictions in
+COCO panoptic format under the reference's paths, results/pans_unified/{pan_2ch,pan,pred.json,gt.json} (and results/pans_combined/...
+with --pan_combined), also for an image set without ground truth (categories then from --panoptic_categories). `--score_panoptic`
+scores such a prediction, or any other tool's, against the panoptic ground truth without building the model
+(metrics['panoptic']). One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
 import pickle
@@ -147,15 +152,38 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
     return results, times
 
 
-def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False):
+def panoptic_predictions(dataset, results, combined, order=None):
+    """The 2-channel maps of the results, unified (the panoptic head's) or combined (the heuristic merge), one per entry of `order`
+    (positions in the image list; default: the image list's own order)."""
+    order = list(range(len(dataset))) if order is None else order
+    if not combined:
+        return dataset.get_unified_pan_result([results['all_ssegs'][k] for k in order], [results['all_panos'][k] for k in order],
+                                              [results['all_pano_cls_inds'][k] for k in order],
+                                              stuff_area_limit=config.test.panoptic_stuff_area_limit)
+
+    def ordered(per_class):
+        return [[v[k] for k in order] if c else v for c, v in enumerate(per_class)]
+    return dataset.get_combined_pan_result([results['all_ssegs'][k] for k in order], ordered(results['all_boxes']),
+                                           ordered(results['all_masks']), stuff_area_limit=config.test.panoptic_stuff_area_limit)
+
+
+def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False, write_panoptic=False,
+                     panoptic_categories=None):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
     'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
-    results['all_proposals']) with eval_proposals and 'instance_ap' (Cityscapes instance-level AP summary) with eval_instances."""
+    results['all_proposals']) with eval_proposals and 'instance_ap' (Cityscapes instance-level AP summary) with eval_instances.
+    write_panoptic: every panoptic result that is scored (or, without ground truth, would be) is also written in COCO panoptic format
+    to results_dir/pans_unified or pans_combined (BaseDataset.write_panoptic)."""
     net = config.network
     metrics = {}
     if not dataset.has_gt:
         logger.info('%s has no annotations (%s): evaluation skipped', dataset.name, os.path.basename(dataset.instances_json_file))
+        if write_panoptic:
+            for combined in ([False] if net.has_panoptic_head else []) + ([True] if pan_combined else []):
+                dataset.write_panoptic(panoptic_predictions(dataset, results, combined),
+                                       os.path.join(results_dir, 'pans_combined' if combined else 'pans_unified'),
+                                       categories_json=panoptic_categories)
         return metrics
     os.makedirs(results_dir, exist_ok=True)
     if net.has_rcnn:
@@ -164,19 +192,16 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
         metrics['mask_ap'] = dataset.evaluate_masks(results['all_boxes'], results['all_masks'], results_dir).stats
     if net.has_panoptic_head:
         logger.info('unified pano result:')
-        order = dataset.panoptic_order()
-        pans = dataset.get_unified_pan_result([results['all_ssegs'][k] for k in order], [results['all_panos'][k] for k in order],
-                                              [results['all_pano_cls_inds'][k] for k in order],
-                                              stuff_area_limit=config.test.panoptic_stuff_area_limit)
+        pans = panoptic_predictions(dataset, results, False, dataset.panoptic_order())
         metrics['panoptic'] = dataset.evaluate_panoptic(pans, os.path.join(results_dir, 'pans_unified'))
+        if write_panoptic:
+            dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_unified'))
     if pan_combined:
         logger.info('combined pano result:')
-        order = dataset.panoptic_order()
-        def ordered(per_class):
-            return [[v[k] for k in order] if c else v for c, v in enumerate(per_class)]
-        pans = dataset.get_combined_pan_result([results['all_ssegs'][k] for k in order], ordered(results['all_boxes']),
-                                               ordered(results['all_masks']), stuff_area_limit=config.test.panoptic_stuff_area_limit)
+        pans = panoptic_predictions(dataset, results, True, dataset.panoptic_order())
         metrics['panoptic_combined'] = dataset.evaluate_panoptic(pans, os.path.join(results_dir, 'pans_combined'))
+        if write_panoptic:
+            dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_combined'))
     if net.has_fcn_head:
         metrics['sseg'] = dataset.evaluate_ssegs(results['all_ssegs'], os.path.join(results_dir, 'ssegs'))
     if eval_proposals:
@@ -211,7 +236,26 @@ def main(argv=None):
         raise SystemExit('--eval_instances scores instance masks against the Cityscapes gtFine instanceIds maps: it needs '
                          'dataset.dataset = Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
                          % (config.dataset.dataset, net.has_rcnn, net.has_mask_head))
+    if args.write_panoptic and not (net.has_panoptic_head or args.pan_combined):
+        raise SystemExit('--write_panoptic writes the panoptic predictions: it needs network.has_panoptic_head, or --pan_combined '
+                         '(has_panoptic_head=%s)' % net.has_panoptic_head)
+    if args.score_panoptic_folder and not args.score_panoptic:
+        raise SystemExit('--score_panoptic_folder names the PNG folder of --score_panoptic <pred.json>, which is missing')
     out_dir = final_output_path(args.cfg)
+    if args.score_panoptic:
+        if not os.path.isfile(args.score_panoptic):
+            raise SystemExit('--score_panoptic: no prediction JSON at %s' % args.score_panoptic)
+        folder = args.score_panoptic_folder or os.path.splitext(args.score_panoptic)[0]
+        if not os.path.isdir(folder):
+            raise SystemExit('--score_panoptic: no PNG folder at %s (name it with --score_panoptic_folder)' % folder)
+        dataset = build_dataset(out_dir)
+        if not dataset.has_gt:
+            raise SystemExit('--score_panoptic: %s has no ground truth to score against' % dataset.name)
+        for p in (dataset.panoptic_json_file,):
+            if not os.path.isfile(p):
+                raise SystemExit('--score_panoptic: no panoptic ground truth at %s' % p)
+        logger.info('panoptic result of %s:', args.score_panoptic)
+        return {'metrics': {'panoptic': dataset.evaluate_panoptic_files(args.score_panoptic, folder)}, 'results_file': None, 'times': None}
     results_dir = os.path.join(out_dir, 'results')
     results_file = os.path.join(results_dir, 'results_list.pkl')
     if args.eval_only:
@@ -226,7 +270,8 @@ def main(argv=None):
         dataset.check_files(images=False)
         if args.eval_instances:
             dataset.check_instance_files()
-        return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances),
+        return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
+                                             args.write_panoptic, args.panoptic_categories or None),
                 'results_file': results_file, 'times': None}
 
     dataset = build_dataset(out_dir)
@@ -248,7 +293,8 @@ def main(argv=None):
     with open(results_file, 'wb') as f:
         pickle.dump(results, f, protocol=2)
     logging.info('%d images, results written to %s', len(dataset), results_file)
-    return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances),
+    return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
+                                             args.write_panoptic, args.panoptic_categories or None),
             'results_file': results_file, 'times': times}
 
 
