@@ -848,6 +848,27 @@ int upsnet_cs_inst_image(void *stream, const uint16_t *gt_ids, int height, int w
                          uint16_t *gt_t, const double *thresholds, int num_thr, int *counts, void *workspace, float *rec_score,
                          unsigned char *rec_cls, unsigned char *rec_code, int64_t *state);
 
+/* ============================== Evaluation: Cityscapes pixel-level IoU / iIoU ============================== */
+
+/* The per-image part of the Cityscapes devkit's evalPixelLevelSemanticLabeling (the rules are restated in
+ * dataset/cityscapes_pixel_eval.py and DESIGN 4.12), csrc/cs_pixel_eval.hip. All on `stream`, no host synchronisation, no allocation.
+ *   gt_labels uint8 [height][width]: the gtFine_labelIds map; gt_ids uint16 [height][width]: the gtFine_instanceIds map, or NULL
+ *   (confusion matrix only: inst, wsum and avg_class_size are then unused and may be NULL); pred uint8 [height][width];
+ *   lut uint8 [256] on the device: label id of every prediction value, anything above 33 = "not a label". height * width <= 2^30.
+ *   avg_class_size: 8 positive doubles on the HOST (person rider car truck bus train motorcycle bicycle).
+ * Outputs on the device:
+ *   conf int64 [34][34], running sums the caller zeroes once: conf[gt label][pred label], every pixel counted;
+ *   inst int [upsnet_cs_pixel_inst_ints()] = [8][1000][3] (zeroed here): for the instance of raw value 1000 * label + k > 1000 of
+ *     class c: pixels | pixels with pred == label | pixels whose pred is an evaluated label of the label's category;
+ *   wsum double [10][4], running sums the caller zeroes once: rows = the 8 classes, human, vehicle; columns = tp | tpWeighted | fn |
+ *     fnWeighted, each instance added in ascending raw value with weight avg_class_size / pixels (float64, the devkit's order);
+ *   bad int [2], zeroed by the caller: pixels whose prediction is not a label (added to [0]) or whose ground-truth label is above 33
+ *     ([1]); such pixels enter no other count. */
+size_t upsnet_cs_pixel_inst_ints(void);
+int upsnet_cs_pixel_image(void *stream, const unsigned char *gt_labels, const uint16_t *gt_ids, const unsigned char *pred,
+                          const unsigned char *lut, int height, int width, const double *avg_class_size, int64_t *conf, int *inst,
+                          double *wsum, int *bad);
+
 /* ============================== COCO panoptic format: write and read back panoptic predictions ============================== */
 
 /* _converter_2ch_single_core (upsnet/dataset/base_dataset.py:463-511, without vis_panoptic) for one image, on the device:

@@ -142,6 +142,8 @@ _SIGNATURES = {
     "upsnet_cs_inst_workspace_bytes": (c_size_t, [c_int]),
     "upsnet_cs_inst_state_words": (c_int, []),
     "upsnet_cs_inst_image": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, c_int, P, P, c_int, P, P, P, P, P, P]),
+    "upsnet_cs_pixel_inst_ints": (c_size_t, []),
+    "upsnet_cs_pixel_image": (c_int, [P, P, P, P, P, c_int, c_int, P, P, P, P, P]),
     "upsnet_pan_format_workspace_bytes": (c_size_t, []),
     "upsnet_pan_format_table_ints": (c_size_t, []),
     "upsnet_pan_format": (c_int, [P, P, c_int, c_int, P, P, P, P]),

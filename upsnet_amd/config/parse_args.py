@@ -25,6 +25,18 @@ def parse_args(description='', argv=None):
     parser.add_argument('--eval_instances', action='store_true',
                         help='Cityscapes only: also score the instance masks with the Cityscapes instance-level AP / AP50% '
                         '(the gtFine instanceIds maps are read)')
+    parser.add_argument('--eval_pixels', action='store_true',
+                        help='Cityscapes only: also score the semantic predictions with the Cityscapes pixel-level IoU / iIoU per class '
+                        'and category (the gtFine labelIds and instanceIds maps are read)')
+    parser.add_argument('--write_ssegs', action='store_true',
+                        help='Cityscapes only: write the semantic predictions as PNGs to results/ssegs (palette PNGs of train ids, as the '
+                        'reference does); also for image sets without ground truth')
+    parser.add_argument('--ssegs_label_ids', action='store_true',
+                        help='with --write_ssegs: grey 8-bit PNGs of label ids in results/ssegs_label_ids instead (the format the '
+                        'benchmark server takes)')
+    parser.add_argument('--score_ssegs', type=str, default='', metavar='FOLDER',
+                        help='Cityscapes only: score a folder of semantic prediction PNGs (<base>.png; palette = train ids, grey = label '
+                        'ids) with the pixel-level IoU / iIoU against the ground truth of --cfg; no model is built')
     parser.add_argument('--write_panoptic', action='store_true',
                         help='write the panoptic predictions in COCO panoptic format: results/pans_unified/{pan_2ch,pan,pred.json,gt.json} '
                         '(and results/pans_combined/... with --pan_combined); also for image sets without ground truth')

@@ -3,7 +3,9 @@
 
     python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
                                   [--eval_proposals] [--eval_instances] [--write_panoptic [--panoptic_categories <json>]]
+                                  [--eval_pixels] [--write_ssegs [--ssegs_label_ids]]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>]
+    python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
 
 The dataset is `config.dataset.dataset` (Cityscapes or coco) on `config.dataset.test_image_set`. Every image and every GT file the
 configured heads need is checked before the first launch. Images are decoded by a bounded host thread pool ahead of the device;
@@ -20,7 +22,12 @@ gtFine instanceIds maps (metrics['instance_ap'], dataset/cityscapes_eval.py). `-
 COCO panoptic format under the reference's paths, results/pans_unified/{pan_2ch,pan,pred.json,gt.json} (and results/pans_combined/...
 with --pan_combined), also for an image set without ground truth (categories then from --panoptic_categories). `--score_panoptic`
 scores such a prediction, or any other tool's, against the panoptic ground truth without building the model
-(metrics['panoptic']). One rank only (WORLD_SIZE > 1 is refused)."""
+(metrics['panoptic']). `--eval_pixels` (Cityscapes with a semantic head) also scores the semantic predictions with the Cityscapes
+pixel-level IoU / iIoU per class and category against the gtFine labelIds and instanceIds maps (metrics['pixel_iou'],
+dataset/cityscapes_pixel_eval.py). `--write_ssegs` writes the semantic predictions as the reference does, palette PNGs of train ids
+under results/ssegs, or with `--ssegs_label_ids` grey PNGs of label ids under results/ssegs_label_ids (what the benchmark server
+takes), also for an image set without ground truth; `--score_ssegs <folder>` scores such a folder, or another tool's, without
+building the model (metrics['pixel_iou']). One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
 import pickle
@@ -167,16 +174,24 @@ def panoptic_predictions(dataset, results, combined, order=None):
                                            ordered(results['all_masks']), stuff_area_limit=config.test.panoptic_stuff_area_limit)
 
 
+def ssegs_folder(results_dir, label_ids):
+    return os.path.join(results_dir, 'ssegs_label_ids' if label_ids else 'ssegs')
+
+
 def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False, write_panoptic=False,
-                     panoptic_categories=None):
+                     panoptic_categories=None, eval_pixels=False, write_ssegs=False, ssegs_label_ids=False):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
     'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
     results['all_proposals']) with eval_proposals and 'instance_ap' (Cityscapes instance-level AP summary) with eval_instances.
     write_panoptic: every panoptic result that is scored (or, without ground truth, would be) is also written in COCO panoptic format
-    to results_dir/pans_unified or pans_combined (BaseDataset.write_panoptic)."""
+    to results_dir/pans_unified or pans_combined (BaseDataset.write_panoptic). eval_pixels adds 'pixel_iou' (Cityscapes pixel-level
+    IoU / iIoU); write_ssegs writes the semantic predictions to results_dir/ssegs (palette PNGs of train ids) or, with
+    ssegs_label_ids, to results_dir/ssegs_label_ids (grey PNGs of label ids), with or without ground truth."""
     net = config.network
     metrics = {}
+    if write_ssegs:
+        dataset.write_segmentation_result(results['all_ssegs'], ssegs_folder(results_dir, ssegs_label_ids), label_ids=ssegs_label_ids)
     if not dataset.has_gt:
         logger.info('%s has no annotations (%s): evaluation skipped', dataset.name, os.path.basename(dataset.instances_json_file))
         if write_panoptic:
@@ -211,7 +226,21 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
     if eval_instances:
         logger.info('instance-level result:')
         metrics['instance_ap'] = dataset.evaluate_instances(results['all_boxes'], results['all_masks'], results_dir)
+    if eval_pixels:
+        logger.info('pixel-level result:')
+        metrics['pixel_iou'] = dataset.evaluate_pixels(results['all_ssegs'], results_dir)
     return metrics
+
+
+def check_pixel_run(dataset, args):
+    """--eval_pixels before anything runs: refused on an image set without ground truth (writing still works there), and the
+    label-id and instance-id maps join the upfront file check."""
+    if not args.eval_pixels:
+        return
+    if not dataset.has_gt:
+        raise SystemExit('--eval_pixels: %s has no ground truth to score against (--write_ssegs [--ssegs_label_ids] writes its '
+                         'predictions)' % dataset.name)
+    dataset.check_pixel_files()
 
 
 def main(argv=None):
@@ -236,6 +265,15 @@ def main(argv=None):
         raise SystemExit('--eval_instances scores instance masks against the Cityscapes gtFine instanceIds maps: it needs '
                          'dataset.dataset = Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
                          % (config.dataset.dataset, net.has_rcnn, net.has_mask_head))
+    if args.score_ssegs and config.dataset.dataset != 'Cityscapes':     # (no model is built: the heads do not matter)
+        raise SystemExit('--score_ssegs scores semantic PNGs against the Cityscapes gtFine maps: it needs dataset.dataset = Cityscapes '
+                         '(dataset=%s)' % config.dataset.dataset)
+    for flag in ('eval_pixels', 'write_ssegs'):
+        if getattr(args, flag) and not (config.dataset.dataset == 'Cityscapes' and net.has_fcn_head):
+            raise SystemExit('--%s works on the semantic predictions of a Cityscapes run (label ids, gtFine maps): it needs dataset.dataset '
+                             '= Cityscapes and network.has_fcn_head (dataset=%s, has_fcn_head=%s)' % (flag, config.dataset.dataset, net.has_fcn_head))
+    if args.ssegs_label_ids and not args.write_ssegs:
+        raise SystemExit('--ssegs_label_ids chooses the format of --write_ssegs, which is missing')
     if args.write_panoptic and not (net.has_panoptic_head or args.pan_combined):
         raise SystemExit('--write_panoptic writes the panoptic predictions: it needs network.has_panoptic_head, or --pan_combined '
                          '(has_panoptic_head=%s)' % net.has_panoptic_head)
@@ -256,6 +294,15 @@ def main(argv=None):
                 raise SystemExit('--score_panoptic: no panoptic ground truth at %s' % p)
         logger.info('panoptic result of %s:', args.score_panoptic)
         return {'metrics': {'panoptic': dataset.evaluate_panoptic_files(args.score_panoptic, folder)}, 'results_file': None, 'times': None}
+    if args.score_ssegs:
+        if not os.path.isdir(args.score_ssegs):
+            raise SystemExit('--score_ssegs: no folder at %s' % args.score_ssegs)
+        dataset = build_dataset(out_dir)
+        if not dataset.has_gt:
+            raise SystemExit('--score_ssegs: %s has no ground truth to score against' % dataset.name)
+        dataset.check_pixel_files()
+        logger.info('pixel-level result of %s:', args.score_ssegs)
+        return {'metrics': {'pixel_iou': dataset.evaluate_pixels_files(args.score_ssegs)}, 'results_file': None, 'times': None}
     results_dir = os.path.join(out_dir, 'results')
     results_file = os.path.join(results_dir, 'results_list.pkl')
     if args.eval_only:
@@ -270,14 +317,17 @@ def main(argv=None):
         dataset.check_files(images=False)
         if args.eval_instances:
             dataset.check_instance_files()
+        check_pixel_run(dataset, args)
         return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
-                                             args.write_panoptic, args.panoptic_categories or None),
+                                             args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
+                                             args.ssegs_label_ids),
                 'results_file': results_file, 'times': None}
 
     dataset = build_dataset(out_dir)
     dataset.check_files()       # every image and GT file, before the first launch
     if args.eval_instances:
         dataset.check_instance_files()
+    check_pixel_run(dataset, args)
     from .upsnet_end2end_test import init_distributed, load_checkpoint_model
     _, _, device = init_distributed()
     if args.synthetic_weights:
@@ -294,7 +344,8 @@ def main(argv=None):
         pickle.dump(results, f, protocol=2)
     logging.info('%d images, results written to %s', len(dataset), results_file)
     return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
-                                             args.write_panoptic, args.panoptic_categories or None),
+                                             args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
+                                             args.ssegs_label_ids),
             'results_file': results_file, 'times': times}
 
 
