@@ -896,6 +896,31 @@ int upsnet_pan_format(void *stream, const unsigned char *pred_2ch, int height, i
 int upsnet_pan_relabel(void *stream, const unsigned char *rgb, int height, int width, const int *table, int num_segments,
                        int image_index, unsigned char *out_2ch, int *counts, uint64_t *status);
 
+/* ============================== Detection visualisations (config.test.vis_mask) ============================== */
+
+/* One image of the reference's vis_all_mask (upsnet/dataset/base_dataset.py:826-896) by the integer drawing rule of DESIGN.md section
+ * 4.13 (restated in the header of csrc/vis_render.hip): box ring, mask fill and contour per detection in order, then the labels.
+ *   image uint8 [height][width][3] RGB; out the same shape (every byte written, each once; must not overlap image);
+ *   the num_dets detections in drawing order: boxes float [n][4] (x1 y1 x2 y2), colours uint8 [n][3] (RGB of the mask fill), labels
+ *   uint8 [n][upsnet_vis_max_label()] of which the first label_len[n] bytes are drawn; masks as the evaluators pass them: trans int
+ *   [num_trans], the ascending column-major change positions x * height + y of all masks one after the other, trans_off int [n + 1]
+ *   the first position of each list (trans_off[n] = num_trans). Lists that are not ascending or leave the image draw a wrong picture;
+ *   the kernels stay inside their arrays regardless.
+ * Limits (error code, nothing clamped): sides 1..32768, height * width <= 2^28, num_dets 0..upsnet_vis_max_detections() (256), a
+ * label_len above upsnet_vis_max_label() (32) is the caller's to refuse (the kernel reads no further than 32 bytes).
+ * workspace: upsnet_vis_workspace_bytes(num_dets, height, width) bytes (0 for sizes beyond the limits), 4-byte aligned; NO zeroing is
+ * asked of the caller and nothing is kept between calls. Four launches on `stream`, no host synchronisation, no allocation, no atomics
+ * on the canvas: the same input gives the same bytes on every run.
+ * upsnet_vis_font: the 95 cells (characters 32..126) of the label font into cells uint8 [95][8] on the HOST: one byte per cell row,
+ * bit 4 = the leftmost of 5 dots, the eighth row empty. */
+int upsnet_vis_max_detections(void);
+int upsnet_vis_max_label(void);
+size_t upsnet_vis_workspace_bytes(int num_dets, int height, int width);
+int upsnet_vis_font(unsigned char *cells);
+int upsnet_vis_render(void *stream, const unsigned char *image, int height, int width, int num_dets, const float *boxes,
+                      const unsigned char *colours, const unsigned char *labels, const int *label_len, const int *trans,
+                      const int *trans_off, int num_trans, void *workspace, unsigned char *out);
+
 #ifdef __cplusplus
 }
 #endif

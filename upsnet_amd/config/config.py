@@ -83,6 +83,7 @@ config.test.panoptic_stuff_area_limit = 4096
 config.test.batch_size = 1
 config.test.scales = [1024]
 config.test.max_size = 2048
+config.test.vis_mask = False          # upsnet_end2end_test.py:172-173, 300-301: draw the detections instead of scoring them
 
 
 def _merge(dst, src):

@@ -3,7 +3,7 @@ global config before anything else is parsed; `--eval_only`, `--weight_path` as 
 implementation (synthetic workload, steps) are accepted too, so that one parser serves both spellings of the entry point."""
 import argparse
 
-from .config import update_config
+from .config import config, update_config
 
 
 def parse_args(description='', argv=None):
@@ -48,9 +48,14 @@ def parse_args(description='', argv=None):
                         'truth of --cfg; no model is built')
     parser.add_argument('--score_panoptic_folder', type=str, default='',
                         help='the PNG folder of --score_panoptic (default: the directory beside the JSON named like it without .json)')
+    parser.add_argument('--vis_mask', action='store_true',
+                        help='sets config.test.vis_mask: draw the detections of score >= 0.5 over every image into results/vis (one PNG '
+                        'per image); in a run instead of the evaluation, with --eval_only before it, as the reference does')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)
+    if args.vis_mask:
+        config.test.vis_mask = True
     if rest:    # (the reference re-parses strictly, parse_args.py:32; an option neither parser knows is reported, not swallowed)
         parser.error('unrecognized arguments: %s' % ' '.join(rest))
     return args

@@ -347,6 +347,17 @@ class BaseDataset(object):
                 f.write(line + '\n')
         return metrics
 
+    # ---------------------------------------------------------------------------------------------- detection visualisations
+    def vis_all_mask(self, all_boxes, all_masks, save_path=None):
+        """The reference's vis_all_mask (:826-896): every image of the list with its detections of score >= 0.5 drawn over it (box
+        outline, name.score label, half-transparent mask with a white contour), one PNG per image named <image basename>.png (so
+        x.jpg.png) under save_path; save_path None returns the rendered uint8 [H, W, 3] arrays instead. Drawn on the device by the
+        integer rule of dataset/vis.py. The k-th kept detection of the run has the colour vis.coco_colour(k), this
+        project's own sequence (the reference cycles Detectron's list). Returns the written paths."""
+        from . import vis
+        return vis.vis_all_mask(self, all_boxes, all_masks, self.dataset.classes, lambda j, k: vis.coco_colour(k),
+                                lambda entry: '{}.png'.format(entry['image'].split('/')[-1]), save_path)
+
     def evaluate_all(self, all_boxes, all_segms, output_dir):
         all_results = self.evaluate_boxes(all_boxes, output_dir)
         self.evaluate_masks(all_boxes, all_segms, output_dir)

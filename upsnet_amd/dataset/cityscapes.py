@@ -205,6 +205,19 @@ class Cityscapes(TestDataset):
             ev.add(labels, ids, pred, train_ids=train_ids, name=path)
         return self._report_pixels(ev, output_dir)
 
+    # ---------------------------------------------------------------------------------------------- detection visualisations
+    def vis_all_mask(self, all_boxes, all_masks, save_path=None):
+        """The reference's override (cityscapes.py:236-345): as BaseDataset.vis_all_mask with the eight instance classes by name and
+        every mask in its class's colour (train ids 11..18 of the palette); PNGs named <base>.png for the image <base>_leftImg8bit.png
+        (the basename minus its last 16 characters)."""
+        from . import vis
+        from .cityscapes_eval import CLASS_NAMES
+        from .cityscapes_pixel_eval import TRAIN_ID_COLOURS
+        first_thing = len(TRAIN_ID_COLOURS) - len(CLASS_NAMES)
+        return vis.vis_all_mask(self, all_boxes, all_masks, ('__background__',) + tuple(CLASS_NAMES),
+                                lambda j, k: TRAIN_ID_COLOURS[first_thing + j - 1],
+                                lambda entry: '{}.png'.format(entry['image'].split('/')[-1][:-16]), save_path)
+
     def evaluate_instances(self, all_boxes, all_segms, output_dir):
         """Cityscapes instance-level AP (the devkit's evalInstanceLevelSemanticLabeling, which the reference's
         Cityscapes.evaluate_masks calls, cityscapes.py:347-397) of all_segms[class][image] (im_post's RLE dicts) scored by

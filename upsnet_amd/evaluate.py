@@ -3,7 +3,7 @@
 
     python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
                                   [--eval_proposals] [--eval_instances] [--write_panoptic [--panoptic_categories <json>]]
-                                  [--eval_pixels] [--write_ssegs [--ssegs_label_ids]]
+                                  [--eval_pixels] [--write_ssegs [--ssegs_label_ids]] [--vis_mask]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
 
@@ -27,7 +27,10 @@ pixel-level IoU / iIoU per class and category against the gtFine labelIds and in
 dataset/cityscapes_pixel_eval.py). `--write_ssegs` writes the semantic predictions as the reference does, palette PNGs of train ids
 under results/ssegs, or with `--ssegs_label_ids` grey PNGs of label ids under results/ssegs_label_ids (what the benchmark server
 takes), also for an image set without ground truth; `--score_ssegs <folder>` scores such a folder, or another tool's, without
-building the model (metrics['pixel_iou']). One rank only (WORLD_SIZE > 1 is refused)."""
+building the model (metrics['pixel_iou']). `--vis_mask` (or `test.vis_mask: true` in the yaml; needs a mask head) draws the detections
+of score >= 0.5 over every image into results/vis, one PNG per image (BaseDataset.vis_all_mask, dataset/vis.py), with the reference's
+control flow: a run writes the pickle, draws and skips the evaluation (upsnet_end2end_test.py:300-301); with `--eval_only` the drawing
+comes first and the evaluation follows (:172-173), and the images must be on disk. One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
 import pickle
@@ -243,8 +246,14 @@ def check_pixel_run(dataset, args):
     dataset.check_pixel_files()
 
 
+def draw_results(dataset, results, results_dir):
+    """config.test.vis_mask: test_dataset.vis_all_mask(all_boxes, all_masks, <results>/vis); returns the written paths."""
+    return dataset.vis_all_mask(results['all_boxes'], results['all_masks'], os.path.join(results_dir, 'vis'))
+
+
 def main(argv=None):
-    """Returns {'metrics': ..., 'results_file': path, 'times': per-image timings (None with --eval_only)}."""
+    """Returns {'metrics': ..., 'results_file': path, 'times': per-image timings (None with --eval_only)}, and with config.test.vis_mask
+    also 'vis_files': the PNGs written under results/vis."""
     from .config.parse_args import parse_args
     args = parse_args('UPSNet: run and score a checkpoint over an evaluation set', argv)
     logging.basicConfig(level=logging.INFO, format='%(asctime)-15s | %(message)s')
@@ -265,6 +274,10 @@ def main(argv=None):
         raise SystemExit('--eval_instances scores instance masks against the Cityscapes gtFine instanceIds maps: it needs '
                          'dataset.dataset = Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
                          % (config.dataset.dataset, net.has_rcnn, net.has_mask_head))
+    vis_mask = bool(config.test.get('vis_mask', False))
+    if vis_mask and not (net.has_rcnn and net.has_mask_head):
+        raise SystemExit('--vis_mask (config.test.vis_mask) draws the detections and their instance masks: it needs network.has_rcnn and '
+                         'has_mask_head (has_rcnn=%s, has_mask_head=%s)' % (net.has_rcnn, net.has_mask_head))
     if args.score_ssegs and config.dataset.dataset != 'Cityscapes':     # (no model is built: the heads do not matter)
         raise SystemExit('--score_ssegs scores semantic PNGs against the Cityscapes gtFine maps: it needs dataset.dataset = Cityscapes '
                          '(dataset=%s)' % config.dataset.dataset)
@@ -314,10 +327,16 @@ def main(argv=None):
             raise SystemExit('--eval_only --eval_proposals: %s holds no proposals (all_proposals); run with --eval_proposals without '
                              '--eval_only first' % results_file)
         dataset = build_dataset(out_dir)
-        dataset.check_files(images=False)
+        dataset.check_files(images=vis_mask)
         if args.eval_instances:
             dataset.check_instance_files()
         check_pixel_run(dataset, args)
+        if vis_mask:        # (upsnet_end2end_test.py:172-173: drawn first, then evaluated)
+            vis_files = draw_results(dataset, results, results_dir)
+            return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
+                                                 args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
+                                                 args.ssegs_label_ids),
+                    'results_file': results_file, 'times': None, 'vis_files': vis_files}
         return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
                                              args.ssegs_label_ids),
@@ -343,6 +362,9 @@ def main(argv=None):
     with open(results_file, 'wb') as f:
         pickle.dump(results, f, protocol=2)
     logging.info('%d images, results written to %s', len(dataset), results_file)
+    if vis_mask:            # (upsnet_end2end_test.py:300-301, an if / else: drawn instead of evaluated)
+        del model
+        return {'metrics': {}, 'results_file': results_file, 'times': times, 'vis_files': draw_results(dataset, results, results_dir)}
     return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
                                              args.ssegs_label_ids),
