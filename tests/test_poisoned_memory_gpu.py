@@ -225,6 +225,11 @@ CASES = [
     _c('panoptic_fuse_up_nchw', _OPS, 'test_panoptic_fuse_with_fused_upsample_bitexact', ('ops.panoptic_fuse_up', 'ops.panoptic_fuse'),
        m=60, S=19, C=9, Hs=64, Ws=128, nhwc=False),
     _c('panoptic_tail_pack', _OPS, 'test_panoptic_tail_pack_and_keep_zero_fill', ('ops.panoptic_tail_pack', 'ops.mask_removal')),
+    _c('panoptic_crowd_dropped', 'test_panoptic_structured_gpu', 'test_mask_removal_structured', ('ops.mask_removal',), name='crowd-dropped'),
+    _c('panoptic_1024_one_class', 'test_panoptic_structured_gpu', 'test_mask_removal_structured', ('ops.mask_removal',),
+       name='many-1024-True'),
+    _c('panoptic_odd_width_101', 'test_panoptic_structured_gpu', 'test_panoptic_fuse_structured',
+       ('ops.panoptic_fuse', 'ops.mask_paste', 'ops.seg_term', 'ops.panoptic_argmax', 'ops.mask_removal'), name='odd_width-101', void=True),
     _c('panoptic_golden', 'test_golden_gpu', 'test_panoptic_head_golden', ('ops.panoptic_fuse', 'ops.panoptic_argmax')),
     _c('unified_pan_odd', 'test_postprocess_gpu', 'test_unified_pan_vs_oracle', ('ops.unified_pan_result',), H=33, W=47, k=3, limit=50, seed=2),
     _c('unified_pan_no_inst', 'test_postprocess_gpu', 'test_unified_pan_vs_oracle', ('ops.unified_pan_result',), H=64, W=64, k=0,
