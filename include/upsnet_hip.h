@@ -896,6 +896,34 @@ int upsnet_pan_format(void *stream, const unsigned char *pred_2ch, int height, i
 int upsnet_pan_relabel(void *stream, const unsigned char *rgb, int height, int width, const int *table, int num_segments,
                        int image_index, unsigned char *out_2ch, int *counts, uint64_t *status);
 
+/* ============================== Evaluation ground truth from the raw Cityscapes download ============================== */
+
+/* One gtFine_instanceIds map -> the labelTrainIds map, the panoptic PNG content with its segment table, and the run-length
+ * transitions of every instance mask (csrc/gt_prepare.hip; the rules are restated in dataset/prepare.py and DESIGN 4.14).
+ *   ids int [height][width]: raw value v in 0..255 (label v) or 1000..65535 (label v / 1000, at most 65); label_ids uint8
+ *   [height][width] or NULL: the gtFine_labelIds map, only cross-checked; train_id, has_instances, thing_row: int [256] each on the device, indexed by label:
+ *   train id (255 = ignored in evaluation), hasInstances (0 / 1), row 0..7 of a thing class or -1 (only for labels that are not ignored).
+ * Outputs on the device:
+ *   train_map uint8 [height][width]: the label's train id; rgb uint8 [height][width][3]: (v % 256, v / 256 % 256, v / 65536), and
+ *     (0,0,0) where the label is ignored; every byte of both is written;
+ *   table int [seg_capacity][9]: the distinct v whose label is not ignored, ascending: v, label, train id, iscrowd (v < 1000 and the
+ *     label has instances), area, x_min, y_min, x_max, y_max; rows past the count are not written;
+ *   instances = the segments with v >= 1000 and a thing row, ascending v; trans_off int [seg_capacity + 1]: [0 .. instances] are
+ *     written; trans int [trans_capacity]: for instance j, trans[trans_off[j] .. trans_off[j + 1]) are the ascending column-major
+ *     positions x * height + y at which (ids == v) changes (0 before the first pixel): the lists dataset/rle.py turns into RLE counts;
+ *   status int [8] (zeroed here): [0] segments, [1] instances, [2] transitions (the true counts, also beyond the capacities),
+ *     [3] flags: 1 = more segments than seg_capacity (no instance list is made, [2] = 0), 2 = more transitions than trans_capacity
+ *     (trans is not written), 4 = a value that encodes no label (negative, 256..999 or beyond 65535: treated as ignored, no table
+ *     is indexed with it, the outputs are not to be used); [4] pixels of label_ids that differ from the label of ids (a value
+ *     without a label differs); [5..7] = 0. Nothing is written out of bounds in either case, and the next call on the workspace is unaffected.
+ * workspace: upsnet_gt_prepare_workspace_bytes(seg_capacity) bytes (0 for a capacity outside 1..65536), 4-byte aligned, ZEROED ONCE
+ * before its first use; every call leaves it as it needs it. height, width <= 32768, height * width < 2^30. Six launches on `stream`,
+ * integer atomics only: the same input gives the same bytes on every run. No host synchronisation, no allocation. */
+size_t upsnet_gt_prepare_workspace_bytes(int seg_capacity);
+int upsnet_gt_prepare(void *stream, const int *ids, const unsigned char *label_ids, int height, int width, const int *train_id,
+                      const int *has_instances, const int *thing_row, int seg_capacity, int trans_capacity, void *workspace,
+                      unsigned char *train_map, unsigned char *rgb, int *table, int *trans_off, int *trans, int *status);
+
 /* ============================== Detection visualisations (config.test.vis_mask) ============================== */
 
 /* One image of the reference's vis_all_mask (upsnet/dataset/base_dataset.py:826-896) by the integer drawing rule of DESIGN.md section

@@ -148,6 +148,8 @@ _SIGNATURES = {
     "upsnet_pan_format_table_ints": (c_size_t, []),
     "upsnet_pan_format": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "upsnet_pan_relabel": (c_int, [P, P, c_int, c_int, P, c_int, c_int, P, P, P]),
+    "upsnet_gt_prepare_workspace_bytes": (c_size_t, [c_int]),
+    "upsnet_gt_prepare": (c_int, [P, P, P, c_int, c_int, P, P, P, c_int, c_int, P, P, P, P, P, P, P]),
     "upsnet_vis_max_detections": (c_int, []),
     "upsnet_vis_max_label": (c_int, []),
     "upsnet_vis_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -1778,3 +1778,31 @@ def proposal_recall(problems, proposals, gt_boxes, max_gt, total_proposals, work
     check(lib().upsnet_proposal_recall(stream(), n, ptr(problems), ptr(proposals), ptr(gt_boxes), int(max_gt), int(total_proposals),
                                        ptr(workspace), ptr(out)), "proposal_recall")
     return out
+
+
+# ----------------------------------------------------------------------------- evaluation ground truth from the raw downloads
+def gt_prepare_workspace(device, seg_capacity=4096):
+    """dataset/gt_prepare.py: the zeroed workspace of gt_prepare / gt_prepare_launch."""
+    from .dataset import gt_prepare as impl
+    return impl.gt_prepare_workspace(device, seg_capacity)
+
+
+def gt_prepare_launch(ids, tables, label_ids=None, seg_capacity=4096, trans_capacity=None, workspace=None):
+    """dataset/gt_prepare.py: one Cityscapes instanceIds map -> train-id map, panoptic RGB, segment table, run lists and status words
+    on the device (csrc/gt_prepare.hip), without synchronising."""
+    from .dataset import gt_prepare as impl
+    return impl.gt_prepare_launch(ids, tables, label_ids, seg_capacity, trans_capacity, workspace)
+
+
+def gt_prepare(ids, tables, label_ids=None, seg_capacity=4096, trans_capacity=None, workspace=None):
+    """dataset/gt_prepare.py: gt_prepare_launch, synchronised, cut to its counts; ValueError for an overflow, a value beyond 16 bits
+    or a labelIds map that disagrees."""
+    from .dataset import gt_prepare as impl
+    return impl.gt_prepare(ids, tables, label_ids, seg_capacity, trans_capacity, workspace)
+
+
+def panoptic_semantic(rgb, segments_info):
+    """dataset/gt_prepare.py: COCO panoptic PNG content -> semantic map of category ids (255: id 0 and ids without a segment),
+    channel 0 of csrc/pan_format.hip's relabel kernel."""
+    from .dataset import gt_prepare as impl
+    return impl.panoptic_semantic(rgb, segments_info)
