@@ -7,7 +7,9 @@ landscape. A COCO evaluation set (upsnet_amd/evaluate.py) is dozens of padded si
 
 Pass one (cheap): one eager forward per size of the population with hipconv.TRACE on; every record becomes a key
 (kind, Cin, Cout, kernel, stride, relu, residual, residual_up, form) -- the form string carries tile form and split factor. No launch may leave the
-hand-written path at any size.
+hand-written path at any size. (The sweep object takes a convolution precision: tests/test_size_sweep_lowprec_gpu.py walks the same
+population in the bf16 and bf16x3 modes, where a key also carries the dtypes of a launch and a one-launch bottleneck has a key of its own;
+the key of an fp32 record is the nine fields above.)
 Pass two: sizes are picked by greedy set cover until every key of pass one is covered (plus the three most extreme portrait sizes and the size
 with the smallest stride-32 map), and at each of them every launch is replayed in float64 from its recorded inputs exactly as
 tests/test_layerwise_gpu.py does (its _replay, its bound |err| <= 1e-4 + 1e-4 |ref|). A launch is skipped only if the same module geometry,
@@ -32,6 +34,10 @@ WEIGHT_SEED = 235
 
 # the sizes tests/test_layerwise_gpu.py and tests/test_trunk_gpu.py run each preset at (fp32 mode)
 _OLD_SIZES = {'CITYSCAPES_R50': [(256, 512), (1024, 2048)], 'COCO_R101_DCN': [(200, 333), (800, 1333), (1024, 2048)]}
+# ... and the sizes the reduced-precision tests of tests/test_layerwise_gpu.py replay each preset at
+_OLD_SIZES_BY_PRECISION = {'fp32': _OLD_SIZES,
+                           'bf16': {'CITYSCAPES_R50': [(256, 512), (1024, 2048)], 'COCO_R101_DCN': [(800, 1333)]},
+                           'bf16x3': {'CITYSCAPES_R50': [(1024, 2048)], 'COCO_R101_DCN': []}}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -57,22 +63,48 @@ def _forced(preset, sizes):
     return portrait[:3] + [smallest]
 
 
+_DTYPE_NAMES = {torch.float32: 'f32', torch.bfloat16: 'bf16', torch.float16: 'f16', torch.float64: 'f64'}
+
+
+def _dtypes(rec):
+    """() for a launch that reads and writes fp32 only (every launch of the fp32 and bf16x3 modes); else (('dtypes', inputs, residual,
+    outputs),): a bf16-in / fp32-out launch is another kernel instantiation than a bf16-in / bf16-out one."""
+    name = lambda t: _DTYPE_NAMES.get(t.dtype, str(t.dtype))
+    ins = tuple(name(x) for x in (rec['xs'] if 'xs' in rec else [rec['x']]))
+    outs = tuple(name(y) for y in (rec['outs'] if 'outs' in rec else [rec['out']]))
+    res = None if rec.get('residual') is None else name(rec['residual'])
+    if all(d == 'f32' for d in ins + outs) and res in (None, 'f32'):
+        return ()
+    return (('dtypes', ins, res, outs),)
+
+
 def _key(rec):
+    """(kind, Cin, Cout, kernel, stride, relu, residual, residual_up, form) -- followed, for the launches the reduced-precision modes add, by
+    what tells them apart: the geometry of a one-launch bottleneck (kind 'block': no single conv module) and the dtypes of a launch that
+    does not read and write fp32 only. The key of an fp32 record is the nine fields alone."""
     m = rec['module']
+    if rec['kind'] == 'block':     # relu(conv3(relu(conv2(relu(conv1(x))))) + shortcut(x)) as one launch: m is the bottleneck
+        c1, c2, c3 = m.conv1, m.conv2, m.conv3
+        return (('block', c1.in_channels, c3.out_channels, tuple(c2.kernel_size), tuple(c1.stride), True, True, False, rec['form']) +
+                (('block', c1.out_channels, tuple(c1.kernel_size), tuple(c2.stride), tuple(c2.padding), m.downsample is not None),) + _dtypes(rec))
     return (rec['kind'], m.in_channels, m.out_channels, tuple(m.kernel_size), tuple(m.stride), bool(rec.get('relu', False)),
-            rec.get('residual') is not None, bool(rec.get('residual_up', False)), rec['form'])
+            rec.get('residual') is not None, bool(rec.get('residual_up', False)), rec['form']) + _dtypes(rec)
 
 
 def _signature(rec):
-    """What a launch is, apart from its values: module geometry, input shape(s), flags, form."""
+    """What a launch is, apart from its values: module geometry, input shape(s) and dtypes, flags, form."""
     m = rec['module']
     xs = rec['xs'] if 'xs' in rec else [rec['x']]
+    if rec['kind'] == 'block':     # (its key holds the geometry of conv1 / conv2 / the projection)
+        return _key(rec) + (tuple(tuple(x.shape) for x in xs),)
     return _key(rec) + (tuple(m.padding), tuple(m.dilation), int(getattr(m, 'groups', 1)), tuple(tuple(x.shape) for x in xs))
 
 
 def _fmt_key(k):
-    return "%s %d->%d k%s s%s%s%s [%s]" % (k[0], k[1], k[2], k[3], k[4], ' relu' if k[5] else '',
-                                           ' + up(residual)' if k[7] else (' + residual' if k[6] else ''), k[8])
+    dt = next((e for e in k[9:] if e[0] == 'dtypes'), None)
+    return "%s %d->%d k%s s%s%s%s [%s]%s" % (k[0], k[1], k[2], k[3], k[4], ' relu' if k[5] else '',
+                                             ' + up(residual)' if k[7] else (' + residual' if k[6] else ''), k[8],
+                                             '' if dt is None else ' %s%s -> %s' % ('+'.join(dt[1]), '' if dt[2] is None else ' (+ %s)' % dt[2], '+'.join(dt[3])))
 
 
 def greedy_cover(keys_by_size, forced=()):
@@ -89,17 +121,20 @@ def greedy_cover(keys_by_size, forced=()):
 
 
 class _Sweep(object):
-    """One model object of a preset (seeded weights) and what pass one saw on it. Built once per preset and process."""
+    """One model object of a preset (seeded weights) in one convolution precision and what pass one saw on it. Built once per
+    (preset, precision) and process."""
     _cache = {}
 
-    def __init__(self, preset):
-        self.preset, self.model, self.keys_by_size, self.old_keys, self.resized, self.done = preset, None, None, None, {}, set()
+    def __init__(self, preset, precision='fp32'):
+        self.preset, self.precision = preset, precision
+        self.model, self.keys_by_size, self.old_keys, self.resized, self.done = None, None, None, {}, set()
+        self.forms_by_size = {}      # padded size -> {(layer name, kind, form)}: which kernel each layer of the model ran on there
 
     @classmethod
-    def get(cls, preset):
-        if preset not in cls._cache:
-            cls._cache[preset] = cls(preset)
-        return cls._cache[preset]
+    def get(cls, preset, precision='fp32'):
+        if (preset, precision) not in cls._cache:
+            cls._cache[(preset, precision)] = cls(preset, precision)
+        return cls._cache[(preset, precision)]
 
     def configure(self):
         from upsnet_amd.config import config as cfgmod
@@ -111,21 +146,24 @@ class _Sweep(object):
         update_config_dict(CITYSCAPES_R50)
 
     def trace(self, h, w, seed):
-        """One eager forward of an h x w image with hipconv.TRACE on -> (records, output). Call between configure() and restore()."""
+        """One eager forward of an h x w image in this sweep's precision with hipconv.TRACE on -> (records, output). Call between
+        configure() and restore(). The session's precision (fp32) is put back whatever happens."""
         from upsnet_amd.models import hipconv
         from upsnet_amd.synthetic import build_model, make_image
-        assert hipconv.PRECISION == 'fp32', hipconv.PRECISION
+        assert hipconv.PRECISION == 'fp32', hipconv.PRECISION      # nothing before this call leaked a reduced precision
         if self.model is None:
             self.model = build_model(seed=WEIGHT_SEED)
         data = make_image(h, w, seed=seed, device='cuda')
         hipconv.TRACE, n_fallbacks = [], len(hipconv.FALLBACKS)
+        saved, hipconv.PRECISION, ran = hipconv.PRECISION, self.precision, None
         try:
             with torch.no_grad():
                 out = self.model(data)
             torch.cuda.synchronize()
-            trace = hipconv.TRACE
+            trace, ran = hipconv.TRACE, hipconv.PRECISION
         finally:
-            hipconv.TRACE = None
+            hipconv.TRACE, hipconv.PRECISION = None, saved
+        assert ran == self.precision, (ran, self.precision)
         assert len(hipconv.FALLBACKS) == n_fallbacks, ((h, w), hipconv.FALLBACKS[n_fallbacks:])
         assert not any(rec['form'] == 'library' for rec in trace), (h, w)
         return trace, out
@@ -141,9 +179,11 @@ class _Sweep(object):
                 assert trace and tuple(out['panoptic_outputs'].shape[1:]) == padded, (resized, padded, len(trace))
                 keys_by_size[padded] = set(_key(rec) for rec in trace)
                 self.resized[padded] = (resized, i)
+                names = {id(m): n for n, m in self.model.named_modules()}
+                self.forms_by_size[padded] = set((names.get(id(rec['module']), '?'), rec['kind'], rec['form']) for rec in trace)
                 del trace, out
             old = set()
-            for j, (h, w) in enumerate(_OLD_SIZES[self.preset]):
+            for j, (h, w) in enumerate(_OLD_SIZES_BY_PRECISION[self.precision][self.preset]):
                 trace, _ = self.trace(h, w, seed=100 + j)
                 old |= set(_key(rec) for rec in trace)
                 del trace
@@ -156,10 +196,10 @@ class _Sweep(object):
         return greedy_cover(self.keys_by_size, _forced(self.preset, _population(self.preset)))
 
 
-def _old_keys_of_both_presets():
+def _old_keys_of_both_presets(precision='fp32'):
     old = set()
     for preset in sorted(_OLD_SIZES):
-        sweep = _Sweep.get(preset)
+        sweep = _Sweep.get(preset, precision)
         sweep.pass_one()
         old |= sweep.old_keys
     return old
