@@ -949,6 +949,37 @@ int upsnet_vis_render(void *stream, const unsigned char *image, int height, int 
                       const unsigned char *colours, const unsigned char *labels, const int *label_len, const int *trans,
                       const int *trans_off, int num_trans, void *workspace, unsigned char *out);
 
+/* ============================== GroupNorm heads (with_norm = 'group_norm') ============================== */
+
+/* nn.GroupNorm(32, C) with a fused epilogue (csrc/group_norm.hip):
+ *   out = relu?( (x - mean_g) * rstd_g * gamma_c + beta_c  [+ residual | + nearest x2 upsampled residual] ),  rstd = 1 / sqrt(var + eps),
+ * mean / biased variance per (sample, group) over C / 32 channels x height x width pixels.
+ * Preconditions of all forms: x, out (and residual) fp32, NHWC-dense (channels-last), 16-byte aligned; gamma, beta fp32 [C], 16-byte
+ * aligned, read in place; C % 128 == 0 and C <= 1024 (a lane owns 4 channels of one group; every head width of the model: 128, 256,
+ * 1024) -- any other C is an error code, nothing runs. eps >= 0. Empty maps (batch, height or width 0) are skipped.
+ * Sums are fp64 from the first add, combined in an order fixed by the shape of one sample: the value of a sample does not depend on
+ * the batch size, on the other maps of the launch or on the run (no atomics); var is never formed as E[x^2] - mean^2 in fp32.
+ *
+ * upsnet_group_norm_nhwc_f32: 1..5 maps x[i] [batch[i], height[i], width[i], C] sharing gamma / beta, two launches (partials per chunk
+ * of upsnet_group_norm_chunk_pixels() pixels into `workspace`, then recombine + apply); bit-identical to one call per map.
+ *   residual: NULL, or one pointer per map (entries may be NULL) together with res_height / res_width, the residual's own size:
+ *   [batch, height, width, C] (residual_up = 0) or [batch, height / 2, width / 2, C] with even height, width (residual_up = 1: read
+ *   through a nearest x2 upsampling); any other size is an error.
+ *   out[i] may alias x[i] or a same-size residual[i], not an upsampled one; nothing may alias the workspace.
+ *   workspace: upsnet_group_norm_workspace_bytes(nseg, batch, height, width) bytes (0 for invalid arguments), 16-byte aligned,
+ *   caller-allocated, no zeroing needed, nothing kept between calls.
+ * upsnet_group_norm_small_nhwc_f32: samples of height * width <= upsnet_group_norm_chunk_pixels() pixels (ROI maps; fc6 rows as
+ * height = width = 1), one launch, one workgroup (rows: half a wave) per sample, no workspace, no residual; out may alias x. For
+ * height * width > 1 bit-identical to upsnet_group_norm_nhwc_f32 on the same sample. */
+int upsnet_group_norm_chunk_pixels(void);
+size_t upsnet_group_norm_workspace_bytes(int nseg, const int batch[], const int height[], const int width[]);
+int upsnet_group_norm_nhwc_f32(void *stream, int nseg, const float *const x[], float *const out[], const int batch[],
+                               const int height[], const int width[], int C, const float *gamma, const float *beta, float eps,
+                               int relu, const float *const residual[], const int res_height[], const int res_width[],
+                               int residual_up, void *workspace);
+int upsnet_group_norm_small_nhwc_f32(void *stream, const float *x, float *out, int batch, int height, int width, int C,
+                                     const float *gamma, const float *beta, float eps, int relu);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@ upsampling to P2 size, concat, 1x1 score, bilinear x4.
 
 MI355X note: the subnet's weights are shared by the four levels, so each deformable layer runs as ONE
 fused launch over all levels (csrc/deform_conv.hip) with bias + ReLU in the epilogue and no column
-buffer; only the small 3x3 offset convolutions stay per level.
+buffer; only the small 3x3 offset convolutions stay per level. With with_norm='group_norm' each layer is
+followed by nn.GroupNorm(32, C): the ReLU moves from the convolution's epilogue into the norm's apply pass,
+again one stats and one apply launch for the four levels (csrc/group_norm.hip).
 """
 import torch
 import torch.nn as nn
@@ -20,7 +22,7 @@ class FCNSubNet(nn.Module):
 
     def __init__(self, in_channels, out_channels, num_layers, deformable_group=1, dilation=1, with_norm='none'):
         super(FCNSubNet, self).__init__()
-        assert with_norm == 'none'
+        norm = hipconv.head_norm(with_norm)
         assert num_layers >= 2
         self.num_layers = num_layers
         self.conv = nn.ModuleList()
@@ -31,6 +33,8 @@ class FCNSubNet(nn.Module):
                 in_channels = out_channels
             else:
                 conv.append(DeformConvWithOffset(in_channels, in_channels, kernel_size=3, stride=1, padding=dilation, dilation=dilation))
+            if norm is not None:
+                conv.append(norm(in_channels))
             conv.append(nn.ReLU(inplace=True))
             self.conv.append(nn.Sequential(*conv))
         self.taps = None   # parity tests: set to a dict to record every layer's predicted offsets (tests/test_trunk_gpu.py)
@@ -46,9 +50,16 @@ class FCNSubNet(nn.Module):
                 if m.bias is not None:
                     m.bias.data.fill_(0)
 
+    def _layer(self, i, x):
+        """Layer i on one map. conv -> GroupNorm -> ReLU goes through hipconv.norm: the Sequential's own forward would run the library's
+        GroupNorm."""
+        if len(self.conv[i]) == 3:
+            return hipconv.norm(self.conv[i][1], self.conv[i][0](x), relu=True)
+        return self.conv[i](x)
+
     def forward(self, x):
         for i in range(self.num_layers):
-            x = self.conv[i](x)
+            x = self._layer(i, x)
         return x
 
     def forward_levels(self, feats):
@@ -58,15 +69,16 @@ class FCNSubNet(nn.Module):
             layer = self.conv[i][0]
             dc = layer.conv
             if not ops.fused_dcn_supported(dc.in_channels, dc.out_channels, dc.deformable_groups, dc.groups, dc.padding, dc.stride, dc.dilation):
-                xs = [self.conv[i](x) for x in xs]
+                xs = [self._layer(i, x) for x in xs]
                 continue
+            gn = self.conv[i][1] if len(self.conv[i]) == 3 else None
             offsets = hipconv.conv_multi(layer.conv_offset, xs)
             if self.taps is not None:
                 self.taps.setdefault('offsets', []).append([o.detach().clone() for o in offsets])
             ys = ops.deform_conv_fused(xs, offsets, ops.cached_dcn_pack(dc.weight), dc.bias, dc.in_channels, dc.out_channels,
-                                       dc.kernel_size, dc.stride, dc.padding, dc.dilation, relu=True)
-            hipconv._trace('dcn', module=dc, xs=xs, offsets=offsets, outs=ys, relu=True, form='dcn_fused multi' + (' bf16' if ops.dcn_precision() == 'bf16' else ''))
-            xs = ys
+                                       dc.kernel_size, dc.stride, dc.padding, dc.dilation, relu=gn is None)
+            hipconv._trace('dcn', module=dc, xs=xs, offsets=offsets, outs=ys, relu=gn is None, form='dcn_fused multi' + (' bf16' if ops.dcn_precision() == 'bf16' else ''))
+            xs = ys if gn is None else hipconv.norm_multi(gn, ys, relu=True)
         return xs
 
 

@@ -1,6 +1,7 @@
 """FPN (upsnet/models/fpn.py:25-104): 1x1 laterals, nearest x2 top-down adds, 3x3 outputs,
-P6 = stride-2 subsample of P5, optional GAP branch (COCO configs). with_norm='none' only (every
-shipped config)."""
+P6 = stride-2 subsample of P5, optional GAP branch (COCO configs). with_norm='none' (every shipped
+config) or 'group_norm': every convolution is then bias-free and followed by nn.GroupNorm(32, feature_dim)
+on the kernels of csrc/group_norm.hip, the top-down add fused into the norm's apply pass."""
 import torch.nn as nn
 import torch.nn.functional as F
 
@@ -13,22 +14,29 @@ class FPN(nn.Module):
     def __init__(self, feature_dim, with_extra_level=True, with_bottom_up_path_aggregation=False, with_norm='none',
                  upsample_method='nearest'):
         super(FPN, self).__init__()
-        assert with_norm == 'none', "only fpn_with_norm='none' is used by the reference configs"
         assert upsample_method in ['nearest', 'bilinear']
+        norm = hipconv.head_norm(with_norm)
         self.feature_dim = feature_dim
         self.upsample_method = upsample_method
         if with_extra_level:
             self.fpn_p6 = nn.MaxPool2d(kernel_size=1, stride=2)
         if config.network.fpn_with_gap:
             self.fpn_gap = nn.Linear(2048, feature_dim)
-        self.fpn_p5_1x1 = nn.Conv2d(2048, feature_dim, 1)
-        self.fpn_p4_1x1 = nn.Conv2d(1024, feature_dim, 1)
-        self.fpn_p3_1x1 = nn.Conv2d(512, feature_dim, 1)
-        self.fpn_p2_1x1 = nn.Conv2d(256, feature_dim, 1)
-        self.fpn_p5 = nn.Conv2d(feature_dim, feature_dim, 3, padding=1)
-        self.fpn_p4 = nn.Conv2d(feature_dim, feature_dim, 3, padding=1)
-        self.fpn_p3 = nn.Conv2d(feature_dim, feature_dim, 3, padding=1)
-        self.fpn_p2 = nn.Conv2d(feature_dim, feature_dim, 3, padding=1)
+        self.with_norm = with_norm
+        if norm is not None:
+            for name, cin in (('fpn_p5_1x1', 2048), ('fpn_p4_1x1', 1024), ('fpn_p3_1x1', 512), ('fpn_p2_1x1', 256)):
+                setattr(self, name, nn.Sequential(nn.Conv2d(cin, feature_dim, 1, bias=False), norm(feature_dim)))
+            for name in ('fpn_p5', 'fpn_p4', 'fpn_p3', 'fpn_p2'):
+                setattr(self, name, nn.Sequential(nn.Conv2d(feature_dim, feature_dim, 3, padding=1, bias=False), norm(feature_dim)))
+        else:
+            self.fpn_p5_1x1 = nn.Conv2d(2048, feature_dim, 1)
+            self.fpn_p4_1x1 = nn.Conv2d(1024, feature_dim, 1)
+            self.fpn_p3_1x1 = nn.Conv2d(512, feature_dim, 1)
+            self.fpn_p2_1x1 = nn.Conv2d(256, feature_dim, 1)
+            self.fpn_p5 = nn.Conv2d(feature_dim, feature_dim, 3, padding=1)
+            self.fpn_p4 = nn.Conv2d(feature_dim, feature_dim, 3, padding=1)
+            self.fpn_p3 = nn.Conv2d(feature_dim, feature_dim, 3, padding=1)
+            self.fpn_p2 = nn.Conv2d(feature_dim, feature_dim, 3, padding=1)
         self.initialize()
 
     def initialize(self):
@@ -42,7 +50,28 @@ class FPN(nn.Module):
         return F.interpolate(x, scale_factor=2, mode=self.upsample_method,
                              align_corners=False if self.upsample_method == 'bilinear' else None)
 
+    def _forward_norm(self, res2, res3, res4, res5):
+        """with_norm = 'group_norm': conv (no bias, no residual) -> GroupNorm; the top-down add rides in the norm's apply pass."""
+        cn = lambda seq, x, **kw: hipconv.norm(seq[1], hipconv.conv(seq[0], x), **kw)
+        p5_1x1 = cn(self.fpn_p5_1x1, res5)
+        if hasattr(self, 'fpn_gap'):
+            gap = self.fpn_gap(F.adaptive_avg_pool2d(res5.float(), (1, 1)).flatten(1)).view(-1, self.feature_dim, 1, 1)
+            p5_1x1 = p5_1x1 + gap
+        if self.upsample_method == 'nearest' and all(t.shape[2] % 2 == 0 and t.shape[3] % 2 == 0 for t in (res2, res3, res4)):
+            up = lambda t: dict(residual=t, residual_up=True)
+        else:
+            up = lambda t: dict(residual=self.fpn_upsample(t))
+        p4_plus = cn(self.fpn_p4_1x1, res4, **up(p5_1x1))
+        p3_plus = cn(self.fpn_p3_1x1, res3, **up(p4_plus))
+        p2_plus = cn(self.fpn_p2_1x1, res2, **up(p3_plus))
+        p5, p4, p3, p2 = (cn(seq, x) for seq, x in ((self.fpn_p5, p5_1x1), (self.fpn_p4, p4_plus), (self.fpn_p3, p3_plus), (self.fpn_p2, p2_plus)))
+        if hasattr(self, 'fpn_p6'):
+            return p2, p3, p4, p5, self.fpn_p6(p5)
+        return p2, p3, p4, p5
+
     def forward(self, res2, res3, res4, res5):
+        if self.with_norm != 'none':
+            return self._forward_norm(res2, res3, res4, res5)
         p5_1x1 = hipconv.conv(self.fpn_p5_1x1, res5)
         if hasattr(self, 'fpn_gap'):
             gap = self.fpn_gap(F.adaptive_avg_pool2d(res5.float(), (1, 1)).flatten(1)).view(-1, self.feature_dim, 1, 1)

@@ -10,7 +10,11 @@ convolution (MIOpen) and is recorded in FALLBACKS. CPU tensors always go through
 the same epilogue in torch): that is the host execution used by oracle.forward.forward_cpu and by synthetic.calibrate_statistics,
 never a product path on a GPU box.
 
-TRACE (parity tests): set to a list and every convolution launch appends a record of its module(s), inputs, fused epilogue
+`norm(gn, x, relu=False, residual=None, residual_up=False)` / `norm_multi(gn, xs, relu=False)` do the same for the nn.GroupNorm(32, C)
+layers of heads built with with_norm = 'group_norm' (csrc/group_norm.hip): relu?(gn(x) + residual), same rules for unsupported layers
+and CPU tensors.
+
+TRACE (parity tests): set to a list and every convolution / GroupNorm launch appends a record of its module(s), inputs, fused epilogue
 operands and output -- tests/test_layerwise_gpu.py replays each record in float64 ("per op, on identical inputs").
 """
 import os
@@ -19,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import group_norm, ops
 
 ENABLED = True
 ALLOW_LIBRARY = os.environ.get('UPSNET_ALLOW_LIBRARY_CONV', '0') == '1'
@@ -765,6 +769,61 @@ def dcn(m, x, offset, relu=False):
                                      m.stride, m.padding, m.dilation, relu=relu)[0]
     y = m(x, offset)
     return torch.relu_(y) if relu else y
+
+
+def head_norm(with_norm):
+    """The norm layer factory of a head built with config.network.{fpn,rcnn,fcn}_with_norm = with_norm (upsnet/models/fpn.py:37-48):
+    None for 'none', nn.GroupNorm(32, C) for 'group_norm'."""
+    assert with_norm in ['batch_norm', 'group_norm', 'none']
+    if with_norm == 'batch_norm':
+        raise NotImplementedError(
+            "with_norm='batch_norm': the reference takes this layer from upsnet/operators/modules/distbatchnorm.py (a synchronised "
+            "BatchNorm2d imported only under Horovod + syncbn), which is not part of its tree -- there is no BatchNorm2d to reproduce; "
+            "use 'group_norm' or 'none'")
+    return None if with_norm == 'none' else (lambda num_channels: nn.GroupNorm(32, num_channels))
+
+
+def norm_supported(gn, x):
+    return (ENABLED and isinstance(gn, nn.GroupNorm) and gn.affine and x.is_cuda and x.dim() in (2, 4) and x.shape[1] == gn.num_channels and
+            group_norm.supported(gn.num_channels, gn.num_groups))
+
+
+def _norm_library(gn, x, relu, residual, residual_up):
+    _library(gn, x, 'hipconv.norm_supported() is false')
+    y = gn(x)
+    if residual is not None:
+        y = y + (F.interpolate(residual, scale_factor=2, mode='nearest') if residual_up else residual)
+    return F.relu(y, inplace=True) if relu else y
+
+
+def norm(gn, x, relu=False, residual=None, residual_up=False):
+    """relu?(gn(x) + residual) for an nn.GroupNorm(32, C) on the kernels of csrc/group_norm.hip (gamma / beta read in place, nothing
+    cached). residual_up: `residual` is at half resolution and is added through a nearest x2 upsampling (the FPN top-down add: norm + add
+    in one apply pass, nothing materialised). The form depends on the shape of ONE sample only, never on the batch size (ROI batches):
+    [n, C] rows and samples of at most group_norm.chunk_pixels() pixels without a residual take the one-launch small form, everything
+    else the stats + apply pair. Unsupported layers go the way of an unsupported convolution (_library)."""
+    if norm_supported(gn, x):
+        if x.dim() == 2 or (residual is None and x.shape[2] * x.shape[3] <= group_norm.chunk_pixels()):
+            y = group_norm.group_norm_small(x, gn.weight, gn.bias, gn.eps, relu=relu)
+            form = 'gn rows' if x.dim() == 2 or x.shape[2] * x.shape[3] == 1 else 'gn small'
+        else:
+            y, form = group_norm.group_norm(x, gn.weight, gn.bias, gn.eps, relu=relu, residual=residual, residual_up=residual_up), 'gn'
+    else:
+        y, form = _norm_library(gn, x, relu, residual, residual_up), 'library'
+    _trace('gn', module=gn, x=x, out=y, relu=relu, residual=residual, residual_up=residual_up, form=form)
+    return y
+
+
+def norm_multi(gn, xs, relu=False):
+    """The same GroupNorm applied to several feature maps (FPN levels) in ONE stats launch and ONE apply launch; bit-identical to the
+    stats + apply pair per map."""
+    xs = list(xs)
+    if 1 <= len(xs) <= group_norm.MAX_MAPS and all(x.dim() == 4 and norm_supported(gn, x) for x in xs):
+        ys = group_norm.group_norm_multi(xs, gn.weight, gn.bias, gn.eps, relu=relu)
+        for x, y in zip(xs, ys):
+            _trace('gn', module=gn, x=x, out=y, relu=relu, residual=None, residual_up=False, form='gn multi')
+        return ys
+    return [norm(gn, x, relu=relu) for x in xs]
 
 
 def clear_cache(model=None):

@@ -110,6 +110,9 @@ class resnet_upsnet(resnet_rcnn):
     # ------------------------------------------------------------------ inference preparation
     def prepare_inference(self, channels_last=True, fold_bn=True):
         """eval(), freeze, optionally fold frozen BN and switch activations/weights to channels-last."""
+        if hipconv.PRECISION != 'fp32' and any(isinstance(m, torch.nn.GroupNorm) for m in self.modules()):
+            raise NotImplementedError("heads with with_norm='group_norm' run in fp32 only (csrc/group_norm.hip); UPSNET_CONV_PRECISION=%s "
+                                      "is not supported for them" % hipconv.PRECISION)
         self.eval()
         for p in self.parameters():
             p.requires_grad = False

@@ -1,4 +1,5 @@
-"""RPN head (upsnet/models/rpn.py:26-57): 3x3 conv + ReLU, 1x1 objectness (sigmoid), 1x1 box deltas."""
+"""RPN head (upsnet/models/rpn.py:26-57): 3x3 conv (+ GroupNorm with with_norm='group_norm') + ReLU, 1x1 objectness (sigmoid), 1x1 box
+deltas."""
 import torch
 import torch.nn as nn
 
@@ -8,9 +9,12 @@ from . import hipconv
 class RPN(nn.Module):
     def __init__(self, num_anchors=15, input_dim=256, with_norm='none'):
         super(RPN, self).__init__()
-        assert with_norm == 'none'
+        norm = hipconv.head_norm(with_norm)
         self.num_anchors = num_anchors
-        self.conv_proposal = nn.Sequential(nn.Conv2d(input_dim, input_dim, 3, padding=1), nn.ReLU(inplace=True))
+        if norm is not None:   # (the reference keeps the convolution's bias here: rpn.py:38)
+            self.conv_proposal = nn.Sequential(nn.Conv2d(input_dim, input_dim, 3, padding=1), norm(input_dim), nn.ReLU(inplace=True))
+        else:
+            self.conv_proposal = nn.Sequential(nn.Conv2d(input_dim, input_dim, 3, padding=1), nn.ReLU(inplace=True))
         self.cls_score = nn.Conv2d(input_dim, self.num_anchors, 1)
         self.bbox_pred = nn.Conv2d(input_dim, self.num_anchors * 4, 1)
         self.initialize()
@@ -22,7 +26,10 @@ class RPN(nn.Module):
                 m.bias.data.zero_()
 
     def forward(self, data):
-        x = hipconv.conv(self.conv_proposal[0], data, relu=True)
+        if len(self.conv_proposal) == 3:
+            x = hipconv.norm(self.conv_proposal[1], hipconv.conv(self.conv_proposal[0], data), relu=True)
+        else:
+            x = hipconv.conv(self.conv_proposal[0], data, relu=True)
         cls_score = hipconv.conv(self.cls_score, x)
         bbox_pred = hipconv.conv(self.bbox_pred, x)
         cls_prob = torch.sigmoid(cls_score)
@@ -33,7 +40,10 @@ def rpn_forward_levels(rpn, feats):
     """All pyramid levels through the shared RPN head: 3 launches (3x3 conv; both 1x1 heads together; ONE sigmoid over the flat
     buffer that backs the head outputs of every level) instead of 4 per level. The probabilities are returned as channel slices of
     NHWC maps; the proposal kernels consume them in place (strided)."""
-    xs = hipconv.conv_multi(rpn.conv_proposal[0], feats, relu=True)
+    if len(rpn.conv_proposal) == 3:   # conv -> GroupNorm -> ReLU: one more pair of launches for all levels
+        xs = hipconv.norm_multi(rpn.conv_proposal[1], hipconv.conv_multi(rpn.conv_proposal[0], feats), relu=True)
+    else:
+        xs = hipconv.conv_multi(rpn.conv_proposal[0], feats, relu=True)
     (scores, boxes), flat, outs = hipconv.conv_multi_cat([rpn.cls_score, rpn.bbox_pred], xs, return_flat=True)
     if flat is None:
         return scores, boxes, [torch.sigmoid(s) for s in scores]
