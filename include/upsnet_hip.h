@@ -980,6 +980,21 @@ int upsnet_group_norm_nhwc_f32(void *stream, int nseg, const float *const x[], f
 int upsnet_group_norm_small_nhwc_f32(void *stream, const float *x, float *out, int batch, int height, int width, int C,
                                      const float *gamma, const float *beta, float eps, int relu);
 
+/* ============================== Cityscapes instance predictions in benchmark format ============================== */
+
+/* The mask planes of the Cityscapes instance-level prediction files (dataset/cityscapes_inst_format.py),
+ * csrc/cs_inst_format.hip: run lists in the form upsnet_cs_inst_image takes -- trans int [trans_off[num_masks]], trans_off int
+ * [num_masks + 1], per mask the NON-DECREASING column-major positions x * height + y in [0, H * W) where the mask changes, the first
+ * starting a run of ones; equal positions cancel (a run of no pixels) -- expanded row-major on `stream`, no host synchronisation, no
+ * allocation, no workspace. The lists are device data and are not inspected: the caller has checked them.
+ *   bits = 8: out uint8 [num_masks][height][width], 0 or 255.
+ *   bits = 1: out uint8 [num_masks][height][(width + 7) / 8], the row layout of a PNG of bit depth 1: the leftmost pixel of a byte in
+ *             its most significant bit, the bits past `width` zero.
+ * Every byte of `out` is written (it may be uninitialised), nothing outside it. height * width <= 2^30. num_masks = 0 launches
+ * nothing (all pointers may be NULL). */
+int upsnet_cs_inst_expand(void *stream, const int *trans, const int *trans_off, int num_masks, int height, int width, int bits,
+                          unsigned char *out);
+
 #ifdef __cplusplus
 }
 #endif

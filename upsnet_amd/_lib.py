@@ -159,6 +159,7 @@ _SIGNATURES = {
     "upsnet_group_norm_workspace_bytes": (c_size_t, [c_int, P, P, P]),
     "upsnet_group_norm_nhwc_f32": (c_int, [P, c_int, P, P, P, P, P, c_int, P, P, c_float, c_int, P, P, P, c_int, P]),
     "upsnet_group_norm_small_nhwc_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, c_float, c_int]),
+    "upsnet_cs_inst_expand": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
 }
 
 _lib = None

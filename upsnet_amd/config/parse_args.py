@@ -37,6 +37,15 @@ def parse_args(description='', argv=None):
     parser.add_argument('--score_ssegs', type=str, default='', metavar='FOLDER',
                         help='Cityscapes only: score a folder of semantic prediction PNGs (<base>.png; palette = train ids, grey = label '
                         'ids) with the pixel-level IoU / iIoU against the ground truth of --cfg; no model is built')
+    parser.add_argument('--write_instances', action='store_true',
+                        help='Cityscapes only: write the instance predictions in the benchmark format, results/inst_seg/<image>pred.txt '
+                        'and one mask PNG per detection under results/inst_seg/seg_results (as the reference does); also for image sets '
+                        'without ground truth')
+    parser.add_argument('--instances_1bit', action='store_true',
+                        help='with --write_instances: mask PNGs of bit depth 1 instead of 8-bit grey 0 / 255')
+    parser.add_argument('--score_instances', type=str, default='', metavar='FOLDER',
+                        help='Cityscapes only: score a folder of instance predictions in the benchmark format (one <image key>*.txt per '
+                        'image naming its mask PNGs) with the instance-level AP against the ground truth of --cfg; no model is built')
     parser.add_argument('--write_panoptic', action='store_true',
                         help='write the panoptic predictions in COCO panoptic format: results/pans_unified/{pan_2ch,pan,pred.json,gt.json} '
                         '(and results/pans_combined/... with --pan_combined); also for image sets without ground truth')

@@ -223,7 +223,8 @@ class Cityscapes(TestDataset):
         Cityscapes.evaluate_masks calls, cityscapes.py:347-397) of all_segms[class][image] (im_post's RLE dicts) scored by
         all_boxes[class][image][:, 4], against the gtFine instanceIds maps, on the device (dataset/cityscapes_eval.py). Logs the
         devkit's table, writes it to instance_results.txt and returns {'AP', 'AP50', 'per_class', 'aps'}. Unlike the reference no
-        mask PNGs or pred.txt files are written: they are the devkit's input format, not a result."""
+        mask PNGs or pred.txt files are written here: they are the devkit's input format, not a result (write_instance_result writes
+        them, evaluate_instances_files scores them)."""
         from .cityscapes_eval import InstanceEvaluator, results_lines
         n_cls = len(all_boxes)
         for c in range(1, n_cls):
@@ -241,4 +242,31 @@ class Cityscapes(TestDataset):
         with open(os.path.join(output_dir, 'instance_results.txt'), 'w') as f:
             for line in lines:
                 f.write(line + '\n')
+        return res
+
+    def write_instance_result(self, all_boxes, all_segms, output_dir, one_bit=False):
+        """The files of the reference's evaluate_masks (cityscapes.py:368-395), the benchmark server's instance-level format:
+        <output_dir>/inst_seg/<basename>pred.txt and one mask PNG per detection under inst_seg/seg_results/<basename>/, 8-bit grey
+        0 / 255 or, with one_bit, bit depth 1 (dataset/cityscapes_inst_format.py). Needs no ground truth. Returns the txt paths."""
+        from .cityscapes_inst_format import write_instance_predictions
+        return write_instance_predictions(self, all_boxes, all_segms, output_dir, one_bit=one_bit)
+
+    def evaluate_instances_files(self, folder, output_dir=None):
+        """evaluate_instances over a folder in the benchmark's format (write_instance_result's output or another tool's submission;
+        the devkit's file rules are restated in dataset/cityscapes_inst_format.py): the same table logged, written to
+        <output_dir>/instance_results.txt when output_dir is given, the same dict returned."""
+        from .cityscapes_eval import results_lines
+        from .cityscapes_inst_format import score_instance_files
+        if not self.has_gt:
+            raise ValueError('%s has no ground truth to score against' % self.name)
+        self.check_instance_files()
+        res = score_instance_files(self, folder).summary()
+        lines = results_lines(res)
+        for line in lines:
+            logger.info(line)
+        if output_dir is not None:
+            os.makedirs(output_dir, exist_ok=True)
+            with open(os.path.join(output_dir, 'instance_results.txt'), 'w') as f:
+                for line in lines:
+                    f.write(line + '\n')
         return res

@@ -24,7 +24,8 @@ evaluators does not change a bit of the result.
 
 Deliberate deviations: a prediction of zero area is dropped (the devkit divides by zero); a class with valid GT and predictions of
 which every one is ignored has AP 0.0 (the devkit indexes an empty array); the score is the float32 of the results widened to double
-(the reference prints a float32 into pred.txt and the devkit parses it: order and ties are the same); no mask PNGs or pred.txt files.
+(the reference prints a float32 into pred.txt and the devkit parses it: order and ties are the same); no mask PNGs or pred.txt files
+(dataset/cityscapes_inst_format.py writes and reads them).
 Refused with ValueError before any launch: wrong dtypes or shapes, a mask or RLE whose size differs from the map's, RLE counts that
 do not sum to H * W, a class outside 1..8, more than 65535 predictions in one image. Scores must not be NaN (device data in
 add_masks, not inspected). Nothing has a capacity beyond that: the tables are indexed by (class, raw id) directly.

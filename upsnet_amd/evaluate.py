@@ -4,8 +4,10 @@
     python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
                                   [--eval_proposals] [--eval_instances] [--write_panoptic [--panoptic_categories <json>]]
                                   [--eval_pixels] [--write_ssegs [--ssegs_label_ids]] [--vis_mask]
+                                  [--write_instances [--instances_1bit]]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
+    python -m upsnet_amd.evaluate --cfg <yaml> --score_instances <folder>
 
 The dataset is `config.dataset.dataset` (Cityscapes or coco) on `config.dataset.test_image_set`. Every image and every GT file the
 configured heads need is checked before the first launch. Images are decoded by a bounded host thread pool ahead of the device;
@@ -27,7 +29,10 @@ pixel-level IoU / iIoU per class and category against the gtFine labelIds and in
 dataset/cityscapes_pixel_eval.py). `--write_ssegs` writes the semantic predictions as the reference does, palette PNGs of train ids
 under results/ssegs, or with `--ssegs_label_ids` grey PNGs of label ids under results/ssegs_label_ids (what the benchmark server
 takes), also for an image set without ground truth; `--score_ssegs <folder>` scores such a folder, or another tool's, without
-building the model (metrics['pixel_iou']). `--vis_mask` (or `test.vis_mask: true` in the yaml; needs a mask head) draws the detections
+building the model (metrics['pixel_iou']). `--write_instances` (Cityscapes with a mask head) writes the instance predictions in the
+benchmark's format, results/inst_seg/<image>pred.txt and one mask PNG per detection under results/inst_seg/seg_results (8-bit grey, or
+bit depth 1 with `--instances_1bit`; dataset/cityscapes_inst_format.py), also for an image set without ground truth;
+`--score_instances <folder>` scores such a folder, or another tool's, without building the model (metrics['instance_ap']). `--vis_mask` (or `test.vis_mask: true` in the yaml; needs a mask head) draws the detections
 of score >= 0.5 over every image into results/vis, one PNG per image (BaseDataset.vis_all_mask, dataset/vis.py), with the reference's
 control flow: a run writes the pickle, draws and skips the evaluation (upsnet_end2end_test.py:300-301); with `--eval_only` the drawing
 comes first and the evaluation follows (:172-173), and the images must be on disk. One rank only (WORLD_SIZE > 1 is refused)."""
@@ -182,7 +187,8 @@ def ssegs_folder(results_dir, label_ids):
 
 
 def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False, write_panoptic=False,
-                     panoptic_categories=None, eval_pixels=False, write_ssegs=False, ssegs_label_ids=False):
+                     panoptic_categories=None, eval_pixels=False, write_ssegs=False, ssegs_label_ids=False, write_instances=False,
+                     instances_1bit=False):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
     'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
@@ -190,11 +196,15 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
     write_panoptic: every panoptic result that is scored (or, without ground truth, would be) is also written in COCO panoptic format
     to results_dir/pans_unified or pans_combined (BaseDataset.write_panoptic). eval_pixels adds 'pixel_iou' (Cityscapes pixel-level
     IoU / iIoU); write_ssegs writes the semantic predictions to results_dir/ssegs (palette PNGs of train ids) or, with
-    ssegs_label_ids, to results_dir/ssegs_label_ids (grey PNGs of label ids), with or without ground truth."""
+    ssegs_label_ids, to results_dir/ssegs_label_ids (grey PNGs of label ids), with or without ground truth. write_instances writes
+    the instance predictions in the Cityscapes benchmark format to results_dir/inst_seg (Cityscapes.write_instance_result; mask PNGs
+    of bit depth 1 with instances_1bit), with or without ground truth."""
     net = config.network
     metrics = {}
     if write_ssegs:
         dataset.write_segmentation_result(results['all_ssegs'], ssegs_folder(results_dir, ssegs_label_ids), label_ids=ssegs_label_ids)
+    if write_instances:
+        dataset.write_instance_result(results['all_boxes'], results['all_masks'], results_dir, one_bit=instances_1bit)
     if not dataset.has_gt:
         logger.info('%s has no annotations (%s): evaluation skipped', dataset.name, os.path.basename(dataset.instances_json_file))
         if write_panoptic:
@@ -274,6 +284,15 @@ def main(argv=None):
         raise SystemExit('--eval_instances scores instance masks against the Cityscapes gtFine instanceIds maps: it needs '
                          'dataset.dataset = Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
                          % (config.dataset.dataset, net.has_rcnn, net.has_mask_head))
+    if args.write_instances and not (config.dataset.dataset == 'Cityscapes' and net.has_rcnn and net.has_mask_head):
+        raise SystemExit('--write_instances writes the instance masks in the Cityscapes benchmark format: it needs dataset.dataset = '
+                         'Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
+                         % (config.dataset.dataset, net.has_rcnn, net.has_mask_head))
+    if args.instances_1bit and not args.write_instances:
+        raise SystemExit('--instances_1bit chooses the mask format of --write_instances, which is missing')
+    if args.score_instances and config.dataset.dataset != 'Cityscapes':     # (no model is built: the heads do not matter)
+        raise SystemExit('--score_instances scores instance prediction files against the Cityscapes gtFine instanceIds maps: it needs '
+                         'dataset.dataset = Cityscapes (dataset=%s)' % config.dataset.dataset)
     vis_mask = bool(config.test.get('vis_mask', False))
     if vis_mask and not (net.has_rcnn and net.has_mask_head):
         raise SystemExit('--vis_mask (config.test.vis_mask) draws the detections and their instance masks: it needs network.has_rcnn and '
@@ -316,6 +335,15 @@ def main(argv=None):
         dataset.check_pixel_files()
         logger.info('pixel-level result of %s:', args.score_ssegs)
         return {'metrics': {'pixel_iou': dataset.evaluate_pixels_files(args.score_ssegs)}, 'results_file': None, 'times': None}
+    if args.score_instances:
+        if not os.path.isdir(args.score_instances):
+            raise SystemExit('--score_instances: no folder at %s' % args.score_instances)
+        dataset = build_dataset(out_dir)
+        if not dataset.has_gt:
+            raise SystemExit('--score_instances: %s has no ground truth to score against' % dataset.name)
+        dataset.check_instance_files()
+        logger.info('instance-level result of %s:', args.score_instances)
+        return {'metrics': {'instance_ap': dataset.evaluate_instances_files(args.score_instances)}, 'results_file': None, 'times': None}
     results_dir = os.path.join(out_dir, 'results')
     results_file = os.path.join(results_dir, 'results_list.pkl')
     if args.eval_only:
@@ -335,11 +363,11 @@ def main(argv=None):
             vis_files = draw_results(dataset, results, results_dir)
             return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                                  args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                                 args.ssegs_label_ids),
+                                                 args.ssegs_label_ids, args.write_instances, args.instances_1bit),
                     'results_file': results_file, 'times': None, 'vis_files': vis_files}
         return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                             args.ssegs_label_ids),
+                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit),
                 'results_file': results_file, 'times': None}
 
     dataset = build_dataset(out_dir)
@@ -367,7 +395,7 @@ def main(argv=None):
         return {'metrics': {}, 'results_file': results_file, 'times': times, 'vis_files': draw_results(dataset, results, results_dir)}
     return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                             args.ssegs_label_ids),
+                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit),
             'results_file': results_file, 'times': times}
 
 
