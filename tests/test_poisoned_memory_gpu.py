@@ -213,6 +213,11 @@ CASES = [
     _c('mask_roi_agnostic_none', _OPS, 'test_mask_roi_bitexact', ('ops.mask_roi',), N=50, C=9, agn=True, thresh=0.999, peaky=0.1),
     _c('mask_roi_dedup', 'test_model_gpu', 'test_mask_head_dedup_is_bit_identical_to_two_passes',
        ('ops.mask_roi_dedup', 'ops.mask_roi', 'ops.mask_logit_gather')),
+    _c('nms_chain_1025', 'test_selection_structured_gpu', 'test_nms_structured', ('ops.gpu_nms', 'ops.nms_batched'), name='chain-1025-0.5'),
+    _c('proposals_tail_pass', 'test_selection_structured_gpu', 'test_proposals_structured', ('ops.pyramid_proposals',),
+       name='decided_in-tail2-60', individual=True),
+    _c('mask_roi_cut_in_tie', 'test_selection_structured_gpu', 'test_mask_roi_structured', ('ops.mask_roi',),
+       name='cut_in_tie', agn=False, clip=True),
     # ---------------------------------------------------------------- panoptic head / fuse / argmax / tail, post-processing
     _c('panoptic_head_one', _OPS, 'test_panoptic_head_bitexact',
        ('ops.panoptic_fuse', 'ops.mask_paste', 'ops.seg_term', 'ops.panoptic_argmax', 'ops.mask_removal'), m=1, S=19, C=9, H=64, W=64, void=True),
