@@ -780,6 +780,35 @@ int upsnet_det_eval_accumulate(void *stream, long num_records, const double *rec
                                const int64_t *npig, const double *rec_thrs, void *workspace, double *precision, double *recall,
                                double *scores);
 
+/* Boundary AP (the Boundary IoU API's COCOeval with iouType 'boundary', Cheng et al. 2021): upsnet_det_eval_image's mask evaluation with
+ * IoU = min(rleIou of the masks, rleIou of their boundaries), boundary = mask & ~erode(mask), the erosion `dilation` (>= 1) rounds of a 3x3
+ * square on the zero-padded mask, i.e. the AND over the (2 * dilation + 1)^2 window with everything outside the image read as 0
+ * (mask_to_boundary; dilation = upsnet_amd.dataset.boundary.boundary_dilation(height, width, ratio) on the host). Crowd GTs get a
+ * boundary like any other; a detection's area stays its mask's. All other arguments, the records and npig as upsnet_det_eval_image with
+ * segm = 1 (no det_xyxy / gt_box). workspace: upsnet_det_eval_boundary_image_workspace_bytes(...) bytes, 256-byte aligned; no zeroing.
+ * upsnet_boundary_dilation_fits: 1 when the erosion window of `dilation` fits the kernel's tile on this image size (always when
+ * 2 * dilation + 1 exceeds the height or the width, else up to dilation 3056); the entry points refuse a dilation that does not. */
+size_t upsnet_det_eval_boundary_image_workspace_bytes(int num_det, int num_rows, int num_gt, int height, int width);
+int upsnet_det_eval_boundary_image(void *stream, int dilation, int height, int width, int num_rows, int num_det,
+                                   const double *det_score, const int64_t *det_cls, const int *class_to_row, int num_classes,
+                                   const float *det_box_f32, const float *mask_prob, int num_mask_channels, int mask_size,
+                                   const int *det_trans, const int64_t *det_trans_off, int num_gt, const int *gt_row_off,
+                                   const double *gt_area, const int *gt_crowd, const int *gt_trans,
+                                   const int64_t *gt_trans_off, const int *gt_trans_dst, int num_gt_rle,
+                                   const unsigned char *const *gt_u8, const int *gt_u8_dst, int num_gt_u8, const int *rows_with_gt,
+                                   int num_rows_with_gt, const double *params, int image_index, void *workspace, double *rec_score,
+                                   int *rec_img, int *rec_rk, uint64_t *rec_match, uint64_t *rec_ign, int64_t *npig);
+int upsnet_boundary_dilation_fits(int height, int width, int dilation);
+
+/* mask_to_boundary of num_masks masks of one size with the evaluator's kernel: either masks_u8 uint8 [num_masks][H][W] (non-zero = set)
+ * or run-lengths trans (ascending column-major change positions, the first starting a run of ones) with trans_off int64
+ * [num_masks + 1]. Outputs (fully written): boundary_u8 uint8 [num_masks][H][W] of 0 / 1, boundary_area int [num_masks] (its pixels).
+ * workspace: upsnet_boundary_masks_workspace_bytes(num_masks, height, width) bytes, 256-byte aligned; no zeroing. H * W < 2^31,
+ * num_masks <= 65535. Launches on `stream` only, no host synchronisation. */
+size_t upsnet_boundary_masks_workspace_bytes(int num_masks, int height, int width);
+int upsnet_boundary_masks(void *stream, int dilation, int height, int width, int num_masks, const unsigned char *masks_u8,
+                          const int *trans, const int64_t *trans_off, void *workspace, unsigned char *boundary_u8, int *boundary_area);
+
 /* Polygon GT -> run-length masks for upsnet_det_eval_image (gt_trans / gt_trans_off), all polygon objects of ONE image: pycocotools'
  * rleFrPoly (frPyObjects of a polygon list) and merge (union) restated from the published algorithm (csrc/poly_raster.hip).
  *   vertices double [total_vertices][2] (x, y) on the device; poly_off int [num_poly + 1]: the first vertex of each polygon;

@@ -134,6 +134,12 @@ _SIGNATURES = {
                                       P, P, P, c_int, P, P, c_int, P, c_int, P, c_int, P, P, P, P, P, P, P]),
     "upsnet_det_eval_accumulate_workspace_bytes": (c_size_t, [c_long, c_int]),
     "upsnet_det_eval_accumulate": (c_int, [P, c_long, P, P, P, P, P, P, c_int, P, P, P, P, P, P]),
+    "upsnet_det_eval_boundary_image_workspace_bytes": (c_size_t, [c_int] * 5),
+    "upsnet_det_eval_boundary_image": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, c_int, c_int, P, P, c_int, P, P, P,
+                                               P, P, P, c_int, P, P, c_int, P, c_int, P, c_int, P, P, P, P, P, P, P]),
+    "upsnet_boundary_dilation_fits": (c_int, [c_int, c_int, c_int]),
+    "upsnet_boundary_masks_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "upsnet_boundary_masks": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
     "upsnet_poly_raster_workspace_bytes": (c_size_t, [c_long, c_long]),
     "upsnet_poly_raster": (c_int, [P, P, P, P, P, P, c_int, c_int, c_long, c_int, c_int, P, P, P]),
     "upsnet_proposal_recall_workspace_bytes": (c_size_t, [c_int, c_long]),

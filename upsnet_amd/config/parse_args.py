@@ -22,6 +22,11 @@ def parse_args(description='', argv=None):
                         help='also score the combined (heuristic merge) panoptic result of the detections and the semantic map')
     parser.add_argument('--eval_proposals', action='store_true',
                         help='also keep the RPN proposals of every image and score their recall (AR@100/300/1000, all/small/medium/large)')
+    parser.add_argument('--eval_boundary', action='store_true',
+                        help='also score the instance masks with Boundary AP (COCOeval with IoU = min(mask IoU, boundary IoU)); needs '
+                        'a mask head')
+    parser.add_argument('--boundary_dilation_ratio', type=float, default=None, metavar='R',
+                        help='with --eval_boundary: the boundary width as a fraction of the image diagonal (default 0.02)')
     parser.add_argument('--eval_instances', action='store_true',
                         help='Cityscapes only: also score the instance masks with the Cityscapes instance-level AP / AP50% '
                         '(the gtFine instanceIds maps are read)')

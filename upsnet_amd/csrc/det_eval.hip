@@ -7,6 +7,9 @@
 //   det_paste_kernel   segm, model masks: the im_post paste rule (impaste.h) into a column-major bit plane, box region only
 //   det_pack_rle_kernel / det_pack_u8_kernel
 //                      segm: run-length (transition list) or uint8 masks into full column-major bit planes + pixel counts
+//   bnd_erode_kernel   boundary ('boundary' of the Boundary IoU API's COCOeval): mask & ~erode(mask, (2d+1) x (2d+1)) of every det and
+//                      GT plane over its rectangle, bit-parallel and separable -- down a column by the nearest zero of the
+//                      neighbouring words, across columns by a doubled window in LDS; the IoU is then min(mask IoU, boundary IoU)
 //   det_iou_kernel     one workgroup per (row, det slot): IoU against every GT of the row -- bbIou in double for boxes, integer
 //                      intersection / union over the det's plane rectangle (__popcll) for masks (rleIou)
 //   det_match_kernel   one wavefront per row, one lane per (area range, IoU threshold): evaluateImg's greedy matching; the
@@ -185,16 +188,171 @@ det_pack_u8_kernel(const unsigned char *__restrict__ mask, const int p, const in
     if (c) atomicAdd(&area[p], c);
 }
 
+// ------------------------------------------------------------------------------------------------------------------ boundary
+// mask_to_boundary of the Boundary IoU API: d rounds of a 3x3 erosion of the zero-padded mask = the AND over the (2d+1) x (2d+1)
+// window with everything outside the image read as 0; boundary = mask & ~eroded.
+#define BND_LDS_WORDS 6144                    // 48 KiB of window words per workgroup
+#define BND_ITEMS (BND_LDS_WORDS / DE_BT)     // words a thread holds across one doubling step
+
+__global__ void bnd_full_rect_kernel(int *__restrict__ rect, const int n, const int W, const int nw)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rect[i * 4 + 0] = 0; rect[i * 4 + 1] = W; rect[i * 4 + 2] = 0; rect[i * 4 + 3] = nw;
+}
+
+// word w of column `col` (words [w0, w1) of the rectangle; every other word reads as 0) eroded along the column: bit y survives iff
+// no zero lies within d rows of it. Inside the word the zeros are smeared d (<= 63) bits both ways; of a neighbouring word only its
+// zero nearest to this word matters.
+__device__ static inline de_u64 bnd_erode_column_word(const de_u64 *__restrict__ col, const int w, const int w0, const int w1, const int d)
+{
+    const de_u64 z = ~col[w];
+    de_u64 up = z, dn = z;
+    const int n = min(d, 63);
+    for (int c = 0; c < n;) {
+        const int t = min(c + 1, n - c);
+        up |= up << t; dn |= dn >> t;
+        c += t;
+    }
+    de_u64 r = up | dn;
+    const int q = (d + 63) >> 6;
+    for (int j = 1; j <= q && r != ~0ull; ++j) {
+        const de_u64 za = w + j < w1 ? ~col[w + j] : ~0ull;   // the word j further down the column: its lowest zero reaches back to row 64j + b - d
+        if (za) {
+            const int lo = 64 * j + __builtin_ctzll(za) - d;
+            if (lo <= 63) r |= lo <= 0 ? ~0ull : ~0ull << lo;
+        }
+        const de_u64 zb = w - j >= w0 ? ~col[w - j] : ~0ull;  // the word j before: its highest zero reaches on to row -64j + b + d
+        if (zb) {
+            const int hi = -64 * j + (63 - __builtin_clzll(zb)) + d;
+            if (hi >= 0) r |= hi >= 63 ? ~0ull : (2ull << hi) - 1ull;
+        }
+    }
+    return ~r;
+}
+
+// Entry e = blockIdx.y: plane plane_of[e] (e when plane_of is null; negative: not evaluated, nothing written) with rectangle rect[e];
+// blockIdx.x = (tile of TX columns, slab of WS words) of that rectangle, blocks past it return. The column-eroded words of the
+// tile's columns and d more on either side (zero outside the rectangle) go to LDS as [column][word of the slab]; log2 steps of
+// P[c] &= P[c + k] leave the AND over p = 2^k columns from c on, and the window of 2d+1 is two of them, at c and at c + 2d+1 - p.
+// d < 0: nothing survives the erosion (2d+1 exceeds the image), the boundary is the mask. cnt[e] += the boundary's pixels.
+__global__ void __launch_bounds__(DE_BT)
+bnd_erode_kernel(const de_u64 *__restrict__ planes, const int *__restrict__ rect, const int *__restrict__ plane_of, const int H, const int W,
+                 const int d, const int TX, const int WS, de_u64 *__restrict__ out, int *__restrict__ cnt)
+{
+    extern __shared__ de_u64 s_win[];
+    __shared__ int s_red[DE_BT / UPS_WAVE];
+    const int e = blockIdx.y, tid = threadIdx.x, nw = (H + 63) >> 6;
+    const int pl = plane_of ? plane_of[e] : e;
+    if (pl < 0) return;
+    const int x0 = rect[e * 4 + 0], x1 = rect[e * 4 + 1], w0 = rect[e * 4 + 2], w1 = rect[e * 4 + 3];
+    const int slabs = (nw + WS - 1) / WS;
+    const int xa = x0 + (int)(blockIdx.x / slabs) * TX, wa = w0 + (int)(blockIdx.x % slabs) * WS;
+    if (xa >= x1 || wa >= w1) return;
+    const int xb = min(xa + TX, x1), ws = min(WS, w1 - wa);
+    const de_u64 *plane = planes + (long)pl * W * nw;
+    de_u64 *oplane = out + (long)pl * W * nw;
+    const int L = 2 * d + 1;
+    int p = 1;
+    if (d >= 0) {
+        const int ca = xa - d, n = (xb - xa + 2 * d) * ws;   // n <= (TX + 2d) * WS <= BND_LDS_WORDS
+        for (int q = tid; q < n; q += DE_BT) {
+            const int x = ca + q / ws, w = wa + q % ws;
+            s_win[q] = (x >= x0 && x < x1) ? bnd_erode_column_word(plane + (long)x * nw, w, w0, w1, d) : 0ull;
+        }
+        __syncthreads();
+        for (; 2 * p <= L; p <<= 1) {
+            de_u64 r[BND_ITEMS];
+#pragma unroll
+            for (int i = 0; i < BND_ITEMS; ++i) {
+                const int q = tid + i * DE_BT;
+                if (q < n) r[i] = s_win[q] & (q + p * ws < n ? s_win[q + p * ws] : 0ull);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < BND_ITEMS; ++i) {
+                const int q = tid + i * DE_BT;
+                if (q < n) s_win[q] = r[i];
+            }
+            __syncthreads();
+        }
+    }
+    int c = 0;
+    const int no = (xb - xa) * ws;
+    for (int q = tid; q < no; q += DE_BT) {
+        const long o = (long)(xa + q / ws) * nw + wa + q % ws;
+        const de_u64 m = plane[o];
+        const de_u64 er = d >= 0 ? s_win[q] & s_win[q + (L - p) * ws] : 0ull;
+        const de_u64 b = m & ~er;
+        oplane[o] = b;
+        c += __popcll(b);
+    }
+    for (int s = UPS_WAVE / 2; s > 0; s >>= 1) c += __shfl_xor(c, s);
+    if ((tid & (UPS_WAVE - 1)) == 0) s_red[tid / UPS_WAVE] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        for (int wv = 0; wv < DE_BT / UPS_WAVE; ++wv) t += s_red[wv];
+        if (t) atomicAdd(&cnt[e], t);
+    }
+}
+
+// planes (inside each plane's rectangle, 0 outside it) -> uint8 [n][H][W] masks of 0 / 1; x fastest: neighbouring threads write
+// neighbouring bytes
+__global__ void __launch_bounds__(DE_BT)
+bnd_unpack_u8_kernel(const de_u64 *__restrict__ planes, const int *__restrict__ rect, const int H, const int W, unsigned char *__restrict__ mask)
+{
+    const int p = blockIdx.y, nw = (H + 63) >> 6;
+    const long q = (long)blockIdx.x * DE_BT + threadIdx.x;
+    if (q >= (long)W * nw) return;
+    const int w = (int)(q / W), x = (int)(q - (long)w * W);
+    const bool in = x >= rect[p * 4 + 0] && x < rect[p * 4 + 1] && w >= rect[p * 4 + 2] && w < rect[p * 4 + 3];
+    const de_u64 bits = in ? planes[((long)p * W + x) * nw + w] : 0ull;
+    unsigned char *o = mask + (long)p * H * W;
+    for (int y = w << 6; y < min((w << 6) + 64, H); ++y) o[(long)y * W + x] = (unsigned char)((bits >> (y & 63)) & 1);
+}
+
+struct BndTile { int d, TX, WS, grid_x; size_t lds; };
+
+// the tile of bnd_erode_kernel for dilation d on an H x W image; false when the window does not fit the LDS budget
+static bool bnd_tile(int H, int W, int d, BndTile *t)
+{
+    const int nw = (H + 63) / 64;
+    if (2L * d + 1 > H || 2L * d + 1 > W) {   // every window leaves the image: nothing survives
+        t->d = -1; t->WS = std::min(nw, 16); t->TX = std::min(W, BND_LDS_WORDS / t->WS); t->lds = 0;
+    } else {
+        if (2L * d + 32 > BND_LDS_WORDS) return false;
+        t->d = d;
+        t->WS = std::min(nw, BND_LDS_WORDS / (2 * d + 32));
+        t->TX = std::min(std::min(W, 256), BND_LDS_WORDS / t->WS - 2 * d);
+        t->lds = sizeof(de_u64) * (size_t)(t->TX + 2 * d) * t->WS;
+    }
+    t->grid_x = ((W + t->TX - 1) / t->TX) * ((nw + t->WS - 1) / t->WS);
+    return true;
+}
+
+static int bnd_launch(hipStream_t st, const BndTile &t, const de_u64 *planes, const int *rect, const int *plane_of, int n, int H, int W,
+                      de_u64 *out, int *cnt)
+{
+    UPS_REQUIRE(n <= 65535, "boundary: %d masks in one call (at most 65535)", n);
+    UPS_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * n, st));
+    hipLaunchKernelGGL(bnd_erode_kernel, dim3(t.grid_x, n), dim3(DE_BT), t.lds, st, planes, rect, plane_of, H, W, t.d, t.TX, t.WS, out, cnt);
+    UPS_CHECK_LAUNCH("bnd_erode_kernel");
+    return 0;
+}
+
 // IoU of det slot (row, d) against the row's GTs -> ious[100 * off_k + d * G_k + g]. bbox: bbIou (maskApi.c) on xywh doubles,
-// det xywh from xyxy as xyxy_to_xywh does (w = x2 - x1 + 1). segm: rleIou, i / u over pixel counts.
+// det xywh from xyxy as xyxy_to_xywh does (w = x2 - x1 + 1). segm: rleIou, i / u over pixel counts. With boundary planes (det_bnd
+// non-null; the GT ones are written inside gt_rect only) the result is the smaller of the mask's and the boundary's rleIou.
 __global__ void __launch_bounds__(DE_BT)
 det_iou_kernel(const int segm, const int *__restrict__ rows, const int *__restrict__ slot, const int *__restrict__ nd,
                const double *__restrict__ det_xyxy, const int *__restrict__ det_rect, const int *__restrict__ det_area,
                const int *__restrict__ plane_of, const de_u64 *__restrict__ det_planes, const int *__restrict__ gt_off, const double *__restrict__ gt_box,
                const int *__restrict__ gt_crowd, const de_u64 *__restrict__ gt_planes, const int *__restrict__ gt_area, const int H,
-               const int W, double *__restrict__ ious)
+               const int W, double *__restrict__ ious, const de_u64 *__restrict__ det_bnd, const int *__restrict__ det_barea,
+               const de_u64 *__restrict__ gt_bnd, const int *__restrict__ gt_barea, const int *__restrict__ gt_rect)
 {
-    __shared__ int s_red[DE_BT / UPS_WAVE];
+    __shared__ int s_red[DE_BT / UPS_WAVE], s_redb[DE_BT / UPS_WAVE];
     const int k = rows[blockIdx.y], d = blockIdx.x, tid = threadIdx.x;
     if (d >= nd[k]) return;
     const int g0 = gt_off[k], G = gt_off[k + 1] - g0;
@@ -227,21 +385,51 @@ det_iou_kernel(const int segm, const int *__restrict__ rows, const int *__restri
     const long nwords = (x1 > x0 && nwr > 0) ? (long)(x1 - x0) * nwr : 0;
     const de_u64 *dp = det_planes + (long)plane_of[i] * W * nw;
     const long da = det_area[i];
-    for (int g = 0; g < G; ++g) {
-        const de_u64 *gp = gt_planes + (long)(g0 + g) * W * nw;
-        int c = 0;
-        for (long q = tid; q < nwords; q += DE_BT) {
-            const long o = (long)(x0 + (int)(q / nwr)) * nw + w0 + (int)(q % nwr);
-            c += __popcll(dp[o] & gp[o]);
+    if (!det_bnd) {
+        for (int g = 0; g < G; ++g) {
+            const de_u64 *gp = gt_planes + (long)(g0 + g) * W * nw;
+            int c = 0;
+            for (long q = tid; q < nwords; q += DE_BT) {
+                const long o = (long)(x0 + (int)(q / nwr)) * nw + w0 + (int)(q % nwr);
+                c += __popcll(dp[o] & gp[o]);
+            }
+            for (int s = UPS_WAVE / 2; s > 0; s >>= 1) c += __shfl_xor(c, s);
+            if ((tid & (UPS_WAVE - 1)) == 0) s_red[tid / UPS_WAVE] = c;
+            __syncthreads();
+            if (tid == 0) {
+                long in = 0;
+                for (int wv = 0; wv < DE_BT / UPS_WAVE; ++wv) in += s_red[wv];
+                const long u = gt_crowd[g0 + g] ? da : da + (long)gt_area[g0 + g] - in;
+                out[g] = in == 0 ? 0.0 : (double)in / (double)u;
+            }
+            __syncthreads();
         }
-        for (int s = UPS_WAVE / 2; s > 0; s >>= 1) c += __shfl_xor(c, s);
-        if ((tid & (UPS_WAVE - 1)) == 0) s_red[tid / UPS_WAVE] = c;
+        return;
+    }
+    const de_u64 *bp = det_bnd + (long)plane_of[i] * W * nw;
+    const long dba = det_barea[i];
+    for (int g = 0; g < G; ++g) {
+        const de_u64 *gp = gt_planes + (long)(g0 + g) * W * nw, *gbp = gt_bnd + (long)(g0 + g) * W * nw;
+        const int *gr = gt_rect + (long)(g0 + g) * 4;
+        const int gx0 = gr[0], gx1 = gr[1], gw0 = gr[2], gw1 = gr[3];
+        int c = 0, cb = 0;
+        for (long q = tid; q < nwords; q += DE_BT) {
+            const int x = x0 + (int)(q / nwr), w = w0 + (int)(q % nwr);
+            const long o = (long)x * nw + w;
+            c += __popcll(dp[o] & gp[o]);
+            if (x >= gx0 && x < gx1 && w >= gw0 && w < gw1) cb += __popcll(bp[o] & gbp[o]);
+        }
+        for (int s = UPS_WAVE / 2; s > 0; s >>= 1) { c += __shfl_xor(c, s); cb += __shfl_xor(cb, s); }
+        if ((tid & (UPS_WAVE - 1)) == 0) { s_red[tid / UPS_WAVE] = c; s_redb[tid / UPS_WAVE] = cb; }
         __syncthreads();
         if (tid == 0) {
-            long in = 0;
-            for (int wv = 0; wv < DE_BT / UPS_WAVE; ++wv) in += s_red[wv];
-            const long u = gt_crowd[g0 + g] ? da : da + (long)gt_area[g0 + g] - in;
-            out[g] = in == 0 ? 0.0 : (double)in / (double)u;
+            long in = 0, inb = 0;
+            for (int wv = 0; wv < DE_BT / UPS_WAVE; ++wv) { in += s_red[wv]; inb += s_redb[wv]; }
+            const int crowd = gt_crowd[g0 + g];
+            const long u = crowd ? da : da + (long)gt_area[g0 + g] - in;
+            const long ub = crowd ? dba : dba + (long)gt_barea[g0 + g] - inb;
+            const double m = in == 0 ? 0.0 : (double)in / (double)u, b = inb == 0 ? 0.0 : (double)inb / (double)ub;
+            out[g] = fmin(m, b);
         }
         __syncthreads();
     }
@@ -521,7 +709,8 @@ det_curve_kernel(const int K, const int64_t *__restrict__ npig, const int *__res
 }
 
 // ------------------------------------------------------------------------------------------------------------------ C ABI
-extern "C" size_t upsnet_det_eval_image_workspace_bytes(int num_det, int num_rows, int num_gt, int height, int width, int segm)
+// mode: 0 bbox, 1 segm, 2 boundary (segm + the boundary planes, their pixel counts and the GT rectangles)
+static size_t det_img_workspace_bytes(int num_det, int num_rows, int num_gt, int height, int width, int segm)
 {
     if (num_det < 0 || num_rows < 1 || num_gt < 0 || height < 1 || width < 1) return 0;
     const size_t plane = (size_t)width * ((height + 63) / 64) * 8;
@@ -529,14 +718,25 @@ extern "C" size_t upsnet_det_eval_image_workspace_bytes(int num_det, int num_row
     size_t b = de_align(sizeof(int) * ((size_t)num_rows * (DE_MAXDET + 1) + 1)) + de_align(sizeof(int) * (num_det + 1))
              + de_align(sizeof(double) * DE_MAXDET * (size_t)num_gt + 8) + de_align((size_t)DE_A * DE_T * num_gt + 1);
     if (segm) b += de_align(sizeof(int) * 6 * (size_t)(num_det + 1)) + plane * nplanes + de_align(sizeof(int) * (num_gt + 1)) + plane * num_gt;
+    if (segm == 2) b += de_align(sizeof(int) * (size_t)(num_det + 1)) + plane * nplanes + de_align(sizeof(int) * 5 * (size_t)(num_gt + 1)) + plane * num_gt;
     return b;
 }
 
+extern "C" size_t upsnet_det_eval_image_workspace_bytes(int num_det, int num_rows, int num_gt, int height, int width, int segm)
+{
+    return det_img_workspace_bytes(num_det, num_rows, num_gt, height, width, segm ? 1 : 0);
+}
+
+extern "C" size_t upsnet_det_eval_boundary_image_workspace_bytes(int num_det, int num_rows, int num_gt, int height, int width)
+{
+    return det_img_workspace_bytes(num_det, num_rows, num_gt, height, width, 2);
+}
+
 struct DetImgLayout {
-    int *slot, *nd, *nplanes, *rank, *plane_of, *det_rect, *det_area, *gt_area;
+    int *slot, *nd, *nplanes, *rank, *plane_of, *det_rect, *det_area, *gt_area, *det_barea, *gt_barea, *gt_rect;
     double *ious;
     unsigned char *gtm;
-    de_u64 *det_planes, *gt_planes;
+    de_u64 *det_planes, *gt_planes, *det_bnd, *gt_bnd;
 };
 
 static DetImgLayout det_img_layout(void *ws, int n, int K, int G, int H, int W, int segm)
@@ -557,18 +757,25 @@ static DetImgLayout det_img_layout(void *ws, int n, int K, int G, int H, int W, 
         L.gt_area = (int *)(p + o); o += de_align(sizeof(int) * (G + 1));
         L.gt_planes = (de_u64 *)(p + o); o += plane * G;
     }
+    if (segm == 2) {
+        L.det_barea = (int *)(p + o); o += de_align(sizeof(int) * (size_t)(n + 1));
+        L.det_bnd = (de_u64 *)(p + o); o += plane * std::min((size_t)n, (size_t)DE_MAXDET * K);
+        L.gt_barea = (int *)(p + o); L.gt_rect = L.gt_barea + (G + 1); o += de_align(sizeof(int) * 5 * (size_t)(G + 1));
+        L.gt_bnd = (de_u64 *)(p + o); o += plane * G;
+    }
     return L;
 }
 
-extern "C" int upsnet_det_eval_image(void *stream, int segm, int height, int width, int num_rows, int num_det, const double *det_xyxy,
-                                     const double *det_score, const int64_t *det_cls, const int *class_to_row, int num_classes,
-                                     const float *det_box_f32, const float *mask_prob, int num_mask_channels, int mask_size,
-                                     const int *det_trans, const int64_t *det_trans_off, int num_gt, const int *gt_row_off,
-                                     const double *gt_box, const double *gt_area, const int *gt_crowd, const int *gt_trans,
-                                     const int64_t *gt_trans_off, const int *gt_trans_dst, int num_gt_rle, const unsigned char *const *gt_u8,
-                                     const int *gt_u8_dst, int num_gt_u8, const int *rows_with_gt, int num_rows_with_gt,
-                                     const double *params, int image_index, void *workspace, double *rec_score, int *rec_img, int *rec_rk,
-                                     uint64_t *rec_match, uint64_t *rec_ign, int64_t *npig)
+// segm: 0 bbox, 1 segm, 2 boundary with dilation d
+static int det_eval_image(void *stream, int segm, int dilation, int height, int width, int num_rows, int num_det, const double *det_xyxy,
+                          const double *det_score, const int64_t *det_cls, const int *class_to_row, int num_classes,
+                          const float *det_box_f32, const float *mask_prob, int num_mask_channels, int mask_size,
+                          const int *det_trans, const int64_t *det_trans_off, int num_gt, const int *gt_row_off,
+                          const double *gt_box, const double *gt_area, const int *gt_crowd, const int *gt_trans,
+                          const int64_t *gt_trans_off, const int *gt_trans_dst, int num_gt_rle, const unsigned char *const *gt_u8,
+                          const int *gt_u8_dst, int num_gt_u8, const int *rows_with_gt, int num_rows_with_gt,
+                          const double *params, int image_index, void *workspace, double *rec_score, int *rec_img, int *rec_rk,
+                          uint64_t *rec_match, uint64_t *rec_ign, int64_t *npig)
 {
     hipStream_t st = (hipStream_t)stream;
     UPS_REQUIRE(height > 0 && width > 0 && (long)height * width < (1L << 31), "det_eval_image: bad image size %dx%d", height, width);
@@ -585,6 +792,8 @@ extern "C" int upsnet_det_eval_image(void *stream, int segm, int height, int wid
                     && (num_gt_u8 == 0 || (gt_u8 && gt_u8_dst)), "det_eval_image: every GT needs one mask");
     }
     const int K = num_rows, n = num_det, G = num_gt, H = height, W = width;
+    BndTile tile = {};
+    if (segm == 2) UPS_REQUIRE(dilation >= 1 && bnd_tile(H, W, dilation, &tile), "det_eval_boundary_image: dilation %d out of range", dilation);
     DetImgLayout L = det_img_layout(workspace, n, K, G, H, W, segm);
     hipLaunchKernelGGL(det_zero_kernel, dim3((K + 1 + DE_BT - 1) / DE_BT), dim3(DE_BT), 0, st, L.nd, K + 1);   // nd and the plane counter
     UPS_CHECK_LAUNCH("det_zero_kernel");
@@ -609,9 +818,13 @@ extern "C" int upsnet_det_eval_image(void *stream, int segm, int height, int wid
                                L.det_area);
             UPS_CHECK_LAUNCH("det_pack_rle_kernel");
         }
+        if (segm == 2 && G > 0) {   // the GT rectangles: the run-length GTs write their column range below, a uint8 GT keeps the whole plane
+            hipLaunchKernelGGL(bnd_full_rect_kernel, dim3((G + DE_BT - 1) / DE_BT), dim3(DE_BT), 0, st, L.gt_rect, G, W, nw);
+            UPS_CHECK_LAUNCH("bnd_full_rect_kernel");
+        }
         if (num_gt_rle > 0) {
             hipLaunchKernelGGL(det_pack_rle_kernel, dim3((unsigned)((words + DE_BT - 1) / DE_BT), num_gt_rle), dim3(DE_BT), 0, st, gt_trans,
-                               gt_trans_off, gt_trans_dst, (const int *)nullptr, H, W, L.gt_planes, (int *)nullptr,
+                               gt_trans_off, gt_trans_dst, (const int *)nullptr, H, W, L.gt_planes, L.gt_rect,
                                L.gt_area);
             UPS_CHECK_LAUNCH("det_pack_rle_kernel");
         }
@@ -620,16 +833,102 @@ extern "C" int upsnet_det_eval_image(void *stream, int segm, int height, int wid
                                H, W, L.gt_planes, L.gt_area);
             UPS_CHECK_LAUNCH("det_pack_u8_kernel");
         }
+        if (segm == 2 && num_rows_with_gt > 0 && n > 0) {   // (no GT or no det: no IoU is taken, no boundary is needed)
+            if (bnd_launch(st, tile, L.det_planes, L.det_rect, L.plane_of, n, H, W, L.det_bnd, L.det_barea)) return 1;
+            if (bnd_launch(st, tile, L.gt_planes, L.gt_rect, (const int *)nullptr, G, H, W, L.gt_bnd, L.gt_barea)) return 1;
+        }
     }
     if (num_rows_with_gt > 0 && n > 0) {
         UPS_REQUIRE(rows_with_gt, "det_eval_image: null row list");
         hipLaunchKernelGGL(det_iou_kernel, dim3(DE_MAXDET, num_rows_with_gt), dim3(DE_BT), 0, st, segm, rows_with_gt, L.slot, L.nd, det_xyxy,
-                           L.det_rect, L.det_area, L.plane_of, L.det_planes, gt_row_off, gt_box, gt_crowd, L.gt_planes, L.gt_area, H, W, L.ious);
+                           L.det_rect, L.det_area, L.plane_of, L.det_planes, gt_row_off, gt_box, gt_crowd, L.gt_planes, L.gt_area, H, W, L.ious,
+                           L.det_bnd, L.det_barea, L.gt_bnd, L.gt_barea, L.gt_rect);
         UPS_CHECK_LAUNCH("det_iou_kernel");
     }
     hipLaunchKernelGGL(det_match_kernel, dim3(K), dim3(UPS_WAVE), 0, st, segm, L.slot, L.nd, det_xyxy, L.det_area, gt_row_off, gt_area,
                        gt_crowd, L.ious, params, L.gtm, (de_u64 *)rec_match, (de_u64 *)rec_ign, npig);
     UPS_CHECK_LAUNCH("det_match_kernel");
+    return 0;
+}
+
+extern "C" int upsnet_det_eval_image(void *stream, int segm, int height, int width, int num_rows, int num_det, const double *det_xyxy,
+                                     const double *det_score, const int64_t *det_cls, const int *class_to_row, int num_classes,
+                                     const float *det_box_f32, const float *mask_prob, int num_mask_channels, int mask_size,
+                                     const int *det_trans, const int64_t *det_trans_off, int num_gt, const int *gt_row_off,
+                                     const double *gt_box, const double *gt_area, const int *gt_crowd, const int *gt_trans,
+                                     const int64_t *gt_trans_off, const int *gt_trans_dst, int num_gt_rle, const unsigned char *const *gt_u8,
+                                     const int *gt_u8_dst, int num_gt_u8, const int *rows_with_gt, int num_rows_with_gt,
+                                     const double *params, int image_index, void *workspace, double *rec_score, int *rec_img, int *rec_rk,
+                                     uint64_t *rec_match, uint64_t *rec_ign, int64_t *npig)
+{
+    return det_eval_image(stream, segm ? 1 : 0, 0, height, width, num_rows, num_det, det_xyxy, det_score, det_cls, class_to_row, num_classes,
+                          det_box_f32, mask_prob, num_mask_channels, mask_size, det_trans, det_trans_off, num_gt, gt_row_off, gt_box, gt_area,
+                          gt_crowd, gt_trans, gt_trans_off, gt_trans_dst, num_gt_rle, gt_u8, gt_u8_dst, num_gt_u8, rows_with_gt,
+                          num_rows_with_gt, params, image_index, workspace, rec_score, rec_img, rec_rk, rec_match, rec_ign, npig);
+}
+
+extern "C" int upsnet_det_eval_boundary_image(void *stream, int dilation, int height, int width, int num_rows, int num_det,
+                                              const double *det_score, const int64_t *det_cls, const int *class_to_row, int num_classes,
+                                              const float *det_box_f32, const float *mask_prob, int num_mask_channels, int mask_size,
+                                              const int *det_trans, const int64_t *det_trans_off, int num_gt, const int *gt_row_off,
+                                              const double *gt_area, const int *gt_crowd, const int *gt_trans,
+                                              const int64_t *gt_trans_off, const int *gt_trans_dst, int num_gt_rle,
+                                              const unsigned char *const *gt_u8, const int *gt_u8_dst, int num_gt_u8, const int *rows_with_gt,
+                                              int num_rows_with_gt, const double *params, int image_index, void *workspace, double *rec_score,
+                                              int *rec_img, int *rec_rk, uint64_t *rec_match, uint64_t *rec_ign, int64_t *npig)
+{
+    return det_eval_image(stream, 2, dilation, height, width, num_rows, num_det, nullptr, det_score, det_cls, class_to_row, num_classes,
+                          det_box_f32, mask_prob, num_mask_channels, mask_size, det_trans, det_trans_off, num_gt, gt_row_off, nullptr, gt_area,
+                          gt_crowd, gt_trans, gt_trans_off, gt_trans_dst, num_gt_rle, gt_u8, gt_u8_dst, num_gt_u8, rows_with_gt,
+                          num_rows_with_gt, params, image_index, workspace, rec_score, rec_img, rec_rk, rec_match, rec_ign, npig);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ boundary masks
+extern "C" int upsnet_boundary_dilation_fits(int height, int width, int dilation)
+{
+    BndTile t;
+    return height >= 1 && width >= 1 && dilation >= 1 && bnd_tile(height, width, dilation, &t) ? 1 : 0;
+}
+
+extern "C" size_t upsnet_boundary_masks_workspace_bytes(int num_masks, int height, int width)
+{
+    if (num_masks < 0 || height < 1 || width < 1) return 0;
+    const size_t plane = (size_t)width * ((height + 63) / 64) * 8;
+    return 2 * plane * num_masks + de_align(sizeof(int) * 5 * (size_t)(num_masks + 1));
+}
+
+extern "C" int upsnet_boundary_masks(void *stream, int dilation, int height, int width, int num_masks, const unsigned char *masks_u8,
+                                     const int *trans, const int64_t *trans_off, void *workspace, unsigned char *boundary_u8,
+                                     int *boundary_area)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const int n = num_masks, H = height, W = width, nw = (H + 63) >> 6;
+    UPS_REQUIRE(H > 0 && W > 0 && (long)H * W < (1L << 31) && n >= 0, "boundary_masks: bad sizes %d x %dx%d", n, H, W);
+    BndTile tile = {};
+    UPS_REQUIRE(dilation >= 1 && bnd_tile(H, W, dilation, &tile), "boundary_masks: dilation %d out of range", dilation);
+    if (n == 0) return 0;
+    UPS_REQUIRE(workspace && boundary_u8 && boundary_area && (masks_u8 || (trans && trans_off)), "boundary_masks: null pointer");
+    const long words = (long)W * nw;
+    de_u64 *planes = (de_u64 *)workspace, *bnd = planes + (size_t)n * words;
+    int *area = (int *)(bnd + (size_t)n * words), *rect = area + (n + 1);
+    const unsigned nb = (unsigned)((words + DE_BT - 1) / DE_BT);
+    UPS_CHECK_HIP(hipMemsetAsync(area, 0, sizeof(int) * n, st));
+    hipLaunchKernelGGL(bnd_full_rect_kernel, dim3((n + DE_BT - 1) / DE_BT), dim3(DE_BT), 0, st, rect, n, W, nw);
+    UPS_CHECK_LAUNCH("bnd_full_rect_kernel");
+    if (masks_u8) {
+        for (int p = 0; p < n; ++p) {
+            hipLaunchKernelGGL(det_pack_u8_kernel, dim3(nb), dim3(DE_BT), 0, st, masks_u8 + (size_t)p * H * W, p, H, W, planes, area);
+            UPS_CHECK_LAUNCH("det_pack_u8_kernel");
+        }
+    } else {
+        UPS_REQUIRE(n <= 65535, "boundary_masks: %d masks in one call (at most 65535)", n);
+        hipLaunchKernelGGL(det_pack_rle_kernel, dim3(nb, n), dim3(DE_BT), 0, st, trans, trans_off, (const int *)nullptr, (const int *)nullptr,
+                           H, W, planes, rect, area);
+        UPS_CHECK_LAUNCH("det_pack_rle_kernel");
+    }
+    if (bnd_launch(st, tile, planes, rect, (const int *)nullptr, n, H, W, bnd, boundary_area)) return 1;
+    hipLaunchKernelGGL(bnd_unpack_u8_kernel, dim3(nb, n), dim3(DE_BT), 0, st, bnd, rect, H, W, boundary_u8);
+    UPS_CHECK_LAUNCH("bnd_unpack_u8_kernel");
     return 0;
 }
 

@@ -1,2 +1,3 @@
 from .cityscapes import Cityscapes
 from .coco import coco
+from .boundary import boundary_dilation, mask_to_boundary

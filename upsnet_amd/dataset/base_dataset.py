@@ -224,9 +224,10 @@ class BaseDataset(object):
             anns[int(a['image_id'])].append(a)
         return image_ids, sizes, anns, [int(c['id']) for c in gt_json['categories']]
 
-    def _evaluate_detections(self, all_boxes, all_segms, output_dir, iou_type):
+    def _evaluate_detections(self, all_boxes, all_segms, output_dir, iou_type, dilation_ratio=0.02):
         """The reference's evaluate_boxes / evaluate_masks: results JSON written as the reference writes it, COCOeval on the device
-        (dataset/coco_eval.py), the metrics logged and the summary lines written to detection_results.txt."""
+        (dataset/coco_eval.py), the metrics logged and the summary lines written to detection_results.txt. iou_type 'boundary'
+        (evaluate_boundary): no results JSON (evaluate_masks writes the segmentations), the summary goes to boundary_results.txt."""
         from .coco_eval import DetectionEvaluator, EvalResult, detection_metrics_lines
         from ..bbox.bbox_transform import xyxy_to_xywh
         image_ids, sizes, anns, cat_ids = self.load_instances_gt()
@@ -249,11 +250,12 @@ class BaseDataset(object):
                     else:
                         r['segmentation'] = all_segms[c][i][k]
                     results.append(r)
-        res_file = os.path.join(output_dir, ('bbox_' if all_segms is None else 'segmentations_') + name + '_results.json')
-        logger.info('Writing %s results json to: %s', iou_type, os.path.abspath(res_file))
-        with open(res_file, 'w') as fid:
-            json.dump(results, fid)
-        ev = DetectionEvaluator(cat_ids, iou_type)
+        if iou_type != 'boundary':
+            res_file = os.path.join(output_dir, ('bbox_' if all_segms is None else 'segmentations_') + name + '_results.json')
+            logger.info('Writing %s results json to: %s', iou_type, os.path.abspath(res_file))
+            with open(res_file, 'w') as fid:
+                json.dump(results, fid)
+        ev = DetectionEvaluator(cat_ids, iou_type, dilation_ratio=dilation_ratio)
         for i, image_id in enumerate(image_ids):
             dets = [[]] + [all_boxes[c][i] for c in range(1, n_cls)]
             rles = None if all_segms is None else [[]] + [all_segms[c][i] for c in range(1, n_cls)]
@@ -264,7 +266,7 @@ class BaseDataset(object):
         res = ev.accumulate()
         for line in detection_metrics_lines(res)[:-12]:
             logger.info(line)
-        with open(os.path.join(output_dir, 'detection_results.txt'), 'w') as f:
+        with open(os.path.join(output_dir, 'boundary_results.txt' if iou_type == 'boundary' else 'detection_results.txt'), 'w') as f:
             for line in res['summary_lines']:
                 print(line)
                 f.write(line + '\n')
@@ -295,6 +297,13 @@ class BaseDataset(object):
         .eval (precision / recall / scores). Writes segmentations_<name>_results.json and detection_results.txt. Polygon GT
         segmentations are rasterised on the device, one call per image (dataset/polygon.py)."""
         return self._evaluate_detections(all_boxes, all_segms, output_dir, 'segm')
+
+    def evaluate_boundary(self, all_boxes, all_segms, output_dir, dilation_ratio=0.02):
+        """Boundary AP (the Boundary IoU API's COCOeval, iouType 'boundary') of the same inputs as evaluate_masks: IoU = min(mask IoU,
+        boundary IoU), boundaries eroded by dilation_ratio x the image diagonal on the device (dataset/boundary.py). Returns an
+        object with .stats and .eval; writes boundary_results.txt only (detection_results.txt and the results JSONs stay as
+        evaluate_masks left them)."""
+        return self._evaluate_detections(all_boxes, all_segms, output_dir, 'boundary', dilation_ratio)
 
     # ---------------------------------------------------------------------------------------------- RPN proposal recall (AR)
     def evaluate_box_proposals(self, roidb, thresholds=None, area='all', limit=None):

@@ -13,8 +13,11 @@ Deliberate deviations, each refused with ValueError before any launch:
     frPyObjects + merge restated) and reach `add` / `add_rle` as views of its handle, `rasterize_polygons(...)[i]`; their run lists
     go to the kernels next to the RLE rows and never visit the host. Views of one call must come from one handle, each at most once.
 Detections of classes with no category id are dropped, as pycocotools drops results of categories outside Params.catIds; so are
-GTs of other categories. Scores must not be NaN (they are device data and are not inspected). Proposal recall
-(evaluate_box_proposals) is dataset/proposal_eval.py, the Cityscapes instance-level AP dataset/cityscapes_eval.py.
+GTs of other categories. iou_type 'boundary' is the Boundary IoU API's COCOeval (Boundary AP): everything as 'segm' except computeIoU,
+which takes min(mask IoU, boundary IoU) with boundary = mask_to_boundary(mask, dilation_ratio) (dataset/boundary.py) computed on the
+device from the same bit planes; that API is not a dependency, its rule is restated from the published source. Scores must not be
+NaN (they are device data and are not inspected). Proposal recall (evaluate_box_proposals) is dataset/proposal_eval.py, the Cityscapes
+instance-level AP dataset/cityscapes_eval.py.
 """
 import ctypes
 import logging
@@ -23,6 +26,7 @@ import numpy as np
 import torch
 
 from .._lib import check, lib, ptr, stream
+from .boundary import check_dilation_ratio, checked_dilation
 from .polygon import PolygonView
 
 logger = logging.getLogger(__name__)
@@ -131,15 +135,18 @@ class EvalResult(object):
 
 
 class DetectionEvaluator(object):
-    """Running COCO box ('bbox') or mask ('segm') evaluation of a sequence of images on one device.
+    """Running COCO box ('bbox'), mask ('segm') or boundary ('boundary': Boundary AP, masks as for 'segm', boundaries eroded by
+    dilation_ratio x the image diagonal) evaluation of a sequence of images on one device.
 
     category_ids: the dataset's category id of each class in class order (class c >= 1 is category_ids[c - 1]; class 0 is the
     background). add() / add_rle() queue one image each (no synchronisation); accumulate() / summary() synchronise once.
-    `a += b` merges the evaluator of another rank (same category_ids and iou_type, disjoint image ids)."""
+    `a += b` merges the evaluator of another rank (same category_ids, iou_type and dilation_ratio, disjoint image ids)."""
 
-    def __init__(self, category_ids, iou_type='bbox', device=None):
-        if iou_type not in ('bbox', 'segm'):
-            raise ValueError("iou_type must be 'bbox' or 'segm', got %r" % (iou_type,))
+    def __init__(self, category_ids, iou_type='bbox', device=None, dilation_ratio=0.02):
+        if iou_type not in ('bbox', 'segm', 'boundary'):
+            raise ValueError("iou_type must be 'bbox', 'segm' or 'boundary', got %r" % (iou_type,))
+        self.boundary = iou_type == 'boundary'
+        self.dilation_ratio = check_dilation_ratio(dilation_ratio) if self.boundary else None
         ids = [int(c) for c in category_ids]
         if len(ids) == 0 or len(set(ids)) != len(ids):
             raise ValueError("category_ids must be non-empty and distinct, got %s" % ids)
@@ -147,7 +154,7 @@ class DetectionEvaluator(object):
         self.category_ids = sorted(ids)   # the rows (COCOeval's p.catIds = np.unique(...))
         self.row_of = {c: r for r, c in enumerate(self.category_ids)}
         self.iou_type = iou_type
-        self.segm = iou_type == 'segm'
+        self.segm = iou_type in ('segm', 'boundary')   # what takes masks
         self.device = torch.device(device) if device is not None else None
         self.image_ids = []   # in the order added
         self._ids = set()
@@ -292,7 +299,7 @@ class DetectionEvaluator(object):
         size, masks = self._image_size(image_size), None
         if self.segm:
             if det_masks is None:
-                raise ValueError("iou_type 'segm' needs det_masks")
+                raise ValueError("iou_type %r needs det_masks" % self.iou_type)
             masks = _tensor(det_masks, 'det_masks', 4, (torch.float32,))
             C, M1, M2 = masks.shape[1:]
             if masks.shape[0] != n or M1 != M2 or not 2 <= M1 <= 32 or not (C == 1 or C >= len(self.class_category_ids) + 1):
@@ -356,7 +363,7 @@ class DetectionEvaluator(object):
         if not self.segm:
             return (1, 1) if size is None else tuple(int(v) for v in size)
         if size is None or len(size) != 2:
-            raise ValueError("iou_type 'segm' needs image_size = (H, W)")
+            raise ValueError("iou_type %r needs image_size = (H, W)" % self.iou_type)
         H, W = (int(v) for v in size)
         if H < 1 or W < 1 or H * W >= 1 << 31:
             raise ValueError("image size %dx%d out of range" % (H, W))
@@ -370,8 +377,12 @@ class DetectionEvaluator(object):
     def _launch_on_device(self, image_id, g, n, xyxy, score, cls, size, box_f32, masks, trans, trans_off):
         H, W = size
         K = len(self.category_ids)
+        dilation = checked_dilation(H, W, self.dilation_ratio) if self.boundary else 0
         st = self._reserve(n)
-        nbytes = int(lib().upsnet_det_eval_image_workspace_bytes(n, K, g['n'], H, W, int(self.segm)))
+        if self.boundary:
+            nbytes = int(lib().upsnet_det_eval_boundary_image_workspace_bytes(n, K, g['n'], H, W))
+        else:
+            nbytes = int(lib().upsnet_det_eval_image_workspace_bytes(n, K, g['n'], H, W, int(self.segm)))
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
         up = self._upload
         gt_row_off, gt_area, gt_crowd = up(g['row_off'], np.int32), up(g['area'], np.float64), up(g['crowd'], np.int32)
@@ -404,13 +415,21 @@ class DetectionEvaluator(object):
             keep += [det_trans, det_off, gt_trans, gt_off, gt_dst] + u8
         rec = st['rec']
         o = self._n_rec
-        check(lib().upsnet_det_eval_image(
-            stream(), int(self.segm), H, W, K, n, ptr(xyxy) if not self.segm else None, ptr(score), ptr(cls), ptr(st['lut']),
-            st['lut'].numel(), ptr(box_f32), ptr(masks), C, Ms, ptr(det_trans), ptr(det_off), g['n'], ptr(gt_row_off), ptr(gt_box), ptr(gt_area),
-            ptr(gt_crowd), ptr(gt_trans), ptr(gt_off), ptr(gt_dst), n_rle, ctypes.cast(u8_ptrs, ctypes.c_void_p) if n_u8 else None,
-            ctypes.cast(u8_dst, ctypes.c_void_p) if n_u8 else None, n_u8, ptr(rows), len(g['rows_with_gt']), ptr(st['params']),
-            self.num_images, ptr(ws), ptr(rec['score'][o:]), ptr(rec['img'][o:]), ptr(rec['rk'][o:]), ptr(rec['match'][o:]),
-            ptr(rec['ign'][o:]), ptr(st['npig'])), "det_eval_image")
+        u8_p = ctypes.cast(u8_ptrs, ctypes.c_void_p) if n_u8 else None
+        u8_d = ctypes.cast(u8_dst, ctypes.c_void_p) if n_u8 else None
+        recs = (ptr(rec['score'][o:]), ptr(rec['img'][o:]), ptr(rec['rk'][o:]), ptr(rec['match'][o:]), ptr(rec['ign'][o:]), ptr(st['npig']))
+        if self.boundary:
+            check(lib().upsnet_det_eval_boundary_image(
+                stream(), dilation, H, W, K, n, ptr(score), ptr(cls), ptr(st['lut']), st['lut'].numel(), ptr(box_f32), ptr(masks), C, Ms,
+                ptr(det_trans), ptr(det_off), g['n'], ptr(gt_row_off), ptr(gt_area), ptr(gt_crowd), ptr(gt_trans), ptr(gt_off), ptr(gt_dst),
+                n_rle, u8_p, u8_d, n_u8, ptr(rows), len(g['rows_with_gt']), ptr(st['params']), self.num_images, ptr(ws), *recs),
+                "det_eval_boundary_image")
+        else:
+            check(lib().upsnet_det_eval_image(
+                stream(), int(self.segm), H, W, K, n, ptr(xyxy) if not self.segm else None, ptr(score), ptr(cls), ptr(st['lut']),
+                st['lut'].numel(), ptr(box_f32), ptr(masks), C, Ms, ptr(det_trans), ptr(det_off), g['n'], ptr(gt_row_off), ptr(gt_box),
+                ptr(gt_area), ptr(gt_crowd), ptr(gt_trans), ptr(gt_off), ptr(gt_dst), n_rle, u8_p, u8_d, n_u8, ptr(rows),
+                len(g['rows_with_gt']), ptr(st['params']), self.num_images, ptr(ws), *recs), "det_eval_image")
         del keep   # the caching allocator orders the reuse of these blocks after the queued launches
         self._n_rec += n
         self.image_ids.append(image_id)
@@ -421,6 +440,8 @@ class DetectionEvaluator(object):
     def __iadd__(self, other):
         if other.class_category_ids != self.class_category_ids or other.iou_type != self.iou_type:
             raise ValueError("cannot merge evaluators of different category_ids / iou_type")
+        if other.dilation_ratio != self.dilation_ratio:
+            raise ValueError("cannot merge boundary evaluators of different dilation_ratio (%r, %r)" % (self.dilation_ratio, other.dilation_ratio))
         dup = self._ids & other._ids
         if dup:
             raise ValueError("image_ids %s added to both evaluators" % sorted(dup)[:8])

@@ -4,7 +4,7 @@
     python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
                                   [--eval_proposals] [--eval_instances] [--write_panoptic [--panoptic_categories <json>]]
                                   [--eval_pixels] [--write_ssegs [--ssegs_label_ids]] [--vis_mask]
-                                  [--write_instances [--instances_1bit]]
+                                  [--write_instances [--instances_1bit]] [--eval_boundary [--boundary_dilation_ratio R]]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
     python -m upsnet_amd.evaluate --cfg <yaml> --score_instances <folder>
@@ -19,6 +19,8 @@ path, keys and nesting (numpy objects only); evaluation follows the reference's 
 `--eval_only` re-scores the pickle without building the model. `--pan_combined` also scores get_combined_pan_result (the
 heuristic merge of the detections and the semantic map) next to the unified result. `--eval_proposals` keeps the RPN proposals
 of every image (results['all_proposals'], original image scale) and scores their recall (metrics['proposal_ar']).
+`--eval_boundary` (a mask head) also scores the instance masks with Boundary AP (metrics['boundary_ap'], 12 stats; boundaries of width
+`--boundary_dilation_ratio` x the image diagonal, default 0.02; dataset/boundary.py), written to results/boundary_results.txt.
 `--eval_instances` (Cityscapes with a mask head) also scores the instance masks with the Cityscapes instance-level AP against the
 gtFine instanceIds maps (metrics['instance_ap'], dataset/cityscapes_eval.py). `--write_panoptic` writes the panoptic predictions in
 COCO panoptic format under the reference's paths, results/pans_unified/{pan_2ch,pan,pred.json,gt.json} (and results/pans_combined/...
@@ -188,7 +190,7 @@ def ssegs_folder(results_dir, label_ids):
 
 def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False, write_panoptic=False,
                      panoptic_categories=None, eval_pixels=False, write_ssegs=False, ssegs_label_ids=False, write_instances=False,
-                     instances_1bit=False):
+                     instances_1bit=False, eval_boundary=False, boundary_dilation_ratio=0.02):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
     'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
@@ -198,7 +200,8 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
     IoU / iIoU); write_ssegs writes the semantic predictions to results_dir/ssegs (palette PNGs of train ids) or, with
     ssegs_label_ids, to results_dir/ssegs_label_ids (grey PNGs of label ids), with or without ground truth. write_instances writes
     the instance predictions in the Cityscapes benchmark format to results_dir/inst_seg (Cityscapes.write_instance_result; mask PNGs
-    of bit depth 1 with instances_1bit), with or without ground truth."""
+    of bit depth 1 with instances_1bit), with or without ground truth. eval_boundary adds 'boundary_ap' (the 12 stats of Boundary AP
+    at boundary_dilation_ratio, BaseDataset.evaluate_boundary) after the mask AP."""
     net = config.network
     metrics = {}
     if write_ssegs:
@@ -218,6 +221,10 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
         metrics['box_ap'] = dataset.evaluate_boxes(results['all_boxes'], results_dir)
     if net.has_rcnn and net.has_mask_head:
         metrics['mask_ap'] = dataset.evaluate_masks(results['all_boxes'], results['all_masks'], results_dir).stats
+    if eval_boundary:
+        logger.info('boundary result:')
+        metrics['boundary_ap'] = dataset.evaluate_boundary(results['all_boxes'], results['all_masks'], results_dir,
+                                                           dilation_ratio=boundary_dilation_ratio).stats
     if net.has_panoptic_head:
         logger.info('unified pano result:')
         pans = panoptic_predictions(dataset, results, False, dataset.panoptic_order())
@@ -284,6 +291,17 @@ def main(argv=None):
         raise SystemExit('--eval_instances scores instance masks against the Cityscapes gtFine instanceIds maps: it needs '
                          'dataset.dataset = Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
                          % (config.dataset.dataset, net.has_rcnn, net.has_mask_head))
+    if args.eval_boundary and not (net.has_rcnn and net.has_mask_head):
+        raise SystemExit('--eval_boundary scores the instance masks with Boundary AP: it needs network.has_rcnn and has_mask_head '
+                         '(has_rcnn=%s, has_mask_head=%s)' % (net.has_rcnn, net.has_mask_head))
+    if args.boundary_dilation_ratio is not None and not args.eval_boundary:
+        raise SystemExit('--boundary_dilation_ratio sets the boundary width of --eval_boundary, which is missing')
+    if args.eval_boundary:
+        from .dataset.boundary import check_dilation_ratio
+        try:
+            check_dilation_ratio(0.02 if args.boundary_dilation_ratio is None else args.boundary_dilation_ratio)
+        except ValueError as e:
+            raise SystemExit('--boundary_dilation_ratio: %s' % e)
     if args.write_instances and not (config.dataset.dataset == 'Cityscapes' and net.has_rcnn and net.has_mask_head):
         raise SystemExit('--write_instances writes the instance masks in the Cityscapes benchmark format: it needs dataset.dataset = '
                          'Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
@@ -311,6 +329,7 @@ def main(argv=None):
                          '(has_panoptic_head=%s)' % net.has_panoptic_head)
     if args.score_panoptic_folder and not args.score_panoptic:
         raise SystemExit('--score_panoptic_folder names the PNG folder of --score_panoptic <pred.json>, which is missing')
+    boundary_ratio = 0.02 if args.boundary_dilation_ratio is None else args.boundary_dilation_ratio
     out_dir = final_output_path(args.cfg)
     if args.score_panoptic:
         if not os.path.isfile(args.score_panoptic):
@@ -363,11 +382,11 @@ def main(argv=None):
             vis_files = draw_results(dataset, results, results_dir)
             return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                                  args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                                 args.ssegs_label_ids, args.write_instances, args.instances_1bit),
+                                                 args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio),
                     'results_file': results_file, 'times': None, 'vis_files': vis_files}
         return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit),
+                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio),
                 'results_file': results_file, 'times': None}
 
     dataset = build_dataset(out_dir)
@@ -395,7 +414,7 @@ def main(argv=None):
         return {'metrics': {}, 'results_file': results_file, 'times': times, 'vis_files': draw_results(dataset, results, results_dir)}
     return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit),
+                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio),
             'results_file': results_file, 'times': times}
 
 
