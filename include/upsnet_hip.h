@@ -1024,6 +1024,44 @@ int upsnet_group_norm_small_nhwc_f32(void *stream, const float *x, float *out, i
 int upsnet_cs_inst_expand(void *stream, const int *trans, const int *trans_off, int num_masks, int height, int width, int bits,
                           unsigned char *out);
 
+/* ============================== Test-time augmentation: the merge step ============================== */
+
+/* Multi-scale / flip test-time augmentation, csrc/tta.hip. An augmentation a has im_info (Hr_a, Wr_a, s_a); q_a = s_a / s_0 and
+ * r_a = s_0 / s_a (float32 divisions made by the caller; augmentation 0 is the base). All arithmetic is float32 in the order DESIGN
+ * 4.18 writes it. The geometry arrays (sizes, q / r, resized widths Wr_a as floats, flip flags) are HOST arrays of num_aug entries and
+ * travel by value with the launch; 1 <= num_aug <= 8. Outputs are caller-allocated; nothing is synchronised or allocated; every index
+ * is clamped to its array.
+ *
+ * upsnet_tta_seg_merge: maps[a] channels-last [map_h[a]][map_w[a]][num_seg] semantic scores, cell = 4 (quarter-resolution score map)
+ *   or 1 (full resolution). out [height][width][num_seg] (the base map's shape):
+ *   out = (((sample_0 + sample_1) + ...) + sample_{A-1}) / A, sample_a the bilinear sample (half-pixel centres, clamped to the map) of
+ *   maps[a] at ((y + 0.5) q_a - 0.5, (x + 0.5) q_a - 0.5), or for a flipped augmentation at column (Wr_a / cell - (x + 0.5) q_a) - 0.5.
+ *   One launch, one store per element; 16-byte accesses when num_seg % 4 == 0 and every base is 16-byte aligned, scalar otherwise. */
+int upsnet_tta_seg_merge(void *stream, int num_aug, const float *const maps[], const int map_h[], const int map_w[], const float q[],
+                         const float resized_w[], const int flip[], int cell, int num_seg, int height, int width, float *out);
+
+/* upsnet_tta_roi_union: per augmentation rois[a] [capacity,5], delta[a] [capacity,delta_dim], prob[a] [capacity,num_classes] and the
+ *   DEVICE count num_rois_dev[a] (int32, clamped to 0..capacity). The valid rows of augmentation a, in their order, go to rows
+ *   sum_{b<a} n_b ... of rois_out [num_aug*capacity,5], delta_out, prob_out; *num_out = sum n_a; rows past it are zero. Flipped:
+ *   x1f = (Wr_a - 1) - x2, x2f = (Wr_a - 1) - x1 and every dx (delta column 4c) negated. Then x1' = r x1, y1' = r y1,
+ *   x2' = r x2 + (r - 1), y2' = r y2 + (r - 1). The prefix over the counts is computed in the kernel: no host read.
+ *   num_aug * capacity <= 8192 (the capacity of upsnet_mask_roi); delta_dim % 4 == 0. */
+int upsnet_tta_roi_union(void *stream, int num_aug, const float *const rois[], const float *const delta[], const float *const prob[],
+                         const int *const num_rois_dev[], const float r[], const float resized_w[], const int flip[], int capacity,
+                         int delta_dim, int num_classes, float *rois_out, float *delta_out, float *prob_out, int *num_out);
+
+/* upsnet_tta_boxes_to_aug: boxes [num_boxes,5] of the base frame -> boxes_out [num_aug][num_boxes][5], the inverse rule:
+ *   x1' = q x1, y1' = q y1, x2' = q x2 + (q - 1), y2' = q y2 + (q - 1), then the flip. Column 0 is copied. num_boxes = 0 launches
+ *   nothing. */
+int upsnet_tta_boxes_to_aug(void *stream, int num_aug, const float q[], const float resized_w[], const int flip[], const float *boxes,
+                            int num_boxes, float *boxes_out);
+
+/* upsnet_tta_mask_merge: logits[a] and out share one dense layout, [num_rois][num_classes][ms][ms] (nhwc = 0) or
+ *   [num_rois][ms][ms][num_classes] (nhwc = 1): out = (((L_0 + L_1) + ...) + L_{A-1}) / A, a flipped augmentation read at column
+ *   ms - 1 - x. num_rois = 0 launches nothing. */
+int upsnet_tta_mask_merge(void *stream, int num_aug, const float *const logits[], const int flip[], int num_rois, int num_classes,
+                          int mask_size, int nhwc, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,10 @@ _SIGNATURES = {
     "upsnet_group_norm_nhwc_f32": (c_int, [P, c_int, P, P, P, P, P, c_int, P, P, c_float, c_int, P, P, P, c_int, P]),
     "upsnet_group_norm_small_nhwc_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, c_float, c_int]),
     "upsnet_cs_inst_expand": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    "upsnet_tta_seg_merge": (c_int, [P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "upsnet_tta_roi_union": (c_int, [P, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
+    "upsnet_tta_boxes_to_aug": (c_int, [P, c_int, P, P, P, P, c_int, P]),
+    "upsnet_tta_mask_merge": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
 }
 
 _lib = None

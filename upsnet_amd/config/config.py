@@ -84,6 +84,10 @@ config.test.batch_size = 1
 config.test.scales = [1024]
 config.test.max_size = 2048
 config.test.vis_mask = False          # upsnet_end2end_test.py:172-173, 300-301: draw the detections instead of scoring them
+# multi-scale / flip test-time augmentation (upsnet_amd/tta.py; the reference reads scales[0] only): further target sizes
+# beside scales[0], and whether every scale is also run mirrored left to right. Both off: the plain single-scale forward.
+config.test.aug_scales = []
+config.test.aug_flip = False
 
 
 def _merge(dst, src):

@@ -65,11 +65,20 @@ def parse_args(description='', argv=None):
     parser.add_argument('--vis_mask', action='store_true',
                         help='sets config.test.vis_mask: draw the detections of score >= 0.5 over every image into results/vis (one PNG '
                         'per image); in a run instead of the evaluation, with --eval_only before it, as the reference does')
+    parser.add_argument('--aug_scales', type=int, nargs='+', default=None, metavar='S',
+                        help='sets config.test.aug_scales: test-time augmentation, further target sizes beside test.scales[0] (the '
+                        'max size scales along); merged on the device')
+    parser.add_argument('--aug_flip', action='store_true',
+                        help='sets config.test.aug_flip: test-time augmentation, every scale also mirrored left to right')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)
     if args.vis_mask:
         config.test.vis_mask = True
+    if args.aug_scales is not None:
+        config.test.aug_scales = list(args.aug_scales)
+    if args.aug_flip:
+        config.test.aug_flip = True
     if rest:    # (the reference re-parses strictly, parse_args.py:32; an option neither parser knows is reported, not swallowed)
         parser.error('unrecognized arguments: %s' % ' '.join(rest))
     return args

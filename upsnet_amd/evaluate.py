@@ -5,6 +5,7 @@
                                   [--eval_proposals] [--eval_instances] [--write_panoptic [--panoptic_categories <json>]]
                                   [--eval_pixels] [--write_ssegs [--ssegs_label_ids]] [--vis_mask]
                                   [--write_instances [--instances_1bit]] [--eval_boundary [--boundary_dilation_ratio R]]
+                                  [--aug_scales S [S ...]] [--aug_flip]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
     python -m upsnet_amd.evaluate --cfg <yaml> --score_instances <folder>
@@ -37,7 +38,11 @@ bit depth 1 with `--instances_1bit`; dataset/cityscapes_inst_format.py), also fo
 `--score_instances <folder>` scores such a folder, or another tool's, without building the model (metrics['instance_ap']). `--vis_mask` (or `test.vis_mask: true` in the yaml; needs a mask head) draws the detections
 of score >= 0.5 over every image into results/vis, one PNG per image (BaseDataset.vis_all_mask, dataset/vis.py), with the reference's
 control flow: a run writes the pickle, draws and skips the evaluation (upsnet_end2end_test.py:300-301); with `--eval_only` the drawing
-comes first and the evaluation follows (:172-173), and the images must be on disk. One rank only (WORLD_SIZE > 1 is refused)."""
+comes first and the evaluation follows (:172-173), and the images must be on disk. `--aug_scales S [S ...]` and `--aug_flip` (or
+`test.aug_scales` / `test.aug_flip` in the yaml) turn on multi-scale / flip test-time augmentation (upsnet_amd/tta.py): every
+image runs once per augmentation, eagerly and with one image in flight, the results are merged on the device in the base frame, and the
+results pickle also carries 'test_aug', the augmentation list; `--eval_proposals` is refused with it (there is no single proposal list).
+One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
 import pickle
@@ -114,7 +119,7 @@ def post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_p
 def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False):
     """The test loop over the whole image list. Returns (results dict as pickled, per-image timings). keep_proposals: also
     results['all_proposals'] (model.keep_proposals is set for the run)."""
-    from .dataset.blob import get_image_blob
+    from .dataset.blob import blob_geometry, get_image_blob
     net = config.network
     n, num_classes = len(dataset), dataset.num_classes
     all_boxes = [[] for _ in range(num_classes)]
@@ -122,10 +127,16 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
     all_ssegs = [] if net.has_fcn_head else None
     all_panos, all_pano_cls_inds = ([], []) if net.has_panoptic_head else (None, None)
     all_proposals = [] if keep_proposals else None
+    from .tta import augmentation_enabled, augmentation_list
+    test_aug = augmentation_list() if augmentation_enabled() else None
+    if test_aug is not None and keep_proposals:
+        raise ValueError('keep_proposals with test-time augmentation: there is no single proposal list to keep')
     if keep_proposals:
         model.keep_proposals = True
     depth = max(1, min(int(in_flight), getattr(model, 'graph_slots', 1))) if hasattr(model, 'forward_async') else 1
     launch = model.forward_async if depth > 1 else model
+    if test_aug is not None:     # one forward per augmentation of the decoded image, eagerly, one image in flight
+        depth = 1
     workers = max(1, min(MAX_DECODE_THREADS, n))     # (never sized from the host's CPU count)
     ahead = 2 * workers                               # images decoded ahead of the device
     times = {'data_time': [], 'net_time': [], 'post_time': []}
@@ -154,10 +165,18 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
             if i + ahead < n:
                 decoded[i + ahead] = pool.submit(dataset.load_image, i + ahead)
             t0 = time.perf_counter()
-            data = get_image_blob(decoded.pop(i).result(), device=device)
-            t1 = time.perf_counter()
-            handle = launch({'data': data['data'], 'im_info': data['im_info']})
-            pending.append((i, handle, data['im_info'][0], t1 - t0, time.perf_counter() - t1))
+            image = decoded.pop(i).result()
+            if test_aug is not None:     # (forward_tta builds every augmentation's blob itself; the outputs are in the base frame)
+                im_scale, resized, _ = blob_geometry(image.shape[0], image.shape[1], config.test.scales[0], config.test.max_size)
+                im_info = np.array([[resized[0], resized[1], im_scale]], dtype=np.float32)
+                t1 = time.perf_counter()
+                handle = model.forward_tta(image, device=device)
+            else:
+                data = get_image_blob(image, device=device)
+                im_info = data['im_info']
+                t1 = time.perf_counter()
+                handle = launch({'data': data['data'], 'im_info': data['im_info']})
+            pending.append((i, handle, im_info[0], t1 - t0, time.perf_counter() - t1))
             if len(pending) >= depth:
                 finish(*pending.pop(0))
         while pending:
@@ -166,6 +185,8 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
                'all_pano_cls_inds': all_pano_cls_inds}
     if keep_proposals:
         results['all_proposals'] = all_proposals
+    if test_aug is not None:
+        results['test_aug'] = [list(a) for a in test_aug]
     return results, times
 
 
@@ -311,6 +332,15 @@ def main(argv=None):
     if args.score_instances and config.dataset.dataset != 'Cityscapes':     # (no model is built: the heads do not matter)
         raise SystemExit('--score_instances scores instance prediction files against the Cityscapes gtFine instanceIds maps: it needs '
                          'dataset.dataset = Cityscapes (dataset=%s)' % config.dataset.dataset)
+    from .tta import augmentation_enabled, augmentation_list
+    if augmentation_enabled() and not (args.eval_only or args.score_panoptic or args.score_ssegs or args.score_instances):
+        if args.eval_proposals:
+            raise SystemExit('--eval_proposals with test-time augmentation (--aug_scales / --aug_flip) is refused: the detections come from '
+                             'the union of every augmentation\'s proposals, so there is no single proposal list to score')
+        try:
+            augmentation_list()
+        except ValueError as e:
+            raise SystemExit('--aug_scales / --aug_flip: %s' % e)
     vis_mask = bool(config.test.get('vis_mask', False))
     if vis_mask and not (net.has_rcnn and net.has_mask_head):
         raise SystemExit('--vis_mask (config.test.vis_mask) draws the detections and their instance masks: it needs network.has_rcnn and '

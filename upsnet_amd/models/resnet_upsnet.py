@@ -209,6 +209,12 @@ class resnet_upsnet(resnet_rcnn):
             return _Pending(self, data, None, self._forward_fused(data, st=None if ent is None else ent['out'], try_graph=False))
         return _Pending(self, data, None, self.forward(data))
 
+    def forward_tta(self, image_u8_bgr, device=None, return_parts=False):
+        """Multi-scale / flip test-time augmentation of one decoded uint8 BGR image (config.test.aug_scales / aug_flip), merged on the
+        device: upsnet_amd/tta.py, DESIGN 4.18. Returns forward()'s output dict in the base frame."""
+        from ..tta import forward_tta
+        return forward_tta(self, image_u8_bgr, device=device, return_parts=return_parts)
+
     # ------------------------------------------------------------------ MI355X pipeline
     def _phase1(self, x, im_info, tail=False):
         """Everything up to the first host read (static shapes: fixed-capacity ROI / detection buffers + device counters), on the

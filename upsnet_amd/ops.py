@@ -1806,3 +1806,31 @@ def panoptic_semantic(rgb, segments_info):
     channel 0 of csrc/pan_format.hip's relabel kernel."""
     from .dataset import gt_prepare as impl
     return impl.panoptic_semantic(rgb, segments_info)
+
+
+# ----------------------------------------------------------------------------- test-time augmentation: the merge step (csrc/tta.hip)
+TTA_MAX_AUG = 8
+
+
+def tta_seg_merge(maps, q, resized_w, flip, cell):
+    """tta.py: the semantic score maps of the augmentations resampled into the frame of maps[0] and averaged."""
+    from . import tta as impl
+    return impl.seg_merge(maps, q, resized_w, flip, cell)
+
+
+def tta_roi_union(rois, delta, prob, num_rois_dev, r, resized_w, flip):
+    """tta.py: every augmentation's valid proposal rows, mapped to the base frame and packed behind each other."""
+    from . import tta as impl
+    return impl.roi_union(rois, delta, prob, num_rois_dev, r, resized_w, flip)
+
+
+def tta_boxes_to_aug(boxes, q, resized_w, flip):
+    """tta.py: boxes of the base frame mapped into every augmentation's frame, [A,n,5]."""
+    from . import tta as impl
+    return impl.boxes_to_aug(boxes, q, resized_w, flip)
+
+
+def tta_mask_merge(logits, flip):
+    """tta.py: the augmentations' mask logits averaged, flipped ones mirrored left to right."""
+    from . import tta as impl
+    return impl.mask_merge(logits, flip)
