@@ -735,6 +735,26 @@ int upsnet_pq_accumulate(void *stream, const unsigned char *pred_2ch, const unsi
                          const int64_t *segments, int num_segments, const unsigned char *cat_known, int image_index, int max_gt,
                          void *workspace, int64_t *tp, int64_t *fp, int64_t *fn, double *iou, uint64_t *status);
 
+/* Boundary PQ (Cheng et al., Boundary IoU, CVPR 2021; csrc/pq_boundary.hip): upsnet_pq_accumulate with every pair scored by
+ * min(mask IoU, boundary IoU). A pixel of a label map is interior iff the (2 * dilation + 1)^2 window centred on it lies inside the
+ * image and holds the pixel's own label throughout; its boundary bit is "not interior" (every pixel when 2 * dilation + 1 exceeds the
+ * height or the width). Labels: GT the 24-bit PNG id, pred cat << 8 | inst with all cat == 255 pixels one VOID label. dilation >= 1 is
+ * upsnet_amd.dataset.boundary.boundary_dilation(height, width, ratio) on the host; there is no upper limit.
+ * upsnet_pan_boundary_map: out_bits uint8 [H,W], bit 0 = GT boundary, bit 1 = pred boundary, every byte written; either map, not both, may
+ * be NULL (its bit stays 0). workspace: upsnet_pan_boundary_workspace_bytes(height, width) bytes, no zeroing, no alignment. Two launches
+ * (one when the window exceeds the image).
+ * upsnet_pq_boundary_accumulate: all other arguments as upsnet_pq_accumulate. workspace: upsnet_pq_boundary_workspace_bytes(max_gt,
+ * height, width) bytes (0 for arguments out of range; a workspace sized for a larger image serves a smaller one), 16-byte aligned,
+ * ZEROED ONCE before its first use; every call leaves its count areas zeroed again. Five launches on `stream`, no host synchronisation,
+ * no allocation. Non-zero return (upsnet_last_error) before anything is launched: null pointers, non-positive sizes, dilation < 1. */
+size_t upsnet_pan_boundary_workspace_bytes(int height, int width);
+int upsnet_pan_boundary_map(void *stream, int dilation, const unsigned char *pred_2ch, const unsigned char *gt_rgb, int height, int width,
+                            void *workspace, unsigned char *out_bits);
+size_t upsnet_pq_boundary_workspace_bytes(int max_gt, int height, int width);
+int upsnet_pq_boundary_accumulate(void *stream, int dilation, const unsigned char *pred_2ch, const unsigned char *gt_rgb, int height,
+                                  int width, const int64_t *segments, int num_segments, const unsigned char *cat_known, int image_index,
+                                  int max_gt, void *workspace, int64_t *tp, int64_t *fp, int64_t *fn, double *iou, uint64_t *status);
+
 /* BaseDataset.get_confusion_matrix (upsnet/dataset/base_dataset.py:806-824) added into confusion int64 [class_num, class_num]:
  * for every pixel with gt_label != ignore_label (ignore_label = -1: no pixel dropped), index = gt * class_num + pred, counted iff
  * index < class_num^2 -- a pred value >= class_num therefore aliases into another cell, as np.bincount does in the reference.

@@ -127,6 +127,10 @@ _SIGNATURES = {
     "upsnet_panoptic_argmax": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P]),
     "upsnet_pq_workspace_bytes": (c_size_t, [c_int]),
     "upsnet_pq_accumulate": (c_int, [P, P, P, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, P, P, P]),
+    "upsnet_pan_boundary_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "upsnet_pan_boundary_map": (c_int, [P, c_int, P, P, c_int, c_int, P, P]),
+    "upsnet_pq_boundary_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "upsnet_pq_boundary_accumulate": (c_int, [P, c_int, P, P, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, P, P, P]),
     "upsnet_restore_label_maps": (c_int, [P, P, P, c_long, c_int, c_int, P, c_int, P, c_int, P, P]),
     "upsnet_confusion_accumulate": (c_int, [P, P, P, c_long, c_int, c_int, P]),
     "upsnet_det_eval_image_workspace_bytes": (c_size_t, [c_int] * 6),

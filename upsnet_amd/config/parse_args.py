@@ -27,6 +27,11 @@ def parse_args(description='', argv=None):
                         'a mask head')
     parser.add_argument('--boundary_dilation_ratio', type=float, default=None, metavar='R',
                         help='with --eval_boundary: the boundary width as a fraction of the image diagonal (default 0.02)')
+    parser.add_argument('--eval_boundary_pq', action='store_true',
+                        help='also score every panoptic result with Boundary PQ (PQ with IoU = min(mask IoU, boundary IoU)); needs a '
+                        'panoptic head or --pan_combined; with --score_panoptic the prediction files are scored with both')
+    parser.add_argument('--boundary_pq_dilation_ratio', type=float, default=None, metavar='R',
+                        help='with --eval_boundary_pq: the boundary width as a fraction of the image diagonal (default 0.02)')
     parser.add_argument('--eval_instances', action='store_true',
                         help='Cityscapes only: also score the instance masks with the Cityscapes instance-level AP / AP50% '
                         '(the gtFine instanceIds maps are read)')

@@ -150,6 +150,18 @@ class BaseDataset(object):
             ev.add(pred, gt, ann['segments_info'])
         return ev.summary()
 
+    def evaluate_panoptic_boundary(self, pred_pans_2ch, output_dir, dilation_ratio=0.02, max_gt_segments=4096):
+        """evaluate_panoptic with Boundary PQ (PanopticEvaluator(boundary=True): every pair scored by min(mask IoU, boundary IoU),
+        boundaries of width dilation_ratio x the image diagonal). Same dict shape; writes nothing to output_dir."""
+        from .pq import PanopticEvaluator
+        images, annotations, categories = self.load_panoptic_gt()
+        if len(pred_pans_2ch) != len(annotations):
+            raise ValueError("%d predictions for %d GT annotations" % (len(pred_pans_2ch), len(annotations)))
+        ev = PanopticEvaluator(categories, max_gt_segments=max_gt_segments, boundary=True, dilation_ratio=dilation_ratio)
+        for pred, gt, ann in zip(pred_pans_2ch, images, annotations):
+            ev.add(pred, gt, ann['segments_info'])
+        return ev.summary()
+
     def write_panoptic(self, pred_pans_2ch, output_dir, categories=None, categories_json=None):
         """The files of the reference's evaluate_panoptic (:321-327): output_dir/pan_2ch/*.png, pan/*.png, pred.json and -- with ground
         truth -- gt.json (dataset/pan_format.write_panoptic: colours, naming, deviations). With ground truth the predictions are
@@ -185,10 +197,11 @@ class BaseDataset(object):
         logger.info('%d panoptic predictions written to %s', len(annotations), os.path.abspath(output_dir))
         return annotations
 
-    def evaluate_panoptic_files(self, pred_json, pred_folder, max_gt_segments=4096):
+    def evaluate_panoptic_files(self, pred_json, pred_folder, max_gt_segments=4096, boundary=False, dilation_ratio=0.02):
         """PQ / SQ / RQ of a prediction in COCO panoptic format (pred_json with its PNG folder: write_panoptic's output, or any other
         tool's) against the panoptic GT, through PanopticEvaluator.add_png. Annotations are paired with the GT by image_id;
-        ValueError if an image of the GT has no prediction, or a prediction no GT image, or an image id occurs twice."""
+        ValueError if an image of the GT has no prediction, or a prediction no GT image, or an image id occurs twice.
+        boundary=True scores Boundary PQ at dilation_ratio instead (evaluate_panoptic_boundary)."""
         from .pq import PanopticEvaluator
         with open(pred_json, 'r') as f:
             pred_anns = json.load(f)['annotations']
@@ -204,7 +217,10 @@ class BaseDataset(object):
         if missing or surplus:
             raise ValueError("%s does not cover the ground truth: %d GT images without a prediction (first: %s), %d predictions without "
                              "a GT image (first: %s)" % (pred_json, len(missing), missing[:3], len(surplus), surplus[:3]))
-        ev = PanopticEvaluator(categories, max_gt_segments=max_gt_segments)
+        if boundary:
+            ev = PanopticEvaluator(categories, max_gt_segments=max_gt_segments, boundary=True, dilation_ratio=dilation_ratio)
+        else:
+            ev = PanopticEvaluator(categories, max_gt_segments=max_gt_segments)
         for gt, ann in zip(images, annotations):
             pred = preds[ann['image_id']]
             ev.add_png(load_panoptic_png(os.path.join(pred_folder, pred['file_name'])), pred['segments_info'], gt, ann['segments_info'])

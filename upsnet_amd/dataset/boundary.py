@@ -96,3 +96,31 @@ def mask_to_boundary(masks, dilation_ratio=0.02, size=None, device=None):
         check(lib().upsnet_boundary_masks(stream(), d, H, W, n, ptr(src), ptr(trans), ptr(off), ptr(ws), ptr(out), ptr(area)),
               "boundary_masks")
     return out
+
+
+def panoptic_boundary(pred_2ch=None, gt_rgb=None, ratio=0.02):
+    """The boundary bits of panoptic label maps (csrc/pq_boundary.hip; the bits Boundary PQ counts, dataset/pq.py): pred_2ch and / or
+    gt_rgb uint8 [H,W,3] device tensors of one shape -> uint8 [H,W], bit 0 = GT boundary, bit 1 = pred boundary (0 for a map not given).
+    d = boundary_dilation(H, W, ratio); a pixel is boundary unless the (2d+1) x (2d+1) window centred on it lies inside the image and
+    holds the pixel's own label (GT: R + 256 G + 65536 B; pred: cat * 256 + inst, every cat == 255 pixel one VOID label), so that
+    boundary & (label == s) is mask_to_boundary(label == s) for every segment s. Any d >= 1 is accepted. ValueError before any launch:
+    a bad ratio, no map, wrong shapes or dtypes, host tensors. A non-contiguous view is copied."""
+    from .. import ops
+    check_dilation_ratio(ratio)
+    maps = [m for m in (pred_2ch, gt_rgb) if m is not None]
+    if not maps:
+        raise ValueError("panoptic_boundary: neither pred_2ch nor gt_rgb given")
+    for m in maps:
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.uint8 or m.dim() != 3 or m.shape[2] != 3:
+            raise ValueError("panoptic_boundary: maps must be uint8 [H,W,3] tensors, got %r"
+                             % ((tuple(m.shape), m.dtype) if isinstance(m, torch.Tensor) else type(m),))
+        if not m.is_cuda:
+            raise ValueError("panoptic_boundary: maps must be device tensors (there is no CPU path)")
+        if tuple(m.shape) != tuple(maps[0].shape):
+            raise ValueError("panoptic_boundary: pred_2ch %s and gt_rgb %s differ in shape" % (tuple(maps[0].shape), tuple(m.shape)))
+    H, W = maps[0].shape[:2]
+    d = boundary_dilation(H, W, ratio)
+    dev = maps[0].device
+    ws = torch.empty((ops.pan_boundary_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    return ops.pan_boundary_map(d, pred_2ch, gt_rgb, ws, out)

@@ -56,9 +56,16 @@ class PanopticEvaluator(object):
 
     categories: the dataset's category table, {id: {'isthing': 0/1, ...}} or the JSON's list of dicts with 'id'.
     add() queues one image on the current stream (no synchronisation, no allocation after the first call); pq_stat() / summary()
-    synchronise once. `a += b` merges the evaluator of another rank (PQStat.__iadd__ semantics: a's sums plus b's)."""
+    synchronise once. `a += b` merges the evaluator of another rank (PQStat.__iadd__ semantics: a's sums plus b's).
 
-    def __init__(self, categories, device=None, max_gt_segments=4096):
+    boundary=True scores Boundary PQ (Cheng et al., Boundary IoU, CVPR 2021; csrc/pq_boundary.hip): every pair's IoU is
+    min(mask IoU, boundary IoU), the boundary bits those of dataset.boundary.panoptic_boundary at d = boundary_dilation(H, W,
+    dilation_ratio) per image, iou_b = inter_b / (area_bp + area_bg - inter_b - void_b) over pixel counts (0 when that union is empty).
+    FP absorption, FN, summation order and the result dicts are unchanged. The workspace then also holds two byte maps of the image: it
+    is allocated for the first image and again only when a larger image arrives. ValueError before any launch: a dilation_ratio that
+    is not a finite number > 0; `a += b` across different ratios or across a boundary and a plain evaluator."""
+
+    def __init__(self, categories, device=None, max_gt_segments=4096, boundary=False, dilation_ratio=0.02):
         if not isinstance(categories, dict):
             categories = {el['id']: el for el in categories}
         bad = [c for c in categories if not 0 <= int(c) <= MAX_CATEGORY]
@@ -69,6 +76,12 @@ class PanopticEvaluator(object):
         self.categories = categories
         self.device = torch.device(device) if device is not None else None
         self.max_gt_segments = int(max_gt_segments)
+        self.boundary = bool(boundary)
+        self.dilation_ratio = None
+        if self.boundary:
+            from .boundary import check_dilation_ratio
+            self.dilation_ratio = check_dilation_ratio(dilation_ratio)
+        self._ws_pixels = 0  # boundary: the image size (pixels) the workspace holds
         self.num_images = 0
         self._state = None   # device tensors, allocated at the first add
 
@@ -78,12 +91,32 @@ class PanopticEvaluator(object):
             self.device = dev
             known = np.zeros(256, np.uint8)
             known[[int(c) for c in self.categories]] = 1
-            self._state = dict(known=torch.from_numpy(known).to(dev), ws=ops.pq_workspace(self.max_gt_segments, dev),
+            self._state = dict(known=torch.from_numpy(known).to(dev),
+                               ws=None if self.boundary else ops.pq_workspace(self.max_gt_segments, dev),
                                tp=torch.zeros(256, dtype=torch.int64, device=dev), fp=torch.zeros(256, dtype=torch.int64, device=dev),
                                fn=torch.zeros(256, dtype=torch.int64, device=dev), iou=torch.zeros(256, dtype=torch.float64, device=dev),
                                status=torch.zeros(1, dtype=torch.int64, device=dev),
                                png_status=torch.zeros(2, dtype=torch.int64, device=dev))
         return self._state
+
+    def _accumulate(self, pred_2ch, gt_rgb, segs):
+        st = self._state
+        segs = torch.from_numpy(segs)
+        if torch.cuda.is_available():
+            segs = segs.pin_memory()
+        segs = segs.to(self.device, non_blocking=True)
+        if not self.boundary:
+            ops.pq_accumulate(pred_2ch, gt_rgb, segs, st['known'], self.num_images, self.max_gt_segments, st['ws'], st['tp'], st['fp'],
+                              st['fn'], st['iou'], st['status'])
+        else:
+            from .boundary import boundary_dilation
+            H, W = pred_2ch.shape[:2]
+            if H * W > self._ws_pixels:   # (the old workspace's count areas are zero by contract: nothing to carry over)
+                st['ws'] = ops.pq_boundary_workspace(self.max_gt_segments, H, W, self.device)
+                self._ws_pixels = H * W
+            ops.pq_boundary_accumulate(boundary_dilation(H, W, self.dilation_ratio), pred_2ch, gt_rgb, segs, st['known'], self.num_images,
+                                       self.max_gt_segments, st['ws'], st['tp'], st['fp'], st['fn'], st['iou'], st['status'])
+        self.num_images += 1
 
     def _upload(self, t):
         if isinstance(t, np.ndarray):
@@ -96,15 +129,9 @@ class PanopticEvaluator(object):
         _check_image('pred_2ch', pred_2ch)
         _check_image('gt_rgb', gt_rgb, pred_2ch.shape)
         segs = segments_array(segments_info, self.max_gt_segments)
-        st = self._dev_state()
+        self._dev_state()
         pred_2ch, gt_rgb = self._upload(pred_2ch), self._upload(gt_rgb)
-        segs = torch.from_numpy(segs)
-        if torch.cuda.is_available():
-            segs = segs.pin_memory()
-        segs = segs.to(self.device, non_blocking=True)
-        ops.pq_accumulate(pred_2ch, gt_rgb, segs, st['known'], self.num_images, self.max_gt_segments, st['ws'], st['tp'], st['fp'],
-                          st['fn'], st['iou'], st['status'])
-        self.num_images += 1
+        self._accumulate(pred_2ch, gt_rgb, segs)
 
     def add_png(self, pred_rgb, pred_segments_info, gt_rgb, gt_segments_info):
         """One image of a prediction in COCO panoptic format: pred_rgb uint8 [H,W,3] PNG of arbitrary ids (id = R + 256 G + 65536 B,
@@ -122,19 +149,16 @@ class PanopticEvaluator(object):
         st = self._dev_state()
         pred_rgb, gt_rgb = self._upload(pred_rgb), self._upload(gt_rgb)
         pred_2ch, _ = relabel(pred_rgb, table, self.num_images, st['png_status'])
-        segs = torch.from_numpy(segs)
-        if torch.cuda.is_available():
-            segs = segs.pin_memory()
-        segs = segs.to(self.device, non_blocking=True)
-        ops.pq_accumulate(pred_2ch, gt_rgb, segs, st['known'], self.num_images, self.max_gt_segments, st['ws'], st['tp'], st['fp'],
-                          st['fn'], st['iou'], st['status'])
-        self.num_images += 1
+        self._accumulate(pred_2ch, gt_rgb, segs)
 
     def __iadd__(self, other):
+        if (self.boundary, self.dilation_ratio) != (other.boundary, other.dilation_ratio):
+            raise ValueError("cannot merge evaluators of different rules: boundary=%s dilation_ratio=%s and boundary=%s dilation_ratio=%s"
+                             % (self.boundary, self.dilation_ratio, other.boundary, other.dilation_ratio))
         if other._state is None:
             self.num_images += other.num_images
             return self
-        st, ot = self._dev_state(), {k: v.to(self.device) for k, v in other._state.items()}
+        st, ot = self._dev_state(), {k: v.to(self.device) for k, v in other._state.items() if k != 'ws'}
         for k in ('tp', 'fp', 'fn', 'iou'):
             st[k] += ot[k]
         # the first error stays first: other's image indices follow this evaluator's

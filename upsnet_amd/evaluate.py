@@ -5,8 +5,8 @@
                                   [--eval_proposals] [--eval_instances] [--write_panoptic [--panoptic_categories <json>]]
                                   [--eval_pixels] [--write_ssegs [--ssegs_label_ids]] [--vis_mask]
                                   [--write_instances [--instances_1bit]] [--eval_boundary [--boundary_dilation_ratio R]]
-                                  [--aug_scales S [S ...]] [--aug_flip]
-    python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>]
+                                  [--eval_boundary_pq [--boundary_pq_dilation_ratio R]] [--aug_scales S [S ...]] [--aug_flip]
+    python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>] [--eval_boundary_pq ...]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
     python -m upsnet_amd.evaluate --cfg <yaml> --score_instances <folder>
 
@@ -22,6 +22,10 @@ heuristic merge of the detections and the semantic map) next to the unified resu
 of every image (results['all_proposals'], original image scale) and scores their recall (metrics['proposal_ar']).
 `--eval_boundary` (a mask head) also scores the instance masks with Boundary AP (metrics['boundary_ap'], 12 stats; boundaries of width
 `--boundary_dilation_ratio` x the image diagonal, default 0.02; dataset/boundary.py), written to results/boundary_results.txt.
+`--eval_boundary_pq` (a panoptic head, or --pan_combined) also scores every panoptic result with Boundary PQ (metrics['panoptic_boundary']
+after metrics['panoptic'], metrics['panoptic_combined_boundary'] with --pan_combined; PQ with every pair scored by min(mask IoU,
+boundary IoU), boundaries of width `--boundary_pq_dilation_ratio` x the image diagonal, default 0.02; dataset/pq.py); with
+`--score_panoptic` the prediction files are scored with both.
 `--eval_instances` (Cityscapes with a mask head) also scores the instance masks with the Cityscapes instance-level AP against the
 gtFine instanceIds maps (metrics['instance_ap'], dataset/cityscapes_eval.py). `--write_panoptic` writes the panoptic predictions in
 COCO panoptic format under the reference's paths, results/pans_unified/{pan_2ch,pan,pred.json,gt.json} (and results/pans_combined/...
@@ -211,7 +215,7 @@ def ssegs_folder(results_dir, label_ids):
 
 def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False, write_panoptic=False,
                      panoptic_categories=None, eval_pixels=False, write_ssegs=False, ssegs_label_ids=False, write_instances=False,
-                     instances_1bit=False, eval_boundary=False, boundary_dilation_ratio=0.02):
+                     instances_1bit=False, eval_boundary=False, boundary_dilation_ratio=0.02, boundary_pq_ratio=None):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
     'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
@@ -222,7 +226,9 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
     ssegs_label_ids, to results_dir/ssegs_label_ids (grey PNGs of label ids), with or without ground truth. write_instances writes
     the instance predictions in the Cityscapes benchmark format to results_dir/inst_seg (Cityscapes.write_instance_result; mask PNGs
     of bit depth 1 with instances_1bit), with or without ground truth. eval_boundary adds 'boundary_ap' (the 12 stats of Boundary AP
-    at boundary_dilation_ratio, BaseDataset.evaluate_boundary) after the mask AP."""
+    at boundary_dilation_ratio, BaseDataset.evaluate_boundary) after the mask AP. boundary_pq_ratio (not None) adds 'panoptic_boundary'
+    after 'panoptic' and 'panoptic_combined_boundary' after 'panoptic_combined': Boundary PQ of the same predictions at that ratio
+    (BaseDataset.evaluate_panoptic_boundary)."""
     net = config.network
     metrics = {}
     if write_ssegs:
@@ -250,12 +256,20 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
         logger.info('unified pano result:')
         pans = panoptic_predictions(dataset, results, False, dataset.panoptic_order())
         metrics['panoptic'] = dataset.evaluate_panoptic(pans, os.path.join(results_dir, 'pans_unified'))
+        if boundary_pq_ratio is not None:
+            logger.info('unified pano boundary result:')
+            metrics['panoptic_boundary'] = dataset.evaluate_panoptic_boundary(pans, os.path.join(results_dir, 'pans_unified'),
+                                                                              dilation_ratio=boundary_pq_ratio)
         if write_panoptic:
             dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_unified'))
     if pan_combined:
         logger.info('combined pano result:')
         pans = panoptic_predictions(dataset, results, True, dataset.panoptic_order())
         metrics['panoptic_combined'] = dataset.evaluate_panoptic(pans, os.path.join(results_dir, 'pans_combined'))
+        if boundary_pq_ratio is not None:
+            logger.info('combined pano boundary result:')
+            metrics['panoptic_combined_boundary'] = dataset.evaluate_panoptic_boundary(pans, os.path.join(results_dir, 'pans_combined'),
+                                                                                       dilation_ratio=boundary_pq_ratio)
         if write_panoptic:
             dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_combined'))
     if net.has_fcn_head:
@@ -323,6 +337,18 @@ def main(argv=None):
             check_dilation_ratio(0.02 if args.boundary_dilation_ratio is None else args.boundary_dilation_ratio)
         except ValueError as e:
             raise SystemExit('--boundary_dilation_ratio: %s' % e)
+    if args.eval_boundary_pq and not (net.has_panoptic_head or args.pan_combined or args.score_panoptic):
+        raise SystemExit('--eval_boundary_pq scores the panoptic predictions with Boundary PQ: it needs network.has_panoptic_head, or '
+                         '--pan_combined (has_panoptic_head=%s)' % net.has_panoptic_head)
+    if args.boundary_pq_dilation_ratio is not None and not args.eval_boundary_pq:
+        raise SystemExit('--boundary_pq_dilation_ratio sets the boundary width of --eval_boundary_pq, which is missing')
+    boundary_pq_ratio = None
+    if args.eval_boundary_pq:
+        from .dataset.boundary import check_dilation_ratio
+        try:
+            boundary_pq_ratio = check_dilation_ratio(0.02 if args.boundary_pq_dilation_ratio is None else args.boundary_pq_dilation_ratio)
+        except ValueError as e:
+            raise SystemExit('--boundary_pq_dilation_ratio: %s' % e)
     if args.write_instances and not (config.dataset.dataset == 'Cityscapes' and net.has_rcnn and net.has_mask_head):
         raise SystemExit('--write_instances writes the instance masks in the Cityscapes benchmark format: it needs dataset.dataset = '
                          'Cityscapes and network.has_rcnn and has_mask_head (dataset=%s, has_rcnn=%s, has_mask_head=%s)'
@@ -374,7 +400,12 @@ def main(argv=None):
             if not os.path.isfile(p):
                 raise SystemExit('--score_panoptic: no panoptic ground truth at %s' % p)
         logger.info('panoptic result of %s:', args.score_panoptic)
-        return {'metrics': {'panoptic': dataset.evaluate_panoptic_files(args.score_panoptic, folder)}, 'results_file': None, 'times': None}
+        metrics = {'panoptic': dataset.evaluate_panoptic_files(args.score_panoptic, folder)}
+        if boundary_pq_ratio is not None:
+            logger.info('panoptic boundary result of %s:', args.score_panoptic)
+            metrics['panoptic_boundary'] = dataset.evaluate_panoptic_files(args.score_panoptic, folder, boundary=True,
+                                                                           dilation_ratio=boundary_pq_ratio)
+        return {'metrics': metrics, 'results_file': None, 'times': None}
     if args.score_ssegs:
         if not os.path.isdir(args.score_ssegs):
             raise SystemExit('--score_ssegs: no folder at %s' % args.score_ssegs)
@@ -412,11 +443,13 @@ def main(argv=None):
             vis_files = draw_results(dataset, results, results_dir)
             return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                                  args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                                 args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio),
+                                                 args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio,
+                                            boundary_pq_ratio=boundary_pq_ratio),
                     'results_file': results_file, 'times': None, 'vis_files': vis_files}
         return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio),
+                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio,
+                                            boundary_pq_ratio=boundary_pq_ratio),
                 'results_file': results_file, 'times': None}
 
     dataset = build_dataset(out_dir)
@@ -444,7 +477,8 @@ def main(argv=None):
         return {'metrics': {}, 'results_file': results_file, 'times': times, 'vis_files': draw_results(dataset, results, results_dir)}
     return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
-                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio),
+                                             args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio,
+                                            boundary_pq_ratio=boundary_pq_ratio),
             'results_file': results_file, 'times': times}
 
 

@@ -1388,6 +1388,82 @@ def pq_accumulate(pred_2ch, gt_rgb, segments, cat_known, image_index, max_gt, wo
                                      ptr(fn), ptr(iou), ptr(status)), "pq_accumulate")
 
 
+def pq_boundary_workspace(max_gt, height, width, device):
+    """Zeroed workspace of pq_boundary_accumulate for images of at most max_gt GT segments (0..4096) and height x width pixels (a
+    smaller image fits too); every call leaves its count areas zeroed again."""
+    nbytes = int(lib().upsnet_pq_boundary_workspace_bytes(int(max_gt), int(height), int(width)))
+    if nbytes == 0:
+        raise ValueError("pq_boundary_workspace: max_gt %d outside 0..4096 or image size %dx%d out of range" % (max_gt, height, width))
+    return torch.zeros((nbytes,), dtype=torch.uint8, device=device)
+
+
+def pq_boundary_accumulate(dilation, pred_2ch, gt_rgb, segments, cat_known, image_index, max_gt, workspace, tp, fp, fn, iou, status):
+    """pq_accumulate with every pair scored by min(mask IoU, boundary IoU) (Boundary PQ, csrc/pq_boundary.hip): `dilation` >= 1 is the
+    boundary width d of this image (dataset.boundary.boundary_dilation); workspace from pq_boundary_workspace, at least as large as
+    this image needs. All other arguments as pq_accumulate. No host synchronisation, no allocation."""
+    require_cuda(pred_2ch, gt_rgb, segments, cat_known, workspace, tp, fp, fn, iou, status)
+    if pred_2ch.dtype != torch.uint8 or gt_rgb.dtype != torch.uint8 or pred_2ch.dim() != 3 or pred_2ch.shape[2] != 3 \
+            or tuple(pred_2ch.shape) != tuple(gt_rgb.shape):
+        raise ValueError("pq_boundary_accumulate: pred_2ch %s %s and gt_rgb %s %s must both be uint8 [H,W,3]"
+                         % (tuple(pred_2ch.shape), pred_2ch.dtype, tuple(gt_rgb.shape), gt_rgb.dtype))
+    if segments.dtype != torch.int64 or segments.dim() != 2 or segments.shape[1] != 4:
+        raise ValueError("pq_boundary_accumulate: segments must be int64 [n,4]")
+    for t, dt, n in ((cat_known, torch.uint8, 256), (tp, torch.int64, 256), (fp, torch.int64, 256), (fn, torch.int64, 256),
+                     (iou, torch.float64, 256), (status, torch.int64, 1)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise ValueError("pq_boundary_accumulate: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
+    if int(dilation) < 1:
+        raise ValueError("pq_boundary_accumulate: dilation %d < 1" % dilation)
+    H, W = pred_2ch.shape[:2]
+    need = int(lib().upsnet_pq_boundary_workspace_bytes(int(max_gt), H, W))
+    if need == 0 or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError("pq_boundary_accumulate: a uint8 workspace of at least %d bytes expected for max_gt %d and %dx%d, got %s %s"
+                         % (need, max_gt, H, W, tuple(workspace.shape), workspace.dtype))
+    pred_2ch, gt_rgb, segments = pred_2ch.contiguous(), gt_rgb.contiguous(), segments.contiguous()
+    check(lib().upsnet_pq_boundary_accumulate(stream(), int(dilation), ptr(pred_2ch), ptr(gt_rgb), H, W,
+                                              ptr(segments) if segments.numel() else None, int(segments.shape[0]), ptr(cat_known),
+                                              int(image_index), int(max_gt), ptr(workspace), ptr(tp), ptr(fp), ptr(fn), ptr(iou), ptr(status)),
+          "pq_boundary_accumulate")
+
+
+def pan_boundary_workspace_bytes(height, width):
+    """Bytes of pan_boundary_map's workspace for a height x width image (no zeroing needed); ValueError for a size out of range."""
+    nbytes = int(lib().upsnet_pan_boundary_workspace_bytes(int(height), int(width)))
+    if nbytes == 0:
+        raise ValueError("pan_boundary_map: image size %dx%d out of range" % (height, width))
+    return nbytes
+
+
+def pan_boundary_map(dilation, pred_2ch, gt_rgb, workspace, out):
+    """The boundary bits of a panoptic label map pair (csrc/pq_boundary.hip) into out uint8 [H,W] (every byte written): bit 0 = GT
+    boundary, bit 1 = pred boundary. A pixel is boundary unless the (2 * dilation + 1)^2 window centred on it lies inside the image and
+    holds the pixel's own label (GT: the PNG id; pred: cat * 256 + inst, all cat == 255 pixels one VOID label). Either map, not both,
+    may be None (its bit stays 0); workspace: uint8, at least pan_boundary_workspace_bytes(H, W). A non-contiguous map is copied.
+    No host synchronisation; dataset.boundary.panoptic_boundary allocates and calls this."""
+    maps = [m for m in (pred_2ch, gt_rgb) if m is not None]
+    if not maps:
+        raise ValueError("pan_boundary_map: neither pred_2ch nor gt_rgb given")
+    require_cuda(workspace, out, *maps)
+    for m in maps:
+        if m.dtype != torch.uint8 or m.dim() != 3 or m.shape[2] != 3 or tuple(m.shape) != tuple(maps[0].shape):
+            raise ValueError("pan_boundary_map: maps must be uint8 [H,W,3] of one shape, got %s %s" % (tuple(m.shape), m.dtype))
+    if int(dilation) < 1:
+        raise ValueError("pan_boundary_map: dilation %d < 1" % dilation)
+    H, W = maps[0].shape[:2]
+    nbytes = pan_boundary_workspace_bytes(H, W)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
+        raise ValueError("pan_boundary_map: a uint8 workspace of at least %d bytes expected, got %s %s"
+                         % (nbytes, tuple(workspace.shape), workspace.dtype))
+    if out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or not out.is_contiguous():
+        raise ValueError("pan_boundary_map: out must be a contiguous uint8 [%d,%d], got %s %s" % (H, W, tuple(out.shape), out.dtype))
+    pred_2ch = pred_2ch.contiguous() if pred_2ch is not None else None
+    gt_rgb = gt_rgb.contiguous() if gt_rgb is not None else None
+    with torch.cuda.device(out.device):
+        check(lib().upsnet_pan_boundary_map(stream(), int(dilation), ptr(pred_2ch) if pred_2ch is not None else None,
+                                            ptr(gt_rgb) if gt_rgb is not None else None, H, W, ptr(workspace), ptr(out)), "pan_boundary_map")
+    return out
+
+
 def confusion_accumulate(gt_label, pred_label, class_num, ignore_label, confusion):
     """get_confusion_matrix on the device, added into confusion int64 [class_num, class_num]: gt_label / pred_label uint8 of one
     shape; pixels with gt == ignore_label dropped (-1: none); index gt * C + pred counted iff < C^2 (pred >= C aliases, as
