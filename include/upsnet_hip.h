@@ -998,6 +998,32 @@ int upsnet_vis_render(void *stream, const unsigned char *image, int height, int 
                       const unsigned char *colours, const unsigned char *labels, const int *label_len, const int *trans,
                       const int *trans_off, int num_trans, void *workspace, unsigned char *out);
 
+/* ============================== Panoptic visualisations (vis_panoptic: flat and overlay) ============================== */
+
+/* One panoptic prediction as a picture, by the integer drawing rule of DESIGN.md section 4.20 (restated in the header of
+ * csrc/pan_vis.hip). mode 0 (flat): the reference's vis_panoptic picture (upsnet/dataset/base_dataset.py:463-511): every
+ * pixel in its category colour, white two-pixel contours around the thing instances. mode 1 (overlay): the photograph with
+ * every segment in its own colour at 1/2, the segment borders in white at 1/2 and the category names at the segments' centroids.
+ *   pred_2ch uint8 [height][width][3] (channel 0 category, 255 = VOID; channel 1 instance), cat_table int [256] as upsnet_pan_format
+ *   takes it; out uint8 [height][width][3] (every byte written, each once; must overlap no input);
+ *   info int [2] (out): [0] = segments of area >= label_min_area, [1] = labels drawn (the first upsnet_pan_vis_max_labels() = 256 of
+ *   them in ascending key); both 0 in flat mode.
+ * Overlay runs on the same stream AFTER upsnet_pan_format on the same map: id_rgb uint8 [height][width][3] and seg_table are that
+ * call's `rgb` and `table`; image uint8 [height][width][3] RGB; names uint8 [256][32] and name_len int [256]: the label of every
+ * category (a name_len outside 0..32 is taken as the nearer bound; bytes outside 32..126 draw as '?'). Flat reads none of id_rgb,
+ * seg_table, image, names, name_len (they may be NULL) and ignores label_min_area's value.
+ * Error code before anything is launched: a null pointer, another mode, sides outside 1..32768, height * width > 2^28, a negative
+ * label_min_area. A seg_table that does not belong to the map draws a wrong picture; the kernels stay inside their arrays regardless.
+ * workspace: upsnet_pan_vis_workspace_bytes() bytes, 16-byte aligned; its first upsnet_pan_vis_workspace_zeroed_bytes() bytes ZEROED
+ * ONCE before the first use, every call leaves them zeroed again; the rest needs no zeroing. Overlay: three launches, flat: one; no
+ * host synchronisation, no allocation, no atomics on the picture: the same input gives the same bytes on every run. */
+size_t upsnet_pan_vis_workspace_bytes(void);
+size_t upsnet_pan_vis_workspace_zeroed_bytes(void);
+int upsnet_pan_vis_max_labels(void);
+int upsnet_pan_vis(void *stream, int mode, const unsigned char *pred_2ch, const unsigned char *id_rgb, const int *seg_table,
+                   const unsigned char *image, int height, int width, const int *cat_table, const unsigned char *names,
+                   const int *name_len, int label_min_area, void *workspace, unsigned char *out, int *info);
+
 /* ============================== GroupNorm heads (with_norm = 'group_norm') ============================== */
 
 /* nn.GroupNorm(32, C) with a fused epilogue (csrc/group_norm.hip):

@@ -165,6 +165,10 @@ _SIGNATURES = {
     "upsnet_vis_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "upsnet_vis_font": (c_int, [P]),
     "upsnet_vis_render": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, P, c_int, P, P]),
+    "upsnet_pan_vis_workspace_bytes": (c_size_t, []),
+    "upsnet_pan_vis_workspace_zeroed_bytes": (c_size_t, []),
+    "upsnet_pan_vis_max_labels": (c_int, []),
+    "upsnet_pan_vis": (c_int, [P, c_int, P, P, P, P, c_int, c_int, P, P, P, c_int, P, P, P]),
     "upsnet_group_norm_chunk_pixels": (c_int, []),
     "upsnet_group_norm_workspace_bytes": (c_size_t, [c_int, P, P, P]),
     "upsnet_group_norm_nhwc_f32": (c_int, [P, c_int, P, P, P, P, P, c_int, P, P, c_float, c_int, P, P, P, c_int, P]),

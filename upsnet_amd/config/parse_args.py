@@ -70,6 +70,13 @@ def parse_args(description='', argv=None):
     parser.add_argument('--vis_mask', action='store_true',
                         help='sets config.test.vis_mask: draw the detections of score >= 0.5 over every image into results/vis (one PNG '
                         'per image); in a run instead of the evaluation, with --eval_only before it, as the reference does')
+    parser.add_argument('--vis_panoptic', choices=('flat', 'overlay', 'both'), default=None,
+                        help='draw every panoptic result that is scored: flat = category colours with white contours around the thing '
+                        'instances into results/pans_unified/vis_flat, overlay = segments, borders and category names over the '
+                        'photograph into results/pans_unified/vis (results/pans_combined/... with --pan_combined); the evaluation '
+                        'still runs; on an image set without ground truth the categories come from --panoptic_categories')
+    parser.add_argument('--vis_panoptic_min_area', type=int, default=None, metavar='N',
+                        help='with --vis_panoptic overlay / both: segments of fewer than N pixels get no label (default 1024)')
     parser.add_argument('--aug_scales', type=int, nargs='+', default=None, metavar='S',
                         help='sets config.test.aug_scales: test-time augmentation, further target sizes beside test.scales[0] (the '
                         'max size scales along); merged on the device')

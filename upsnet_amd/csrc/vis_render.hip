@@ -38,6 +38,7 @@
 
 #include "common.h"
 #include "upsnet_hip.h"
+#include "vis_font.h"
 
 #define VIS_MAX_DETS 256
 #define VIS_MAX_LABEL 32
@@ -51,57 +52,6 @@
 #define VIS_CELL_W 12       // a character at scale 2
 #define VIS_CELL_H 16
 #define VIS_INT_MAX 0x7fffffff
-
-// The font: one byte per cell row, bit 4 = the leftmost dot; the eighth row of every cell is empty. Characters 32..126.
-#define VIS_FONT_ROWS                                                                                                              \
-    {0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0}, /*   */ {0x04, 0x04, 0x04, 0x04, 0x04, 0x00, 0x04, 0}, /* ! */                    \
-    {0x0A, 0x0A, 0x0A, 0x00, 0x00, 0x00, 0x00, 0}, /* " */ {0x0A, 0x0A, 0x1F, 0x0A, 0x1F, 0x0A, 0x0A, 0}, /* # */                    \
-    {0x04, 0x0F, 0x14, 0x0E, 0x05, 0x1E, 0x04, 0}, /* $ */ {0x18, 0x19, 0x02, 0x04, 0x08, 0x13, 0x03, 0}, /* % */                    \
-    {0x0C, 0x12, 0x14, 0x08, 0x15, 0x12, 0x0D, 0}, /* & */ {0x0C, 0x04, 0x08, 0x00, 0x00, 0x00, 0x00, 0}, /* ' */                    \
-    {0x02, 0x04, 0x08, 0x08, 0x08, 0x04, 0x02, 0}, /* ( */ {0x08, 0x04, 0x02, 0x02, 0x02, 0x04, 0x08, 0}, /* ) */                    \
-    {0x00, 0x04, 0x15, 0x0E, 0x15, 0x04, 0x00, 0}, /* * */ {0x00, 0x04, 0x04, 0x1F, 0x04, 0x04, 0x00, 0}, /* + */                    \
-    {0x00, 0x00, 0x00, 0x00, 0x0C, 0x04, 0x08, 0}, /* , */ {0x00, 0x00, 0x00, 0x1F, 0x00, 0x00, 0x00, 0}, /* - */                    \
-    {0x00, 0x00, 0x00, 0x00, 0x00, 0x0C, 0x0C, 0}, /* . */ {0x00, 0x01, 0x02, 0x04, 0x08, 0x10, 0x00, 0}, /* / */                    \
-    {0x0E, 0x11, 0x13, 0x15, 0x19, 0x11, 0x0E, 0}, /* 0 */ {0x04, 0x0C, 0x04, 0x04, 0x04, 0x04, 0x0E, 0}, /* 1 */                    \
-    {0x0E, 0x11, 0x01, 0x02, 0x04, 0x08, 0x1F, 0}, /* 2 */ {0x1F, 0x02, 0x04, 0x02, 0x01, 0x11, 0x0E, 0}, /* 3 */                    \
-    {0x02, 0x06, 0x0A, 0x12, 0x1F, 0x02, 0x02, 0}, /* 4 */ {0x1F, 0x10, 0x1E, 0x01, 0x01, 0x11, 0x0E, 0}, /* 5 */                    \
-    {0x06, 0x08, 0x10, 0x1E, 0x11, 0x11, 0x0E, 0}, /* 6 */ {0x1F, 0x01, 0x02, 0x04, 0x08, 0x08, 0x08, 0}, /* 7 */                    \
-    {0x0E, 0x11, 0x11, 0x0E, 0x11, 0x11, 0x0E, 0}, /* 8 */ {0x0E, 0x11, 0x11, 0x0F, 0x01, 0x02, 0x0C, 0}, /* 9 */                    \
-    {0x00, 0x0C, 0x0C, 0x00, 0x0C, 0x0C, 0x00, 0}, /* : */ {0x00, 0x0C, 0x0C, 0x00, 0x0C, 0x04, 0x08, 0}, /* ; */                    \
-    {0x02, 0x04, 0x08, 0x10, 0x08, 0x04, 0x02, 0}, /* < */ {0x00, 0x00, 0x1F, 0x00, 0x1F, 0x00, 0x00, 0}, /* = */                    \
-    {0x08, 0x04, 0x02, 0x01, 0x02, 0x04, 0x08, 0}, /* > */ {0x0E, 0x11, 0x01, 0x02, 0x04, 0x00, 0x04, 0}, /* ? */                    \
-    {0x0E, 0x11, 0x01, 0x0D, 0x15, 0x15, 0x0E, 0}, /* @ */ {0x0E, 0x11, 0x11, 0x11, 0x1F, 0x11, 0x11, 0}, /* A */                    \
-    {0x1E, 0x11, 0x11, 0x1E, 0x11, 0x11, 0x1E, 0}, /* B */ {0x0E, 0x11, 0x10, 0x10, 0x10, 0x11, 0x0E, 0}, /* C */                    \
-    {0x1C, 0x12, 0x11, 0x11, 0x11, 0x12, 0x1C, 0}, /* D */ {0x1F, 0x10, 0x10, 0x1E, 0x10, 0x10, 0x1F, 0}, /* E */                    \
-    {0x1F, 0x10, 0x10, 0x1E, 0x10, 0x10, 0x10, 0}, /* F */ {0x0E, 0x11, 0x10, 0x17, 0x11, 0x11, 0x0F, 0}, /* G */                    \
-    {0x11, 0x11, 0x11, 0x1F, 0x11, 0x11, 0x11, 0}, /* H */ {0x0E, 0x04, 0x04, 0x04, 0x04, 0x04, 0x0E, 0}, /* I */                    \
-    {0x07, 0x02, 0x02, 0x02, 0x02, 0x12, 0x0C, 0}, /* J */ {0x11, 0x12, 0x14, 0x18, 0x14, 0x12, 0x11, 0}, /* K */                    \
-    {0x10, 0x10, 0x10, 0x10, 0x10, 0x10, 0x1F, 0}, /* L */ {0x11, 0x1B, 0x15, 0x15, 0x11, 0x11, 0x11, 0}, /* M */                    \
-    {0x11, 0x11, 0x19, 0x15, 0x13, 0x11, 0x11, 0}, /* N */ {0x0E, 0x11, 0x11, 0x11, 0x11, 0x11, 0x0E, 0}, /* O */                    \
-    {0x1E, 0x11, 0x11, 0x1E, 0x10, 0x10, 0x10, 0}, /* P */ {0x0E, 0x11, 0x11, 0x11, 0x15, 0x12, 0x0D, 0}, /* Q */                    \
-    {0x1E, 0x11, 0x11, 0x1E, 0x14, 0x12, 0x11, 0}, /* R */ {0x0F, 0x10, 0x10, 0x0E, 0x01, 0x01, 0x1E, 0}, /* S */                    \
-    {0x1F, 0x04, 0x04, 0x04, 0x04, 0x04, 0x04, 0}, /* T */ {0x11, 0x11, 0x11, 0x11, 0x11, 0x11, 0x0E, 0}, /* U */                    \
-    {0x11, 0x11, 0x11, 0x11, 0x11, 0x0A, 0x04, 0}, /* V */ {0x11, 0x11, 0x11, 0x15, 0x15, 0x15, 0x0A, 0}, /* W */                    \
-    {0x11, 0x11, 0x0A, 0x04, 0x0A, 0x11, 0x11, 0}, /* X */ {0x11, 0x11, 0x11, 0x0A, 0x04, 0x04, 0x04, 0}, /* Y */                    \
-    {0x1F, 0x01, 0x02, 0x04, 0x08, 0x10, 0x1F, 0}, /* Z */ {0x0E, 0x08, 0x08, 0x08, 0x08, 0x08, 0x0E, 0}, /* [ */                    \
-    {0x00, 0x10, 0x08, 0x04, 0x02, 0x01, 0x00, 0}, /* \ */ {0x0E, 0x02, 0x02, 0x02, 0x02, 0x02, 0x0E, 0}, /* ] */                    \
-    {0x04, 0x0A, 0x11, 0x00, 0x00, 0x00, 0x00, 0}, /* ^ */ {0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x1F, 0}, /* _ */                    \
-    {0x08, 0x04, 0x02, 0x00, 0x00, 0x00, 0x00, 0}, /* ` */ {0x00, 0x00, 0x0E, 0x01, 0x0F, 0x11, 0x0F, 0}, /* a */                    \
-    {0x10, 0x10, 0x16, 0x19, 0x11, 0x11, 0x1E, 0}, /* b */ {0x00, 0x00, 0x0E, 0x10, 0x10, 0x11, 0x0E, 0}, /* c */                    \
-    {0x01, 0x01, 0x0D, 0x13, 0x11, 0x11, 0x0F, 0}, /* d */ {0x00, 0x00, 0x0E, 0x11, 0x1F, 0x10, 0x0E, 0}, /* e */                    \
-    {0x06, 0x09, 0x08, 0x1C, 0x08, 0x08, 0x08, 0}, /* f */ {0x00, 0x0F, 0x11, 0x11, 0x0F, 0x01, 0x0E, 0}, /* g */                    \
-    {0x10, 0x10, 0x16, 0x19, 0x11, 0x11, 0x11, 0}, /* h */ {0x04, 0x00, 0x0C, 0x04, 0x04, 0x04, 0x0E, 0}, /* i */                    \
-    {0x02, 0x00, 0x06, 0x02, 0x02, 0x12, 0x0C, 0}, /* j */ {0x10, 0x10, 0x12, 0x14, 0x18, 0x14, 0x12, 0}, /* k */                    \
-    {0x0C, 0x04, 0x04, 0x04, 0x04, 0x04, 0x0E, 0}, /* l */ {0x00, 0x00, 0x1A, 0x15, 0x15, 0x11, 0x11, 0}, /* m */                    \
-    {0x00, 0x00, 0x16, 0x19, 0x11, 0x11, 0x11, 0}, /* n */ {0x00, 0x00, 0x0E, 0x11, 0x11, 0x11, 0x0E, 0}, /* o */                    \
-    {0x00, 0x00, 0x1E, 0x11, 0x1E, 0x10, 0x10, 0}, /* p */ {0x00, 0x00, 0x0D, 0x13, 0x0F, 0x01, 0x01, 0}, /* q */                    \
-    {0x00, 0x00, 0x16, 0x19, 0x10, 0x10, 0x10, 0}, /* r */ {0x00, 0x00, 0x0E, 0x10, 0x0E, 0x01, 0x1E, 0}, /* s */                    \
-    {0x08, 0x08, 0x1C, 0x08, 0x08, 0x09, 0x06, 0}, /* t */ {0x00, 0x00, 0x11, 0x11, 0x11, 0x13, 0x0D, 0}, /* u */                    \
-    {0x00, 0x00, 0x11, 0x11, 0x11, 0x0A, 0x04, 0}, /* v */ {0x00, 0x00, 0x11, 0x11, 0x15, 0x15, 0x0A, 0}, /* w */                    \
-    {0x00, 0x00, 0x11, 0x0A, 0x04, 0x0A, 0x11, 0}, /* x */ {0x00, 0x00, 0x11, 0x11, 0x0F, 0x01, 0x0E, 0}, /* y */                    \
-    {0x00, 0x00, 0x1F, 0x02, 0x04, 0x08, 0x1F, 0}, /* z */ {0x02, 0x04, 0x04, 0x08, 0x04, 0x04, 0x02, 0}, /* { */                    \
-    {0x04, 0x04, 0x04, 0x04, 0x04, 0x04, 0x04, 0}, /* | */ {0x08, 0x04, 0x04, 0x02, 0x04, 0x04, 0x08, 0}, /* } */                    \
-    {0x00, 0x00, 0x08, 0x15, 0x02, 0x00, 0x00, 0}  /* ~ */
 
 static const unsigned char h_vis_font[][8] = {VIS_FONT_ROWS};
 __device__ static const unsigned char d_vis_font[][8] = {VIS_FONT_ROWS};

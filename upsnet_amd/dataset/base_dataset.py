@@ -197,6 +197,36 @@ class BaseDataset(object):
         logger.info('%d panoptic predictions written to %s', len(annotations), os.path.abspath(output_dir))
         return annotations
 
+    def vis_panoptic(self, pred_pans_2ch, output_dir, mode='overlay', categories=None, categories_json=None, label_min_area=1024):
+        """The predictions write_panoptic would write, as pictures (dataset/pan_vis.vis_panoptic): mode 'flat' -- the
+        reference's vis_panoptic picture, category colours with white contours around the thing instances -- to output_dir/vis_flat,
+        mode 'overlay' -- the photograph with the segments, their borders and their names -- to output_dir/vis; file names as
+        write_panoptic's. Predictions, names and categories are resolved exactly as write_panoptic resolves them (with ground truth:
+        one prediction per annotation of self.panoptic_json_file, in its order; without: the image list's order and categories= or
+        categories_json=). Returns the written paths."""
+        from .pan_vis import vis_panoptic
+        if getattr(self, 'has_gt', True):
+            with open(self.panoptic_json_file, 'r') as f:
+                gt_json = json.load(f)
+            images = gt_json['images']
+            if len(images) != len(gt_json['annotations']):
+                raise ValueError("%s lists %d images and %d annotations" % (self.panoptic_json_file, len(images), len(gt_json['annotations'])))
+            if categories is None and categories_json is None:
+                categories = gt_json['categories']
+            order = self.panoptic_order() if mode == 'overlay' else None
+        else:
+            images = [{'id': e['id'], 'file_name': e['file_name']} for e in self.roidb]
+            order = list(range(len(self.roidb)))
+        if categories is None:
+            if categories_json is None:
+                raise ValueError("%s has no ground truth and so no category table: pass categories= or the path of a panoptic JSON "
+                                 "whose 'categories' to use (categories_json=)" % getattr(self, 'name', type(self).__name__))
+            with open(categories_json, 'r') as f:
+                categories = json.load(f)['categories']
+        image_paths = [self.roidb[k]['image'] for k in order] if mode == 'overlay' else None
+        os.makedirs(output_dir, exist_ok=True)
+        return vis_panoptic(pred_pans_2ch, images, categories, output_dir, mode, image_paths=image_paths, label_min_area=label_min_area)
+
     def evaluate_panoptic_files(self, pred_json, pred_folder, max_gt_segments=4096, boundary=False, dilation_ratio=0.02):
         """PQ / SQ / RQ of a prediction in COCO panoptic format (pred_json with its PNG folder: write_panoptic's output, or any other
         tool's) against the panoptic GT, through PanopticEvaluator.add_png. Annotations are paired with the GT by image_id;

@@ -56,6 +56,12 @@ def font_table():
     return cells
 
 
+def load_image(path):
+    """The photograph at `path` as RGB uint8 [H, W, 3] (json_dataset.imread_bgr's decoding, channels reversed)."""
+    from .json_dataset import imread_bgr
+    return np.ascontiguousarray(imread_bgr(path)[:, :, ::-1])
+
+
 def kept_detections(all_boxes, all_masks, i, class_names):
     """The detections of image i that the reference draws, in its order: [(class index j, row k, box float32 [4], score float32,
     label str, RLE dict)]. class_names[j] is the name of class j; '__background__' is skipped."""

@@ -4,6 +4,7 @@
     python -m upsnet_amd.evaluate --cfg <yaml> (--weight_path <pth> | --synthetic_weights) [--eval_only] [--in-flight N] [--pan_combined]
                                   [--eval_proposals] [--eval_instances] [--write_panoptic [--panoptic_categories <json>]]
                                   [--eval_pixels] [--write_ssegs [--ssegs_label_ids]] [--vis_mask]
+                                  [--vis_panoptic {flat,overlay,both} [--vis_panoptic_min_area N]]
                                   [--write_instances [--instances_1bit]] [--eval_boundary [--boundary_dilation_ratio R]]
                                   [--eval_boundary_pq [--boundary_pq_dilation_ratio R]] [--aug_scales S [S ...]] [--aug_flip]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>] [--eval_boundary_pq ...]
@@ -42,7 +43,11 @@ bit depth 1 with `--instances_1bit`; dataset/cityscapes_inst_format.py), also fo
 `--score_instances <folder>` scores such a folder, or another tool's, without building the model (metrics['instance_ap']). `--vis_mask` (or `test.vis_mask: true` in the yaml; needs a mask head) draws the detections
 of score >= 0.5 over every image into results/vis, one PNG per image (BaseDataset.vis_all_mask, dataset/vis.py), with the reference's
 control flow: a run writes the pickle, draws and skips the evaluation (upsnet_end2end_test.py:300-301); with `--eval_only` the drawing
-comes first and the evaluation follows (:172-173), and the images must be on disk. `--aug_scales S [S ...]` and `--aug_flip` (or
+comes first and the evaluation follows (:172-173), and the images must be on disk. `--vis_panoptic {flat,overlay,both}` (a panoptic
+head, or --pan_combined) draws every panoptic result that is scored into the folder --write_panoptic uses: <folder>/vis_flat (category
+colours, white contours around the thing instances: the reference's vis_panoptic picture) and / or <folder>/vis (segments, borders and
+category names over the photograph; labels from `--vis_panoptic_min_area` pixels, default 1024), beside the evaluation and also for an
+image set without ground truth (dataset/pan_vis.py; the paths come back as 'vis_panoptic_files'). `--aug_scales S [S ...]` and `--aug_flip` (or
 `test.aug_scales` / `test.aug_flip` in the yaml) turn on multi-scale / flip test-time augmentation (upsnet_amd/tta.py): every
 image runs once per augmentation, eagerly and with one image in flight, the results are merged on the device in the base frame, and the
 results pickle also carries 'test_aug', the augmentation list; `--eval_proposals` is refused with it (there is no single proposal list).
@@ -215,7 +220,8 @@ def ssegs_folder(results_dir, label_ids):
 
 def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False, write_panoptic=False,
                      panoptic_categories=None, eval_pixels=False, write_ssegs=False, ssegs_label_ids=False, write_instances=False,
-                     instances_1bit=False, eval_boundary=False, boundary_dilation_ratio=0.02, boundary_pq_ratio=None):
+                     instances_1bit=False, eval_boundary=False, boundary_dilation_ratio=0.02, boundary_pq_ratio=None, vis_panoptic=None,
+                     vis_panoptic_min_area=1024, vis_panoptic_files=None):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
     'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
@@ -228,7 +234,9 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
     of bit depth 1 with instances_1bit), with or without ground truth. eval_boundary adds 'boundary_ap' (the 12 stats of Boundary AP
     at boundary_dilation_ratio, BaseDataset.evaluate_boundary) after the mask AP. boundary_pq_ratio (not None) adds 'panoptic_boundary'
     after 'panoptic' and 'panoptic_combined_boundary' after 'panoptic_combined': Boundary PQ of the same predictions at that ratio
-    (BaseDataset.evaluate_panoptic_boundary)."""
+    (BaseDataset.evaluate_panoptic_boundary). vis_panoptic ('flat', 'overlay' or 'both'): every panoptic result that is scored (or,
+    without ground truth, would be) is also drawn into the folder write_panoptic uses, <folder>/vis_flat and / or <folder>/vis
+    (BaseDataset.vis_panoptic, labels from vis_panoptic_min_area pixels); the written paths are appended to vis_panoptic_files."""
     net = config.network
     metrics = {}
     if write_ssegs:
@@ -237,11 +245,13 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
         dataset.write_instance_result(results['all_boxes'], results['all_masks'], results_dir, one_bit=instances_1bit)
     if not dataset.has_gt:
         logger.info('%s has no annotations (%s): evaluation skipped', dataset.name, os.path.basename(dataset.instances_json_file))
-        if write_panoptic:
+        if write_panoptic or vis_panoptic:
             for combined in ([False] if net.has_panoptic_head else []) + ([True] if pan_combined else []):
-                dataset.write_panoptic(panoptic_predictions(dataset, results, combined),
-                                       os.path.join(results_dir, 'pans_combined' if combined else 'pans_unified'),
-                                       categories_json=panoptic_categories)
+                pans = panoptic_predictions(dataset, results, combined)
+                folder = os.path.join(results_dir, 'pans_combined' if combined else 'pans_unified')
+                if write_panoptic:
+                    dataset.write_panoptic(pans, folder, categories_json=panoptic_categories)
+                draw_panoptic(dataset, pans, folder, vis_panoptic, vis_panoptic_min_area, panoptic_categories, vis_panoptic_files)
         return metrics
     os.makedirs(results_dir, exist_ok=True)
     if net.has_rcnn:
@@ -262,6 +272,7 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
                                                                               dilation_ratio=boundary_pq_ratio)
         if write_panoptic:
             dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_unified'))
+        draw_panoptic(dataset, pans, os.path.join(results_dir, 'pans_unified'), vis_panoptic, vis_panoptic_min_area, None, vis_panoptic_files)
     if pan_combined:
         logger.info('combined pano result:')
         pans = panoptic_predictions(dataset, results, True, dataset.panoptic_order())
@@ -272,6 +283,7 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
                                                                                        dilation_ratio=boundary_pq_ratio)
         if write_panoptic:
             dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_combined'))
+        draw_panoptic(dataset, pans, os.path.join(results_dir, 'pans_combined'), vis_panoptic, vis_panoptic_min_area, None, vis_panoptic_files)
     if net.has_fcn_head:
         metrics['sseg'] = dataset.evaluate_ssegs(results['all_ssegs'], os.path.join(results_dir, 'ssegs'))
     if eval_proposals:
@@ -285,6 +297,14 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
         logger.info('pixel-level result:')
         metrics['pixel_iou'] = dataset.evaluate_pixels(results['all_ssegs'], results_dir)
     return metrics
+
+
+def draw_panoptic(dataset, pans, folder, which, min_area, categories_json, files):
+    """--vis_panoptic: the pictures of one panoptic result into folder/vis_flat and / or folder/vis; `files` collects the paths."""
+    for mode in {'flat': ('flat',), 'overlay': ('overlay',), 'both': ('flat', 'overlay')}.get(which, ()):
+        paths = dataset.vis_panoptic(pans, folder, mode=mode, categories_json=categories_json, label_min_area=min_area)
+        if files is not None:
+            files.extend(paths)
 
 
 def check_pixel_run(dataset, args):
@@ -305,7 +325,8 @@ def draw_results(dataset, results, results_dir):
 
 def main(argv=None):
     """Returns {'metrics': ..., 'results_file': path, 'times': per-image timings (None with --eval_only)}, and with config.test.vis_mask
-    also 'vis_files': the PNGs written under results/vis."""
+    also 'vis_files': the PNGs written under results/vis, and with --vis_panoptic 'vis_panoptic_files': the pictures written under
+    results/pans_unified (and pans_combined)."""
     from .config.parse_args import parse_args
     args = parse_args('UPSNet: run and score a checkpoint over an evaluation set', argv)
     logging.basicConfig(level=logging.INFO, format='%(asctime)-15s | %(message)s')
@@ -383,6 +404,17 @@ def main(argv=None):
     if args.write_panoptic and not (net.has_panoptic_head or args.pan_combined):
         raise SystemExit('--write_panoptic writes the panoptic predictions: it needs network.has_panoptic_head, or --pan_combined '
                          '(has_panoptic_head=%s)' % net.has_panoptic_head)
+    if args.vis_panoptic and not (net.has_panoptic_head or args.pan_combined):
+        raise SystemExit('--vis_panoptic draws the panoptic predictions: it needs network.has_panoptic_head, or --pan_combined '
+                         '(has_panoptic_head=%s)' % net.has_panoptic_head)
+    if args.vis_panoptic_min_area is not None and args.vis_panoptic not in ('overlay', 'both'):
+        raise SystemExit('--vis_panoptic_min_area sets the smallest labelled segment of --vis_panoptic overlay / both, which is missing')
+    if args.vis_panoptic_min_area is not None and args.vis_panoptic_min_area < 0:
+        raise SystemExit('--vis_panoptic_min_area: %d is negative' % args.vis_panoptic_min_area)
+    pv_files = []
+    pv_kw = dict(vis_panoptic=args.vis_panoptic, vis_panoptic_files=pv_files,
+                 vis_panoptic_min_area=1024 if args.vis_panoptic_min_area is None else args.vis_panoptic_min_area)
+    pv_out = {'vis_panoptic_files': pv_files} if args.vis_panoptic else {}
     if args.score_panoptic_folder and not args.score_panoptic:
         raise SystemExit('--score_panoptic_folder names the PNG folder of --score_panoptic <pred.json>, which is missing')
     boundary_ratio = 0.02 if args.boundary_dilation_ratio is None else args.boundary_dilation_ratio
@@ -435,7 +467,7 @@ def main(argv=None):
             raise SystemExit('--eval_only --eval_proposals: %s holds no proposals (all_proposals); run with --eval_proposals without '
                              '--eval_only first' % results_file)
         dataset = build_dataset(out_dir)
-        dataset.check_files(images=vis_mask)
+        dataset.check_files(images=vis_mask or args.vis_panoptic in ('overlay', 'both'))
         if args.eval_instances:
             dataset.check_instance_files()
         check_pixel_run(dataset, args)
@@ -444,13 +476,13 @@ def main(argv=None):
             return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                                  args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
                                                  args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio,
-                                            boundary_pq_ratio=boundary_pq_ratio),
-                    'results_file': results_file, 'times': None, 'vis_files': vis_files}
+                                            boundary_pq_ratio=boundary_pq_ratio, **pv_kw),
+                    'results_file': results_file, 'times': None, 'vis_files': vis_files, **pv_out}
         return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
                                              args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio,
-                                            boundary_pq_ratio=boundary_pq_ratio),
-                'results_file': results_file, 'times': None}
+                                            boundary_pq_ratio=boundary_pq_ratio, **pv_kw),
+                'results_file': results_file, 'times': None, **pv_out}
 
     dataset = build_dataset(out_dir)
     dataset.check_files()       # every image and GT file, before the first launch
@@ -474,12 +506,12 @@ def main(argv=None):
     logging.info('%d images, results written to %s', len(dataset), results_file)
     if vis_mask:            # (upsnet_end2end_test.py:300-301, an if / else: drawn instead of evaluated)
         del model
-        return {'metrics': {}, 'results_file': results_file, 'times': times, 'vis_files': draw_results(dataset, results, results_dir)}
+        return {'metrics': {}, 'results_file': results_file, 'times': times, 'vis_files': draw_results(dataset, results, results_dir), **pv_out}
     return {'metrics': evaluate_results(dataset, results, results_dir, args.pan_combined, args.eval_proposals, args.eval_instances,
                                              args.write_panoptic, args.panoptic_categories or None, args.eval_pixels, args.write_ssegs,
                                              args.ssegs_label_ids, args.write_instances, args.instances_1bit, args.eval_boundary, boundary_ratio,
-                                            boundary_pq_ratio=boundary_pq_ratio),
-            'results_file': results_file, 'times': times}
+                                            boundary_pq_ratio=boundary_pq_ratio, **pv_kw),
+            'results_file': results_file, 'times': times, **pv_out}
 
 
 if __name__ == '__main__':
