@@ -17,6 +17,7 @@ and CPU tensors.
 TRACE (parity tests): set to a list and every convolution / GroupNorm launch appends a record of its module(s), inputs, fused epilogue
 operands and output -- tests/test_layerwise_gpu.py replays each record in float64 ("per op, on identical inputs").
 """
+import collections
 import os
 
 import torch
@@ -92,6 +93,49 @@ def _pack(m, slot, pack, *extra):
     return ops.cached_pack(m, slot, (m.weight, m.bias), lambda: pack(m.weight.detach()), *extra)
 
 
+# ---- geometry of a launch: every rule below reads shapes through these
+def _out_hw(m, x):
+    """(height, width) of m(x)."""
+    k, st, pd, dl = m.kernel_size[0], m.stride[0], m.padding[0], m.dilation[0]
+    return (x.shape[2] + 2 * pd - dl * (k - 1) - 1) // st + 1, (x.shape[3] + 2 * pd - dl * (k - 1) - 1) // st + 1
+
+
+def _out_pixels(m, xs):
+    """output pixels of one launch of m over the maps xs."""
+    pix = 0
+    for x in xs:
+        ho, wo = _out_hw(m, x)
+        pix += x.shape[0] * ho * wo
+    return pix
+
+
+def _plain(m, k, pad, strides=(1,)):
+    """is m a k x k convolution with padding `pad` and one of `strides`, undilated and ungrouped?"""
+    return (tuple(m.kernel_size) == (k, k) and tuple(m.padding) == (pad, pad) and m.stride[0] == m.stride[1] and m.stride[0] in strides and
+            tuple(m.dilation) == (1, 1) and m.groups == 1)
+
+
+def _tiles(x, t):
+    """t x t output tiles of one image of a 3x3 / stride 1 / pad 1 layer on x."""
+    return -(-x.shape[2] // t) * -(-x.shape[3] // t)
+
+
+def _wino_workgroups(m, xs, tm=64):
+    """workgroups of the F(2x2) form over xs: tm 2x2 tiles x 64 channels each (x all channels for Cout <= 32)."""
+    tiles = sum(-(-(x.shape[0] * _tiles(x, 2)) // tm) for x in xs)
+    return tiles * (1 if m.out_channels <= 32 else -(-m.out_channels // 64))
+
+
+def _wino36_workgroups(m, xs):
+    """per map, the workgroups of the F(4x4) form: 32 4x4 tiles x 64 channels each."""
+    return [-(-(x.shape[0] * _tiles(x, 4)) // 32) * (m.out_channels // 64) for x in xs]
+
+
+def _ldw32(cout):
+    """row length of the general kernel's weight pack (ops.pack_conv_weight): its instance is chosen by it."""
+    return (cout + 31) // 32 * 32
+
+
 def _plan(m):
     return _pack(m, 'direct', ops.pack_conv_weight)
 
@@ -101,14 +145,11 @@ def _conv1x1_plan(m):
 
 
 def _use_conv1x1(m, x, always=False):
-    if not (CONV1X1 and tuple(m.kernel_size) == (1, 1) and tuple(m.padding) == (0, 0) and m.stride[0] in (1, 2) and
-            m.in_channels % 32 == 0 and m.out_channels >= 32):
+    if not (CONV1X1 and _plain(m, 1, 0, (1, 2)) and m.in_channels % 32 == 0 and m.out_channels >= 32):
         return False
     if always:   # layers whose batch size varies at run time: the kernel (hence the summation order) must not depend on it
         return True
-    st = m.stride[0]
-    pix = x.shape[0] * ((x.shape[2] - 1) // st + 1) * ((x.shape[3] - 1) // st + 1)
-    return -(-pix // 64) * -(-m.out_channels // 64) >= CONV1X1_MIN_WG
+    return -(-_out_pixels(m, [x]) // 64) * -(-m.out_channels // 64) >= CONV1X1_MIN_WG
 
 
 # A workgroup of the lean 1x1 kernel (4 waves, one per SIMD) keeps its CU's matrix pipe busy by itself (measured: a lone workgroup
@@ -154,9 +195,8 @@ def _c1_best_split(wgs, walk_us, nsl, cus):
 
 def _c1_balance(m, x, cus=None):
     """-> (rows of the unsplit main part, split factor of the tail part); (all rows, 1) = one plain launch."""
-    st = m.stride[0]
-    M = x.shape[0] * ((x.shape[2] - 1) // st + 1) * ((x.shape[3] - 1) // st + 1)
-    if not BALANCE or st != 1:
+    M = _out_pixels(m, [x])
+    if not BALANCE or m.stride[0] != 1:
         return M, 1
     cus = cus or _cus(x.device)
     cin, cout, nsl = m.in_channels, m.out_channels, m.in_channels // 32
@@ -178,13 +218,10 @@ def _c1_balance(m, x, cus=None):
     return main_tiles * 64, ks
 
 
-def _conv1x1_balanced(m, x, relu, residual):
-    """conv1x1_frag of a stride-1 layer as (unsplit main rows) + (split-K tail rows), both writing into one output; rows = pixels in
-    NHWC order, so each part is a contiguous [rows, C] slab viewed as a 1 x rows image."""
-    rows_main, ks = _c1_balance(m, x)
+def _conv1x1_balanced(m, x, rows_main, ks, relu, residual):
+    """conv1x1_frag of a stride-1 layer as (unsplit main rows) + (split-K tail rows) -- _c1_balance --, both writing into one output;
+    rows = pixels in NHWC order, so each part is a contiguous [rows, C] slab viewed as a 1 x rows image."""
     wp = _conv1x1_plan(m)
-    if ks == 1:
-        return ops.conv1x1_frag(x, wp, m.bias, m.out_channels, 1, relu=relu, residual=residual), 'conv1x1'
     x = ops.nhwc(x.float())
     N, C, H, W = x.shape
     M, co = N * H * W, m.out_channels
@@ -198,7 +235,7 @@ def _conv1x1_balanced(m, x, relu, residual):
                          out=img(orow[:rows_main], co))
     ops.conv1x1_frag(img(xr[rows_main:], C), wp, m.bias, co, 1, relu=relu, residual=None if rr is None else img(rr[rows_main:], co),
                      out=img(orow[rows_main:], co), ksplit=ks)
-    return out, 'conv1x1 %s splitk%d' % ('main + tail' if rows_main else 'all', ks)
+    return out
 
 
 # r13: the small-tile 1x1 kernel (csrc/conv1x1_ksw.hip: 16 pixels x 64 channels of v_mfma_f32_16x16x4_f32 fragments, K split over the four
@@ -218,13 +255,10 @@ def _ksw_plan(m):
 
 
 def _use_ksw(m, x, cus=None):
-    if not (KSW and PRECISION == 'fp32' and x.dtype == torch.float32 and tuple(m.kernel_size) == (1, 1) and tuple(m.padding) == (0, 0) and
-            m.stride[0] in (1, 2) and m.in_channels % 16 == 0 and m.out_channels % 4 == 0 and m.in_channels >= 256 and
-            m.in_channels >= 2 * m.out_channels):
+    if not (KSW and PRECISION == 'fp32' and x.dtype == torch.float32 and _plain(m, 1, 0, (1, 2)) and m.in_channels % 16 == 0 and
+            m.out_channels % 4 == 0 and m.in_channels >= 256 and m.in_channels >= 2 * m.out_channels):
         return False
-    st = m.stride[0]
-    pix = x.shape[0] * ((x.shape[2] - 1) // st + 1) * ((x.shape[3] - 1) // st + 1)
-    m_tiles = -(-pix // 64)
+    m_tiles = -(-_out_pixels(m, [x]) // 64)
     wgs = m_tiles * -(-m.out_channels // _c1_bn(m_tiles, m.out_channels))
     cus = cus or _cus(x.device)
     return wgs < KSW_MAX_FILL * -(-wgs // cus) * cus
@@ -242,8 +276,7 @@ def _ksw3_plan(m):
 
 
 def _use_ksw3(m, x):
-    return (KSW3 and PRECISION == 'fp32' and x.dtype == torch.float32 and tuple(m.kernel_size) == (3, 3) and tuple(m.stride) == (1, 1) and
-            tuple(m.padding) == (1, 1) and tuple(m.dilation) == (1, 1) and m.out_channels <= 32 and m.in_channels % 16 == 0)
+    return KSW3 and PRECISION == 'fp32' and x.dtype == torch.float32 and _plain(m, 3, 1) and m.out_channels <= 32 and m.in_channels % 16 == 0
 
 
 PAIR = os.environ.get('UPSNET_CONV1X1_PAIR', '1') != '0'
@@ -263,10 +296,9 @@ def use_pair(m3, m1, x, residual):
     Not in the bf16 modes (there the layers follow hipconv._use_bf16)."""
     if not (PAIR and CONV1X1 and PRECISION == 'fp32' and supported(m3, x) and residual is not None and isinstance(m1, nn.Conv2d)):
         return False
-    ok = lambda m: (tuple(m.kernel_size) == (1, 1) and tuple(m.stride) == (1, 1) and tuple(m.padding) == (0, 0) and m.groups == 1)
-    if not (ok(m3) and ok(m1) and m3.out_channels % 128 == 0 and m1.in_channels == m3.out_channels):
+    if not (_plain(m3, 1, 0) and _plain(m1, 1, 0) and m3.out_channels % 128 == 0 and m1.in_channels == m3.out_channels):
         return False
-    tiles = x.shape[0] * x.shape[2] * x.shape[3] // 64
+    tiles = _out_pixels(m3, [x]) // 64
     if m3.in_channels == 64 and m1.out_channels == 64:
         return tiles >= PAIR_MIN_TILES
     if PAIR_RES3 and m3.in_channels == 128 and m1.out_channels == 128:
@@ -293,12 +325,11 @@ def use_siblings(ma, mb, x):
     if not (SIBLINGS and CONV1X1 and PRECISION == 'fp32' and isinstance(ma, nn.Conv2d) and isinstance(mb, nn.Conv2d) and supported(ma, x) and
             supported(mb, x) and x.dtype == torch.float32):
         return False
-    ok = lambda m: tuple(m.kernel_size) == (1, 1) and tuple(m.padding) == (0, 0) and m.groups == 1 and m.stride[0] in (1, 2)
     # only where BOTH layers would take the lean kernel on their own (_use_conv1x1: enough workgroups): on small maps the separate
     # layers go to the implicit-GEMM split-K path, which is faster there, and the results stay the ones of the unfused model
     if not (_use_conv1x1(ma, x) and _use_conv1x1(mb, x)):
         return False
-    return (ok(ma) and ok(mb) and ma.stride == mb.stride and ma.in_channels == mb.in_channels and ma.in_channels % 32 == 0 and
+    return (_plain(ma, 1, 0, (1, 2)) and _plain(mb, 1, 0, (1, 2)) and ma.stride == mb.stride and ma.in_channels == mb.in_channels and ma.in_channels % 32 == 0 and
             ma.out_channels % 32 == 0 and (ma.bias is None) == (mb.bias is None))
 
 
@@ -331,11 +362,8 @@ def _use_bf16(m, xs, always=False):
         return False
     if always or xs[0].dtype == torch.bfloat16:   # layers whose batch size varies at run time: the choice (hence the rounding) must
         return True                               # not depend on it; bf16 activations: only the bf16 kernels read them
-    k, st, pd, dl = m.kernel_size[0], m.stride[0], m.padding[0], m.dilation[0]
-    wgs = 0
-    for x in xs:
-        ho, wo = (x.shape[2] + 2 * pd - (dl * (k - 1) + 1)) // st + 1, (x.shape[3] + 2 * pd - (dl * (k - 1) + 1)) // st + 1
-        wgs += -(-(x.shape[0] * ho * wo) // 128)
+    k, st, dl = m.kernel_size[0], m.stride[0], m.dilation[0]
+    wgs = sum(-(-_out_pixels(m, [x]) // 128) for x in xs)
     # (3x3 / 1 layers with 256-channel blocks run on csrc/conv3x3_wreg_bf16.hip, which has 2-row tiles for small maps: P4 / P5 outputs)
     small_ok = PRECISION == 'bf16' and k == 3 and st == 1 and dl == 1 and m.out_channels % 256 == 0
     return wgs * -(-m.out_channels // 128) >= (BF16_MIN_WG_WREG if small_ok else BF16_MIN_WG)
@@ -364,12 +392,11 @@ def use_block(blk, x):
         return False
     c1, c2, c3 = blk.conv1, blk.conv2, blk.conv3
     cm, cin, st = c1.out_channels, c1.in_channels, c1.stride[0]
-    plain = lambda m, k, p, s=1: (tuple(m.kernel_size) == (k, k) and tuple(m.stride) == (s, s) and tuple(m.padding) == (p, p) and
-                                  tuple(m.dilation) == (1, 1) and m.groups == 1)
+    plain = lambda m, k, p, s=1: _plain(m, k, p, (s,))
     if not (plain(c2, 3, 1) and plain(c3, 1, 0) and c2.in_channels == cm and c2.out_channels == cm and c3.in_channels == cm and
             c3.out_channels == 4 * cm):
         return False
-    ho, wo = (x.shape[2] - 1) // st + 1, (x.shape[3] - 1) // st + 1
+    ho, wo = _out_hw(c1, x)
     # (the kernel's tiles are 8x16 / 8x8 / 4x8 pixels at widths 64 / 128 / >= 256: a map with fewer tiles than half the CUs -- res5 at
     # 1024x2048, 64 tiles, 9 MB of weights per block -- stays on the separate layers: measured 156 us fused vs 130 us)
     th, tw = {64: (8, 16), 128: (8, 8)}.get(cm, (4, 8))
@@ -405,19 +432,20 @@ WINO_TAIL_SPLIT = os.environ.get('UPSNET_WINO_TAIL_SPLIT', '1') != '0'   # r10: 
 # (UPSNET_WINO_TAIL_FUSED=0) it was 114.5
 
 
-def _wino_tail_split(m, x):
+def _wino_tail_split(m, x, tm=None):
     """A batched launch (the mask head: N ROIs of 14 x 14) on the 32-tile x 64-channel form is ceil(N tiles / 32) x Cout / 64
     workgroups, two resident per CU. 100 ROIs = 616 workgroups = 1.2 rounds of 512: the last 104 run one per CU on 104 CUs while 152
     CUs idle, and the layer takes as long as 1.55 full rounds (115 us, 0.57 of the MFMA peak). Returns n_main > 0 if the batch should
     be split: the first n_main images = whole rounds on the 32 x 64 form, the remaining ones on the 32 x 32 form (twice the workgroups,
-    half the work each: at most one per CU) -- same bits from both forms, so a ROI's logits still do not depend on the batch."""
+    half the work each: at most one per CU) -- same bits from both forms, so a ROI's logits still do not depend on the batch.
+    tm: _wino_tm(m, [x]) if the caller has it."""
     if not WINO_TAIL_SPLIT or x.shape[0] < 2 or m.out_channels % 64:
         return 0
     cus = _cus(x.device)
-    n, tiles, nt = x.shape[0], ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2), m.out_channels // 64
+    n, tiles, nt = x.shape[0], _tiles(x, 2), m.out_channels // 64
     slots = 2 * cus
-    wgs = -(-(n * tiles) // 32) * nt
-    if wgs <= slots or _wino_tm(m, [x]) != 32:
+    wgs = _wino_workgroups(m, [x], 32)
+    if wgs <= slots or (_wino_tm(m, [x]) if tm is None else tm) != 32:
         return 0
     n_main = ((wgs // slots) * slots // nt) * 32 // tiles
     # the tail as large as still fits one half-size workgroup per CU (100 ROIs: 80 + 20 -- 99.5 us against 102.5 for 83 + 17)
@@ -449,8 +477,7 @@ def _winograd36_plan(m):
 
 
 def _winograd36_shape_ok(m):
-    return (tuple(m.kernel_size) == (3, 3) and tuple(m.stride) == (1, 1) and tuple(m.padding) == (1, 1) and tuple(m.dilation) == (1, 1) and
-            m.in_channels % 32 == 0 and m.out_channels % 64 == 0)
+    return _plain(m, 3, 1) and m.in_channels % 32 == 0 and m.out_channels % 64 == 0
 
 
 def _use_winograd36(m, xs):
@@ -460,7 +487,7 @@ def _use_winograd36(m, xs):
     if not (WINO36 and WINOGRAD and _winograd36_shape_ok(m) and all(x.dtype == torch.float32 for x in xs)):
         return False
     cus = _cus(xs[0].device)
-    wgs = sum(-(-(x.shape[0] * ((x.shape[2] + 3) // 4) * ((x.shape[3] + 3) // 4)) // 32) for x in xs) * (m.out_channels // 64)
+    wgs = sum(_wino36_workgroups(m, xs))
     if cus // 2 <= wgs < cus and m.in_channels >= 256:
         # (r13) half a round of workgroups with a long channel walk (>= 16 slabs against the ~9.5 us a workgroup costs besides them): still faster
         # than the F(2x2) form -- UPSNet-101-DCN at 800x1333, FPN P3 on the 100 x 168 map: 132 workgroups, 94.9 vs 120.6 us
@@ -482,7 +509,7 @@ def _wino36_round_prefix(m, xs):
     if not WINO36_PREFIX or n < 2:
         return n
     cus = _cus(xs[0].device)
-    per = [-(-(x.shape[0] * ((x.shape[2] + 3) // 4) * ((x.shape[3] + 3) // 4)) // 32) * (m.out_channels // 64) for x in xs]
+    per = _wino36_workgroups(m, xs)
     fill = lambda w: w / float(-(-w // cus) * cus)
     last = sum(per) % cus
     if last == 0 or last >= cus // 2:
@@ -500,25 +527,24 @@ def _wino36_ksplit(m, x):
     if not (WINO36 and WINOGRAD and _winograd36_shape_ok(m) and x.dtype == torch.float32):
         return 1
     cus = _cus(x.device)
-    wgs = -(-(x.shape[0] * ((x.shape[2] + 3) // 4) * ((x.shape[3] + 3) // 4)) // 32) * (m.out_channels // 64)
+    wgs = _wino36_workgroups(m, [x])[0]
     if wgs >= cus or wgs < cus // 4 or (wgs >= cus // 2 and m.in_channels >= 256):   # (the last: the unsplit form takes those, _use_winograd36)
         return 1
     ks = min(cus // wgs, (m.in_channels // 16) // 4, 8)
     return ks if ks >= 2 else 1
 
 
+def _wino_choice(m, xs, always=False):
+    """(2x2 tiles per workgroup, split-K factor) of the F(2x2) form for this launch; None where the form does not apply or pay."""
+    if not (WINOGRAD and _plain(m, 3, 1) and m.in_channels % 16 == 0):
+        return None
+    tm = _wino_tm(m, xs)
+    ks = 1 if always else _wino_ksplit(m, xs, tm)
+    return (tm, ks) if always or _wino_workgroups(m, xs, tm) * ks >= WINOGRAD_MIN_WORKGROUPS else None
+
+
 def _use_winograd(m, xs, always=False):
-    if not (WINOGRAD and tuple(m.kernel_size) == (3, 3) and tuple(m.stride) == (1, 1) and tuple(m.padding) == (1, 1) and
-            tuple(m.dilation) == (1, 1) and m.in_channels % 16 == 0):
-        return False
-    if always:
-        return True
-    return _wino_workgroups(m, xs, _wino_tm(m, xs)) * _wino_ksplit(m, xs) >= WINOGRAD_MIN_WORKGROUPS
-
-
-def _wino_workgroups(m, xs, tm=64):
-    tiles = sum(-(-(x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2)) // tm) for x in xs)
-    return tiles * (1 if m.out_channels <= 32 else -(-m.out_channels // 64))
+    return _wino_choice(m, xs, always) is not None
 
 
 def _wino_tm(m, xs):
@@ -527,11 +553,11 @@ def _wino_tm(m, xs):
     return 64 if m.out_channels > 32 and _wino_workgroups(m, xs, 64) > WINO_TM64_MIN else 32
 
 
-def _wino_ksplit(m, xs):
+def _wino_ksplit(m, xs, tm=None):
     """Split-K factor of the Winograd kernel for one map with fewer than 256 32-tile x 64-channel workgroups (res5 3x3, FPN
     P5): the largest split that stays within the 512 workgroup slots of 256 CUs and keeps >= 4 slabs of 16 channels per
-    workgroup."""
-    if not SPLITK or len(xs) != 1 or m.out_channels % 4 or _wino_tm(m, xs) == 64:
+    workgroup. tm: _wino_tm(m, xs) if the caller has it."""
+    if not SPLITK or len(xs) != 1 or m.out_channels % 4 or (_wino_tm(m, xs) if tm is None else tm) == 64:
         return 1
     wgs, slabs = _wino_workgroups(m, xs, 32), m.in_channels // 16
     if wgs >= 256:   # (res4 conv2, 256 workgroups: 46 us unsplit, 53 us split in two + the reduce launch)
@@ -549,9 +575,8 @@ def _ksplit(m, x, ldw):
     workgroups walking 72 slabs one after the other (66 us for 2 us of matrix work, 28 such launches per image): split up to 8 ways."""
     if not SPLITK:
         return 1
-    k, st, pd = m.kernel_size[0], m.stride[0], m.padding[0]
-    pix = x.shape[0] * ((x.shape[2] + 2 * pd - k) // st + 1) * ((x.shape[3] + 2 * pd - k) // st + 1)
-    slabs = k * k * m.in_channels // 32
+    pix = _out_pixels(m, [x])
+    slabs = m.kernel_size[0] * m.kernel_size[0] * m.in_channels // 32
     if ldw == 32:
         blocks, ks = -(-pix // 128), 1
         while ks < 8 and blocks * (ks + 1) <= 384 and slabs // (ks + 1) >= 6:
@@ -569,109 +594,220 @@ def _ksplit(m, x, ldw):
     return 1
 
 
-def conv(m, x, relu=False, residual=None, residual_up=False, winograd=True, pin=False, out_dtype=None):
-    """relu?(m(x) + residual) on the hand-written kernels -- see _conv for the arguments. out_dtype=torch.bfloat16 (bf16 mode, a
-    layer the bf16 kernels take): the result is stored as bf16; a bf16 `x` on a layer those kernels do not take is widened first."""
-    if x.dtype == torch.bfloat16 and not (supported(m, x) and _use_bf16(m, [x])):
-        x = x.float()
-    if residual is not None and residual.dtype == torch.bfloat16 and not (supported(m, x) and _use_bf16(m, [x], always=pin or winograd == 'always')):
-        residual = residual.float()
-    y, form = _conv(m, x, relu, residual, residual_up, winograd, pin or winograd == 'always', out_dtype)
-    _trace('conv', module=m, x=x, out=y, relu=relu, residual=residual, residual_up=residual_up, form=form)
-    return y
+# ---- which kernel form a launch takes (route), and how each form is launched (_LAUNCH)
+# Route: the key of the launcher in _LAUNCH (one per kernel family and weight pack), the `form` of the trace record, then what the launcher needs
+# beyond the module and the maps. ksplit > 1: the family's split-K form; n_main: images (Winograd tail split) / rows (balanced 1x1) of the unsplit
+# part; prefix: the leading maps that go into this launch (None = all of them); widen_x / widen_residual: a bf16 input / residual is converted
+# to fp32 first (no bf16 kernel takes the layer).
+Route = collections.namedtuple('Route', 'launcher form ksplit n_main prefix tile out_dtype widen_x widen_residual',
+                               defaults=(1, 0, None, None, torch.float32, False, False))
+_Map = collections.namedtuple('_Map', 'shape dtype device is_cuda')   # all that the rules read of a map: here, one as it will be once widened
 
 
-def _conv(m, x, relu=False, residual=None, residual_up=False, winograd=True, pin=False, out_dtype=None):
-    """residual_up: `residual` is at half resolution and is added through a nearest x2 upsampling (FPN top-down add).
+def _same_geometry(ms):
+    m0 = ms[0]
+    return all(isinstance(m, nn.Conv2d) and m.kernel_size == m0.kernel_size and m.stride == m0.stride and m.padding == m0.padding and
+               m.dilation == m0.dilation and m.in_channels == m0.in_channels and (m.bias is None) == (m0.bias is None) for m in ms)
+
+
+def route(m, xs, residual=None, residual_up=False, winograd=True, pin=False, out_dtype=None, multi=False, cat=None):
+    """The kernel form of relu?(m(x) + residual) for the maps xs in one launch -- conv (one map), conv_multi (multi=True), conv_multi_cat
+    (cat = the sibling modules, m = the first of them: may one launch over their concatenated channels replace theirs?). Reads shapes, dtypes,
+    module attributes, the knobs above and the CU count, nothing else: no pack, no launch, no library call; meta tensors will do.
+    residual_up: `residual` is at half resolution and is added through a nearest x2 upsampling (FPN top-down add).
     winograd=False / 'always' pins the direct / the Winograd form; 'f2x2' = the usual choice WITHOUT the F(4x4,3x3) form (3x3 layers upstream
     of a chain of deformable bottlenecks: models/resnet.py, _Block.feeds_deformable); pin=True (implied by 'always') makes every kernel choice
     (bf16 or fp32, lean 1x1 GEMM or general kernel) independent of the batch size, for layers fed by ROI batches whose size
     varies at run time: the logits of a ROI must not depend on how many other ROIs share the launch."""
-    if supported(m, x):
-        if (not residual_up or tuple(m.kernel_size) == (1, 1)) and _use_bf16(m, [x], always=pin):
-            hi, lo, ldw = _bf16_plan(m)
-            od = out_dtype if (out_dtype == torch.bfloat16 and lo is None) else torch.float32
-            return ops.conv2d_nhwc_bf16_multi([x], hi, lo, ldw, m.bias, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0],
-                                              relu=relu, residuals=None if residual is None else [residual],
-                                              residual_up=residual_up, out_dtype=od)[0], _bf16_form()
-        if winograd is True and not pin and residual is None and WINO36_SPLITK and _wino36_ksplit(m, x) > 1:
-            wp, ldw = _winograd36_plan(m)
+    pinned, sfx, widen = pin or winograd == 'always', ' multi' if multi else '', {}
+    if multi:
+        if len(xs) > 5 or not all(supported(m, x) for x in xs):
+            return Route('per_map', None)
+        x, use16 = xs[0], _use_bf16(m, xs)
+    else:
+        x = xs[0]
+        ok = supported(m, x)
+        if not ok and x.dtype == torch.bfloat16:
+            x = _Map(x.shape, torch.float32, x.device, x.is_cuda)
+            ok = supported(m, x)
+        use16 = ok and _use_bf16(m, [x], always=pinned)
+        if not use16 and x.dtype == torch.bfloat16:
+            x = _Map(x.shape, torch.float32, x.device, x.is_cuda)
+        widen = dict(widen_x=x.dtype != xs[0].dtype, widen_residual=residual is not None and residual.dtype == torch.bfloat16 and not use16)
+        if not ok:
+            return Route('library', 'library', **widen)
+        xs = [x]
+    f32, bare = x.dtype == torch.float32, residual is None
+    if use16 and (not residual_up or tuple(m.kernel_size) == (1, 1)):
+        # (bf16 activations between layers only in the plain bf16 mode: the 3-term split reads and writes fp32)
+        return Route('bf16', PRECISION, out_dtype=out_dtype if (out_dtype == torch.bfloat16 and PRECISION != 'bf16x3') else torch.float32, **widen)
+    if winograd is True and not pinned and bare:
+        if WINO36_SPLITK and not multi:
             ks = _wino36_ksplit(m, x)
-            return ops.conv2d_winograd36_splitk(x, wp, ldw, m.bias, m.out_channels, ks, relu=relu), 'winograd36 splitk%d' % ks
-        if winograd is True and not pin and residual is None and _use_winograd36(m, [x]):
-            wp, ldw = _winograd36_plan(m)
-            return ops.conv2d_winograd36_multi([x], wp, ldw, m.bias, m.out_channels, relu=relu)[0], 'winograd36'
-        if (winograd == 'always' and WINO36 and WINO36_ROI and residual is None and x.dtype == torch.float32 and _winograd36_shape_ok(m) and
-                x.shape[2] * x.shape[3] <= 1024):
-            # ROI batches (the mask head's 14 x 14 maps; opt-in): the F(4x4) kernel whatever the batch size -- 100 ROIs are 200 workgroups, 0.78
-            # of one round: 94 us alone against 100-107 on the F(2x2) form with its half-size tail (tools/bench_winograd36.py)
-            wp, ldw = _winograd36_plan(m)
-            return ops.conv2d_winograd36_multi([x], wp, ldw, m.bias, m.out_channels, relu=relu)[0], 'winograd36 roi'
-        if winograd and not residual_up and _use_winograd(m, [x], always=(winograd == 'always')):
-            wp, ldw = _winograd_plan(m)
-            ks = 1 if winograd == 'always' else _wino_ksplit(m, [x])
             if ks > 1:
-                return ops.conv2d_winograd_splitk(x, wp, ldw, m.bias, m.out_channels, ks, relu=relu, residual=residual), 'winograd splitk%d' % ks
-            n_main = _wino_tail_split(m, x) if (residual is None and x.dtype == torch.float32) else 0
-            if n_main:
-                return _wino_split_launch(m, x, n_main, relu), 'winograd tm32 + tail tn32'
-            return ops.conv2d_winograd_multi([x], wp, ldw, m.bias, m.out_channels, relu=relu,
-                                             residuals=None if residual is None else [residual])[0], 'winograd tm%d' % _wino_tm(m, [x])
-        if not pin and residual is None and _use_ksw3(m, x):
+                return Route('wino36', 'winograd36 splitk%d' % ks, ksplit=ks, **widen)
+        if _use_winograd36(m, xs):
+            # (r13) prefix: the leading maps fill whole rounds of F(4x4) workgroups; the small trailing maps would be a last round that is mostly
+            # empty (the five-level RPN launch at 1024x2048: 1024 + 256 | + 64 + 16 + 4 workgroups = 5 rounds | + a third of a sixth): they go
+            # where maps of their size go anyway (the F(2x2) multi-map launch)
+            return Route('wino36', 'winograd36' + sfx, prefix=_wino36_round_prefix(m, xs), **widen)
+    if winograd == 'always' and WINO36 and WINO36_ROI and bare and f32 and _winograd36_shape_ok(m) and x.shape[2] * x.shape[3] <= 1024:
+        # ROI batches (the mask head's 14 x 14 maps; opt-in): the F(4x4) kernel whatever the batch size -- 100 ROIs are 200 workgroups, 0.78
+        # of one round: 94 us alone against 100-107 on the F(2x2) form with its half-size tail (tools/bench_winograd36.py)
+        return Route('wino36', 'winograd36 roi', **widen)
+    wino = _wino_choice(m, xs, winograd == 'always') if (winograd and not residual_up) else None
+    if wino:
+        tm, ks = wino
+        if ks > 1 and not multi:   # (a one-map conv_multi counts the split towards WINOGRAD_MIN_WORKGROUPS and launches unsplit)
+            return Route('wino', 'winograd splitk%d' % ks, ksplit=ks, **widen)
+        n_main = _wino_tail_split(m, x, tm) if (bare and f32 and not multi) else 0
+        if n_main:
+            return Route('wino', 'winograd tm32 + tail tn32', n_main=n_main, **widen)
+        return Route('wino', 'winograd tm%d%s' % (tm, sfx), **widen)
+    if not multi:
+        if not pinned and bare and _use_ksw3(m, x):
             # (reached only where the Winograd 32-channel form was not taken: maps below WINOGRAD_MIN_WORKGROUPS workgroups)
-            return ops.conv3x3_ksw(x, _ksw3_plan(m), m.bias, m.out_channels, relu=relu), 'conv3x3 ksw 16x32'
-        if not pin and not residual_up and _use_ksw(m, x):
+            return Route('ksw3', 'conv3x3 ksw 16x32', **widen)
+        if not pinned and not residual_up and _use_ksw(m, x):
             # (before the lean / general choice: maps below CONV1X1_MIN_WG workgroups -- res5, the P5 lateral -- are the emptiest launches)
-            return ops.conv1x1_ksw(x, _ksw_plan(m), m.bias, m.out_channels, KSW_TILE, stride=m.stride[0], relu=relu,
-                                   residual=residual), 'conv1x1 ksw %dx%d' % KSW_TILE
-        if _use_conv1x1(m, x, always=pin):
-            if not pin and not residual_up and m.stride[0] == 1:
-                return _conv1x1_balanced(m, x, relu, residual)
-            return ops.conv1x1_frag(x, _conv1x1_plan(m), m.bias, m.out_channels, m.stride[0], relu=relu, residual=residual,
-                                    residual_up=residual_up), 'conv1x1'
-        wp, ldw = _plan(m)
-        ks = 1 if (residual_up or pin) else _ksplit(m, x, ldw)
+            return Route('ksw', 'conv1x1 ksw %dx%d' % KSW_TILE, tile=KSW_TILE, **widen)
+        if _use_conv1x1(m, x, always=pinned):
+            if not pinned and not residual_up and m.stride[0] == 1:
+                rows_main, ks = _c1_balance(m, x)
+                if ks > 1:
+                    return Route('c1x1', 'conv1x1 %s splitk%d' % ('main + tail' if rows_main else 'all', ks), ksplit=ks, n_main=rows_main, **widen)
+            return Route('c1x1', 'conv1x1', **widen)
+        ks = 1 if (residual_up or pinned) else _ksplit(m, x, _ldw32(m.out_channels))
         if ks > 1:
-            return ops.conv2d_nhwc_splitk(x, wp, ldw, m.bias, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], ks,
-                                          relu=relu, residual=residual), 'igemm splitk%d' % ks
-        return ops.conv2d_nhwc(x, wp, ldw, m.bias, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0],
-                               relu=relu, residual=residual, residual_up=residual_up), 'igemm'
-    _library(m, x, 'hipconv.supported() is false')
-    y = m(x)
+            return Route('igemm', 'igemm splitk%d' % ks, ksplit=ks, **widen)
+    # (cat: the instance is chosen by ldw: the concatenation must stay on the one the separate heads would use. bf16 modes: heads narrower
+    # than 64 channels stay on the fp32 kernel -- _use_bf16 -- and are concatenated all the same)
+    if cat is not None and f32 and _ldw32(sum(c.out_channels for c in cat)) == 32 and _same_geometry(cat):
+        return Route('cat', 'igemm multi cat')
+    return Route('igemm', 'igemm' + sfx, **widen)
+
+
+def _each(t):
+    return None if t is None else [t]
+
+
+def _launch_library(m, xs, r, relu, residual, residual_up):
+    _library(m, xs[0], 'hipconv.supported() is false')
+    y = m(xs[0])
     if residual is not None:
         y = y + (F.interpolate(residual, scale_factor=2, mode='nearest') if residual_up else residual)
-    return (F.relu(y, inplace=True) if relu else y), 'library'
+    return [F.relu(y, inplace=True) if relu else y]
+
+
+def _launch_bf16(m, xs, r, relu, residual, residual_up):
+    hi, lo, ldw = _bf16_plan(m)
+    return ops.conv2d_nhwc_bf16_multi(xs, hi, lo, ldw, m.bias, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], relu=relu,
+                                      residuals=_each(residual), residual_up=residual_up, out_dtype=r.out_dtype)
+
+
+def _launch_wino36(m, xs, r, relu, residual, residual_up):
+    wp, ldw = _winograd36_plan(m)
+    if r.ksplit > 1:
+        return [ops.conv2d_winograd36_splitk(xs[0], wp, ldw, m.bias, m.out_channels, r.ksplit, relu=relu)]
+    return ops.conv2d_winograd36_multi(xs, wp, ldw, m.bias, m.out_channels, relu=relu)
+
+
+def _launch_wino(m, xs, r, relu, residual, residual_up):
+    if r.n_main:
+        return [_wino_split_launch(m, xs[0], r.n_main, relu)]
+    wp, ldw = _winograd_plan(m)
+    if r.ksplit > 1:
+        return [ops.conv2d_winograd_splitk(xs[0], wp, ldw, m.bias, m.out_channels, r.ksplit, relu=relu, residual=residual)]
+    return ops.conv2d_winograd_multi(xs, wp, ldw, m.bias, m.out_channels, relu=relu, residuals=_each(residual))
+
+
+def _launch_ksw3(m, xs, r, relu, residual, residual_up):
+    return [ops.conv3x3_ksw(xs[0], _ksw3_plan(m), m.bias, m.out_channels, relu=relu)]
+
+
+def _launch_ksw(m, xs, r, relu, residual, residual_up):
+    return [ops.conv1x1_ksw(xs[0], _ksw_plan(m), m.bias, m.out_channels, r.tile, stride=m.stride[0], relu=relu, residual=residual)]
+
+
+def _launch_c1x1(m, xs, r, relu, residual, residual_up):
+    if r.ksplit > 1:
+        return [_conv1x1_balanced(m, xs[0], r.n_main, r.ksplit, relu, residual)]
+    return [ops.conv1x1_frag(xs[0], _conv1x1_plan(m), m.bias, m.out_channels, m.stride[0], relu=relu, residual=residual, residual_up=residual_up)]
+
+
+def _launch_igemm(m, xs, r, relu, residual, residual_up):
+    wp, ldw = _plan(m)
+    geom = (m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0])
+    if r.ksplit > 1:
+        return [ops.conv2d_nhwc_splitk(xs[0], wp, ldw, m.bias, *geom, r.ksplit, relu=relu, residual=residual)]
+    return ops.conv2d_nhwc_multi(xs, wp, ldw, m.bias, *geom, relu=relu, residuals=_each(residual), residual_up=residual_up)
+
+
+def _launch_cat(ms, xs, r, relu, residual, residual_up):
+    """the sibling modules ms as one general-kernel launch over their concatenated output channels."""
+    m0 = ms[0]
+    (wp, ldw), b = ops.cached_pack(m0, 'cat', [t for m in ms for t in (m.weight, m.bias)], lambda: (
+        ops.pack_conv_weight(torch.cat([m.weight.detach() for m in ms], 0)),
+        None if m0.bias is None else torch.cat([m.bias.detach() for m in ms], 0)))
+    return ops.conv2d_nhwc_multi(xs, wp, ldw, b, sum(m.out_channels for m in ms), m0.kernel_size[0], m0.stride[0], m0.padding[0], relu=relu)
+
+
+# launcher(module, maps, route, relu, residual, residual_up) -> one output per map
+_LAUNCH = {'library': _launch_library, 'bf16': _launch_bf16, 'wino36': _launch_wino36, 'wino': _launch_wino, 'ksw3': _launch_ksw3, 'ksw': _launch_ksw,
+           'c1x1': _launch_c1x1, 'igemm': _launch_igemm, 'cat': _launch_cat}
+
+
+def _form(r):
+    return _bf16_form() if r.launcher == 'bf16' else r.form
+
+
+def conv(m, x, relu=False, residual=None, residual_up=False, winograd=True, pin=False, out_dtype=None):
+    """relu?(m(x) + residual) on the hand-written kernels -- see route for the arguments. out_dtype=torch.bfloat16 (bf16 mode, a
+    layer the bf16 kernels take): the result is stored as bf16; a bf16 `x` on a layer those kernels do not take is widened first."""
+    r = route(m, [x], residual, residual_up, winograd, pin, out_dtype)
+    if r.widen_x:
+        x = x.float()
+    if r.widen_residual:
+        residual = residual.float()
+    y = _LAUNCH[r.launcher](m, [x], r, relu, residual, residual_up)[0]
+    _trace('conv', module=m, x=x, out=y, relu=relu, residual=residual, residual_up=residual_up, form=_form(r))
+    return y
 
 
 def conv_multi(m, xs, relu=False):
     """The same conv module applied to several feature maps (FPN levels) in ONE launch."""
     xs = list(xs)
-    if len(xs) <= 5 and all(supported(m, x) for x in xs):
-        if _use_bf16(m, xs):
-            hi, lo, ldw = _bf16_plan(m)
-            ys, form = ops.conv2d_nhwc_bf16_multi(xs, hi, lo, ldw, m.bias, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], relu=relu), _bf16_form()
-        elif _use_winograd36(m, xs):
-            wp, ldw = _winograd36_plan(m)
-            k = _wino36_round_prefix(m, xs)
-            if k < len(xs):
-                # (r13) the leading maps fill whole rounds of F(4x4) workgroups; the small trailing maps would be a last round that is mostly empty
-                # (the five-level RPN launch at 1024x2048: 1024 + 256 | + 64 + 16 + 4 workgroups = 5 rounds | + a third of a sixth): they go where
-                # maps of their size go anyway (the F(2x2) multi-map launch)
-                ys = ops.conv2d_winograd36_multi(xs[:k], wp, ldw, m.bias, m.out_channels, relu=relu)
-                for x, y in zip(xs[:k], ys):
-                    _trace('conv', module=m, x=x, out=y, relu=relu, residual=None, residual_up=False, form='winograd36 multi')
-                return ys + conv_multi(m, xs[k:], relu=relu)
-            ys, form = ops.conv2d_winograd36_multi(xs, wp, ldw, m.bias, m.out_channels, relu=relu), 'winograd36 multi'
-        elif _use_winograd(m, xs):
-            wp, ldw = _winograd_plan(m)
-            ys, form = ops.conv2d_winograd_multi(xs, wp, ldw, m.bias, m.out_channels, relu=relu), 'winograd tm%d multi' % _wino_tm(m, xs)
-        else:
-            wp, ldw = _plan(m)
-            ys, form = ops.conv2d_nhwc_multi(xs, wp, ldw, m.bias, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], relu=relu), 'igemm multi'
-        for x, y in zip(xs, ys):
-            _trace('conv', module=m, x=x, out=y, relu=relu, residual=None, residual_up=False, form=form)
-        return ys
-    return [conv(m, x, relu=relu) for x in xs]
+    r = route(m, xs, multi=True)
+    if r.launcher == 'per_map':
+        return [conv(m, x, relu=relu) for x in xs]
+    n = len(xs) if r.prefix is None else r.prefix
+    ys = _LAUNCH[r.launcher](m, xs[:n], r, relu, None, False)
+    form = _form(r)
+    for x, y in zip(xs, ys):
+        _trace('conv', module=m, x=x, out=y, relu=relu, residual=None, residual_up=False, form=form)
+    return ys if n == len(xs) else ys + conv_multi(m, xs[n:], relu=relu)
+
+
+def conv_multi_cat(ms, xs, return_flat=False):
+    """Several sibling convolutions of the same geometry (the RPN's objectness and box-delta 1x1 heads) on the same maps as ONE
+    launch over the concatenated output channels: the input maps are read once instead of once per head. Returns one list of
+    per-map outputs per module (channel slices of the shared output). Every output channel is computed exactly as in a separate
+    launch (same kernel instance, same K order)."""
+    xs = list(xs)
+    r = route(ms[0], xs, multi=True, cat=ms)
+    if r.launcher != 'cat':
+        res = [conv_multi(m, xs) for m in ms]
+        return (res, None, None) if return_flat else res
+    outs = _LAUNCH['cat'](ms, xs, r, False, None, False)
+    res, c0 = [], 0
+    for m in ms:
+        res.append([o[:, c0:c0 + m.out_channels] for o in outs])
+        for x, y in zip(xs, res[-1]):
+            _trace('conv', module=m, x=x, out=y, relu=False, residual=None, residual_up=False, form=r.form)
+        c0 += m.out_channels
+    if return_flat:
+        return res, getattr(outs[0], '_ups_flat', None), outs
+    return res
 
 
 def stem_supported(m, x):
@@ -834,36 +970,3 @@ def clear_cache(model=None):
             m.__dict__.pop('_hip_plans', None)
             for p in m.parameters(recurse=False):
                 p.__dict__.pop('_hip_plans', None)
-
-
-def conv_multi_cat(ms, xs, return_flat=False):
-    """Several sibling convolutions of the same geometry (the RPN's objectness and box-delta 1x1 heads) on the same maps as ONE
-    launch over the concatenated output channels: the input maps are read once instead of once per head. Returns one list of
-    per-map outputs per module (channel slices of the shared output). Every output channel is computed exactly as in a separate
-    launch (same kernel instance, same K order)."""
-    xs = list(xs)
-    m0 = ms[0]
-    same = all(isinstance(m, nn.Conv2d) and m.kernel_size == m0.kernel_size and m.stride == m0.stride and m.padding == m0.padding and
-               m.dilation == m0.dilation and m.in_channels == m0.in_channels and (m.bias is None) == (m0.bias is None) for m in ms)
-    couts = [m.out_channels for m in ms]
-    # (the instance is chosen by ldw: the concatenation must stay on the one the separate heads would use)
-    # (bf16 modes: heads narrower than 64 channels stay on the fp32 kernel -- _use_bf16 -- and are concatenated all the same)
-    if (not same or any(_use_bf16(m, xs) for m in ms) or xs[0].dtype != torch.float32 or len(xs) > 5 or
-            not all(supported(m0, x) for x in xs) or
-            (sum(couts) + 31) // 32 != 1 or _use_winograd(m0, xs)):
-        res = [conv_multi(m, xs) for m in ms]
-        return (res, None, None) if return_flat else res
-    (wp, ldw), b = ops.cached_pack(m0, 'cat', [t for m in ms for t in (m.weight, m.bias)], lambda: (
-        ops.pack_conv_weight(torch.cat([m.weight.detach() for m in ms], 0)),
-        None if m0.bias is None else torch.cat([m.bias.detach() for m in ms], 0)))
-    outs = ops.conv2d_nhwc_multi(xs, wp, ldw, b, sum(couts), m0.kernel_size[0], m0.stride[0], m0.padding[0], relu=False)
-    res, c0 = [], 0
-    for m, c in zip(ms, couts):
-        res.append([o[:, c0:c0 + c] for o in outs])
-        for x, y in zip(xs, res[-1]):
-            _trace('conv', module=m, x=x, out=y, relu=False, residual=None, residual_up=False, form='igemm multi cat')
-        c0 += c
-    if return_flat:
-        return res, getattr(outs[0], '_ups_flat', None), outs
-    return res
-
