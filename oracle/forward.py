@@ -29,13 +29,16 @@ def _cfg():
     return config
 
 
-def check_taps(taps, enable_void=True):
+def check_taps(taps, enable_void=True, thresholds=None):
     """Stage-by-stage parity on the tensors recorded during ONE product forward (model.taps):
     every custom-op stage is recomputed by the oracle from the recorded inputs of that stage and compared
     with the recorded outputs. Library convolutions / GEMMs are not re-executed, so their run-to-run
     non-determinism (MIOpen / hipBLASLt) cannot leak into the comparison.
+    thresholds: optional dict over THRESHOLD_KEYS (score_thresh, panoptic_score_thresh, max_det) that replaces the named fields of
+    config.test for the oracle's two detection selections, for a forward that ran with other knobs than the configuration's.
     Returns a dict name -> bool (all must be True) plus counters."""
     cfg = _cfg()
+    th = _thresholds(thresholds)
     C, S = cfg.dataset.num_classes, cfg.dataset.num_seg_classes
     im_info = np.asarray(taps['im_info'], np.float32).reshape(-1, 3)
     res = {}
@@ -49,10 +52,10 @@ def check_taps(taps, enable_void=True):
     res['proposals'] = (n == rois.shape[0]) and np.array_equal(got_rois, rois)
     # 2. detection selection (both variants) from the recorded box-head outputs
     cls_prob, bbox_pred = _np(taps['cls_prob'])[:n], _np(taps['bbox_pred'])[:n]
-    ds, db, dc = oops.mask_roi(got_rois, bbox_pred, cls_prob, im_info, C, cfg.test.nms_thresh, cfg.test.score_thresh,
-                               cfg.test.max_det, False, cfg.network.bbox_reg_weights)
-    ps, pb, pc = oops.mask_roi(got_rois, bbox_pred, cls_prob, im_info, C, 0.5, cfg.test.panoptic_score_thresh,
-                               cfg.test.max_det, True, cfg.network.bbox_reg_weights)
+    ds, db, dc = oops.mask_roi(got_rois, bbox_pred, cls_prob, im_info, C, cfg.test.nms_thresh, th['score_thresh'],
+                               th['max_det'], False, cfg.network.bbox_reg_weights)
+    ps, pb, pc = oops.mask_roi(got_rois, bbox_pred, cls_prob, im_info, C, 0.5, th['panoptic_score_thresh'],
+                               th['max_det'], True, cfg.network.bbox_reg_weights)
     res['mask_roi'] = (np.array_equal(_np(taps['det_boxes']), db) and np.array_equal(_np(taps['det_scores']), ds) and
                        np.array_equal(taps['det_cls'].cpu().numpy(), dc))
     res['mask_roi_panoptic'] = (np.array_equal(_np(taps['pan_boxes']), pb) and np.array_equal(_np(taps['pan_scores']), ps) and
@@ -69,6 +72,7 @@ def check_taps(taps, enable_void=True):
     res['panoptic'] = np.array_equal(taps['panoptic'].cpu().numpy()[0], head['panoptic'])
     res['semantic'] = np.array_equal(taps['sem'].cpu().numpy()[0], head['sem'])
     res['counts'] = dict(n_rois=n, n_det=int(db.shape[0]), n_pan=int(pb.shape[0]), n_inst=int(head['k']),
+                         classes=[int(c) for c in pc[head['keep_inds']]],
                          label_mismatch=int((taps['panoptic'].cpu().numpy()[0] != head['panoptic']).sum()))
     return res
 
@@ -147,21 +151,38 @@ def _fpn_pool_cpu(feats, rois, size):
     return torch.from_numpy(oops.fpn_roi_align([_np(f) for f in feats], rois, size, size))
 
 
-def forward_cpu(model_cpu, data, stage_times=None):
-    """Whole inference forward on the host. model_cpu: a CPU copy of the product model *before* BN folding or
-    after (both fine). Returns the reference's result dict as numpy arrays."""
+THRESHOLD_KEYS = ('score_thresh', 'panoptic_score_thresh', 'max_det')
+
+
+def _thresholds(thresholds):
+    """config.test's detection-selection knobs, each replaced by its entry in `thresholds` (a dict over THRESHOLD_KEYS) where given."""
+    t = _cfg().test
+    th = {k: t[k] for k in THRESHOLD_KEYS}
+    if thresholds:
+        unknown = sorted(set(thresholds) - set(THRESHOLD_KEYS))
+        if unknown:
+            raise KeyError("thresholds: unknown keys %s (known: %s)" % (unknown, list(THRESHOLD_KEYS)))
+        th.update(thresholds)
+    return th
+
+
+def _marker(stage_times):
     import time
-    cfg = _cfg()
-    C, S = cfg.dataset.num_classes, cfg.dataset.num_seg_classes
-    m = model_cpu
-    t0 = time.time()
+    t0 = [time.time()]
 
     def mark(name):
-        nonlocal t0
         if stage_times is not None:
-            stage_times[name] = stage_times.get(name, 0.0) + time.time() - t0
-        t0 = time.time()
+            stage_times[name] = stage_times.get(name, 0.0) + time.time() - t0[0]
+        t0[0] = time.time()
+    return mark
 
+
+def box_stage_cpu(model_cpu, data, stage_times=None):
+    """First half of forward_cpu: everything that does not depend on the selection thresholds (trunk, proposals, semantic head, box
+    head). Returns the dict that head_stage_cpu continues from; it is not modified there, so one box stage serves many head stages."""
+    cfg = _cfg()
+    m = model_cpu
+    mark = _marker(stage_times)
     with torch.no_grad():
         x = data['data'].float().cpu()
         res = _backbone_cpu(m.resnet_backbone, x)
@@ -197,10 +218,24 @@ def forward_cpu(model_cpu, data, stage_times=None):
         fc7 = m.rcnn.fc7(fc6)
         cls_prob = _np(F.softmax(m.rcnn.cls_score(fc7), dim=1))
         bbox_pred = _np(m.rcnn.bbox_pred(fc7))
-        ds, db, dc = oops.mask_roi(rois, bbox_pred, cls_prob, im_info, C, cfg.test.nms_thresh, cfg.test.score_thresh,
-                                   cfg.test.max_det, False, cfg.network.bbox_reg_weights)
-        ps, pb, pc = oops.mask_roi(rois, bbox_pred, cls_prob, im_info, C, 0.5, cfg.test.panoptic_score_thresh,
-                                   cfg.test.max_det, True, cfg.network.bbox_reg_weights)
+        mark('box_head_select')
+    return dict(feats=feats, rois=rois, im_info=im_info, fcn_output=_np(fcn_output), cls_prob=cls_prob, bbox_pred=bbox_pred)
+
+
+def head_stage_cpu(model_cpu, stage, stage_times=None, thresholds=None):
+    """Second half of forward_cpu from box_stage_cpu's dict: both detection selections, the mask head on their boxes and the panoptic
+    head. thresholds: see check_taps."""
+    cfg = _cfg()
+    C, S = cfg.dataset.num_classes, cfg.dataset.num_seg_classes
+    m = model_cpu
+    th = _thresholds(thresholds)
+    mark = _marker(stage_times)
+    feats, rois, im_info = stage['feats'], stage['rois'], stage['im_info']
+    with torch.no_grad():
+        ds, db, dc = oops.mask_roi(rois, stage['bbox_pred'], stage['cls_prob'], im_info, C, cfg.test.nms_thresh, th['score_thresh'],
+                                   th['max_det'], False, cfg.network.bbox_reg_weights)
+        ps, pb, pc = oops.mask_roi(rois, stage['bbox_pred'], stage['cls_prob'], im_info, C, 0.5, th['panoptic_score_thresh'],
+                                   th['max_det'], True, cfg.network.bbox_reg_weights)
         mark('box_head_select')
 
         def mask_head(boxes):
@@ -212,11 +247,19 @@ def forward_cpu(model_cpu, data, stage_times=None):
         ms = cfg.network.mask_size
         pan_logit = mask_head(pb).gather(1, torch.from_numpy(pc).view(-1, 1, 1, 1).expand(-1, -1, ms, ms))
         mark('mask_head')
-        head = oops.panoptic_head(_np(fcn_output), pb, ps, _np(pan_logit), pc, S, C, enable_void=m.enable_void)
+        head = oops.panoptic_head(stage['fcn_output'], pb, ps, _np(pan_logit), pc, S, C, enable_void=m.enable_void)
         mark('panoptic_head')
     return dict(cls_probs=ds, pred_boxes=db, mask_probs=_np(mask_prob), fcn_outputs=head['sem'], cls_inds=dc,
                 panoptic_cls_inds=head['cls_idx'], panoptic_cls_probs=ps[head['keep_inds']],
-                panoptic_outputs=head['panoptic'], n_rois=rois.shape[0], n_det=db.shape[0], n_inst=int(head['k']))
+                panoptic_outputs=head['panoptic'], n_rois=rois.shape[0], n_det=db.shape[0], n_inst=int(head['k']),
+                pan_boxes=pb, pan_scores=ps, pan_cls=pc, keep_inds=head['keep_inds'])
+
+
+def forward_cpu(model_cpu, data, stage_times=None, thresholds=None):
+    """Whole inference forward on the host. model_cpu: a CPU copy of the product model *before* BN folding or
+    after (both fine). Returns the reference's result dict as numpy arrays (plus the counts and the panoptic selection).
+    = head_stage_cpu(box_stage_cpu(...)); thresholds: see check_taps."""
+    return head_stage_cpu(model_cpu, box_stage_cpu(model_cpu, data, stage_times), stage_times, thresholds)
 
 
 def cpu_copy(model):

@@ -433,14 +433,10 @@ def rle_counts(mask):
     """pycocotools rleEncode (common/maskApi.c, pycocotools 2.0 -- third-party, not in /root/reference: published algorithm
     restated): column-major run lengths, alternating zeros / ones, starting with the (possibly empty) run of zeros."""
     flat = np.asarray(mask, np.uint8).reshape(-1, order='F')
-    counts, prev, run = [], 0, 0
-    for v in flat:
-        if v != prev:
-            counts.append(run)
-            run, prev = 0, v
-        run += 1
-    counts.append(run)
-    return counts
+    # run boundaries where the value changes (array form of the scan `if v != prev: close the run`, prev starting at 0)
+    bounds = np.concatenate([[0], np.flatnonzero(flat[1:] != flat[:-1]) + 1, [flat.size]])
+    counts = np.diff(bounds).tolist()
+    return [0] + counts if flat.size and flat[0] != 0 else counts
 
 
 def rle_to_string(counts):

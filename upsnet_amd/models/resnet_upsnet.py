@@ -252,7 +252,7 @@ class resnet_upsnet(resnet_rcnn):
         cls_prob = F.softmax(rcnn_output['cls_score'], dim=1)
         bbox_pred = rcnn_output['bbox_pred']
         self._tap(rpn_cls_prob=rpn_cls_prob, rpn_bbox_pred=rpn_bbox_pred,
-                  im_info=im_info, rois=rois, n_rois=n_rois, cls_prob=cls_prob, bbox_pred=bbox_pred)
+                  im_info=im_info, rois=rois, n_rois=n_rois, cls_prob=cls_prob, bbox_pred=bbox_pred, feats=feats)
         # both detection selections are launched back to back; ONE host read of the counters (in forward)
         det_boxes, det_scores, det_cls, det_src, det_num = self.mask_roi.forward_padded(rois, bbox_pred, cls_prob, im_info, n_rois)
         # The mask head of the per-class detections starts as soon as they exist -- on the side stream (idle once the semantic
@@ -475,7 +475,7 @@ class resnet_upsnet(resnet_rcnn):
         cls_prob = F.softmax(cls_score, dim=1)
         self._tap(rpn_cls_prob=rpn_cls_prob, rpn_bbox_pred=rpn_bbox_pred,
                   im_info=im_info, rois=rois, n_rois=rois.shape[0], cls_prob=cls_prob, bbox_pred=bbox_pred,
-                  fcn_output=fcn_output['fcn_output'])
+                  fcn_output=fcn_output['fcn_output'], feats=feats)
 
         cls_prob_all, mask_rois, cls_idx = self.mask_roi(rois, bbox_pred, cls_prob, im_info)
         mask_score = self.mask_branch(feats, mask_rois)
