@@ -1108,6 +1108,27 @@ int upsnet_tta_boxes_to_aug(void *stream, int num_aug, const float q[], const fl
 int upsnet_tta_mask_merge(void *stream, int num_aug, const float *const logits[], const int flip[], int num_rois, int num_classes,
                           int mask_size, int nhwc, float *out);
 
+/* ============================== Box voting ============================== */
+
+/* Score-weighted box voting on the output of upsnet_mask_roi(_ex) (Detectron's TEST.BBOX_VOTE, `ID` scoring; the reference has none).
+ * Inputs: the selection's own rois [num_rois,5], bbox_delta [num_rois,4*num_classes], cls_prob [num_rois,num_classes], the optional
+ * DEVICE row count num_rois_dev (clamped to 0..num_rois; NULL: num_rois), im_info, clip_boxes and reg_weights_host; its outputs boxes
+ * [cap,5], cls [cap] int64 and the DEVICE count num. voted [cap,5] is caller-allocated and must not overlap boxes.
+ *   For k < max(*num, 0) (clamped to cap), c = cls[k] (clamped to 0..num_classes-1), b = boxes[k,1:5]: row r < n is a voter when
+ *   cls_prob[r,c] > vote_score_thresh and iou(b, d_r) >= vote_iou_thresh, d_r the class-c decode (+ clip) of row r exactly as the
+ *   selection builds its candidates, iou the "+1" IoU; a NaN IoU is no voter. Five fp32 sums S_w = sum w_r, S_i = sum w_r * d_r[i],
+ *   w_r = cls_prob[r,c], each term one rounded multiply: partial j (0..63) starts at +0 and adds the voters with r % 64 == j in
+ *   ascending r; then for s = 32,16,8,4,2,1: p[j] = p[j] + p[j+s] (j < s); the sum is p[0].
+ *   S_w > 0: voted[k,1+i] = S_i / S_w, with clip_boxes clamped again to [0, im_w-1] / [0, im_h-1]; otherwise voted[k,1:5] = b.
+ *   voted[k,0] = boxes[k,0].
+ *   Rows max(*num, 0) <= k < cap are a bit copy of boxes[k] (a negative *num, the selection's overflow marker, copies every row).
+ * One launch; nothing is synchronised or allocated. Refused before any launch: a null pointer, num_rois <= 0, num_classes < 2,
+ * cap < 0, vote_iou_thresh NaN or <= 0. cap = 0 launches nothing (boxes / cls / voted may be NULL). */
+int upsnet_box_vote(void *stream, const float *rois, const float *bbox_delta, const float *cls_prob, int num_rois,
+                    const int *num_rois_dev, int num_classes, const float *im_info, int clip_boxes, const float reg_weights_host[4],
+                    float vote_score_thresh, float vote_iou_thresh, const float *boxes, const int64_t *cls, const int *num, int cap,
+                    float *voted);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,7 @@ _SIGNATURES = {
     "upsnet_tta_roi_union": (c_int, [P, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
     "upsnet_tta_boxes_to_aug": (c_int, [P, c_int, P, P, P, P, c_int, P]),
     "upsnet_tta_mask_merge": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
+    "upsnet_box_vote": (c_int, [P, P, P, P, c_int, P, c_int, P, c_int, P, c_float, c_float, P, P, P, c_int, P]),
 }
 
 _lib = None

@@ -88,6 +88,11 @@ config.test.vis_mask = False          # upsnet_end2end_test.py:172-173, 300-301:
 # beside scales[0], and whether every scale is also run mirrored left to right. Both off: the plain single-scale forward.
 config.test.aug_scales = []
 config.test.aug_flip = False
+# box voting on the augmented (eager) path (csrc/box_vote.hip; the reference has none): every kept detection box becomes
+# the score-weighted mean of the candidates of its class above test.score_thresh whose IoU with it is >= bbox_vote_thresh. On its own
+# (no aug_scales / aug_flip) the evaluation run takes the eager path with the base augmentation alone.
+config.test.bbox_vote = False
+config.test.bbox_vote_thresh = 0.8
 
 
 def _merge(dst, src):

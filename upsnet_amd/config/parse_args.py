@@ -82,6 +82,11 @@ def parse_args(description='', argv=None):
                         'max size scales along); merged on the device')
     parser.add_argument('--aug_flip', action='store_true',
                         help='sets config.test.aug_flip: test-time augmentation, every scale also mirrored left to right')
+    parser.add_argument('--bbox_vote', action='store_true',
+                        help='sets config.test.bbox_vote: every kept detection box becomes the score-weighted mean of the candidates of '
+                        'its class that overlap it (box voting, on the device); the run is the eager one of the test-time augmentation')
+    parser.add_argument('--bbox_vote_thresh', type=float, default=None, metavar='T',
+                        help='with --bbox_vote: sets config.test.bbox_vote_thresh, the IoU from which a candidate votes (default 0.8)')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)
@@ -91,6 +96,12 @@ def parse_args(description='', argv=None):
         config.test.aug_scales = list(args.aug_scales)
     if args.aug_flip:
         config.test.aug_flip = True
+    if args.bbox_vote:
+        config.test.bbox_vote = True
+    if args.bbox_vote_thresh is not None:
+        if not config.test.get('bbox_vote', False):
+            parser.error('--bbox_vote_thresh sets the IoU threshold of --bbox_vote, which is missing')
+        config.test.bbox_vote_thresh = float(args.bbox_vote_thresh)
     if rest:    # (the reference re-parses strictly, parse_args.py:32; an option neither parser knows is reported, not swallowed)
         parser.error('unrecognized arguments: %s' % ' '.join(rest))
     return args

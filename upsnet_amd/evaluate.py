@@ -7,6 +7,7 @@
                                   [--vis_panoptic {flat,overlay,both} [--vis_panoptic_min_area N]]
                                   [--write_instances [--instances_1bit]] [--eval_boundary [--boundary_dilation_ratio R]]
                                   [--eval_boundary_pq [--boundary_pq_dilation_ratio R]] [--aug_scales S [S ...]] [--aug_flip]
+                                  [--bbox_vote [--bbox_vote_thresh T]]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>] [--eval_boundary_pq ...]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
     python -m upsnet_amd.evaluate --cfg <yaml> --score_instances <folder>
@@ -51,6 +52,11 @@ image set without ground truth (dataset/pan_vis.py; the paths come 
 `test.aug_scales` / `test.aug_flip` in the yaml) turn on multi-scale / flip test-time augmentation (upsnet_amd/tta.py): every
 image runs once per augmentation, eagerly and with one image in flight, the results are merged on the device in the base frame, and the
 results pickle also carries 'test_aug', the augmentation list; `--eval_proposals` is refused with it (there is no single proposal list).
+`--bbox_vote [--bbox_vote_thresh T]` (or `test.bbox_vote` / `test.bbox_vote_thresh` in the yaml) turns on box voting (csrc/box_vote.hip,
+DESIGN 4.21): every kept detection box, class-wise and panoptic, becomes the score-weighted mean of the candidates of its class above
+`test.score_thresh` whose IoU with it is >= T (default 0.8); scores, classes and order stay. Voting lives on the eager path of the
+augmentation: on its own it runs that path with the base augmentation alone; the results pickle also carries 'bbox_vote',
+[score_thresh, T]; `--eval_proposals` is refused with it as well.
 One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
@@ -136,10 +142,11 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
     all_ssegs = [] if net.has_fcn_head else None
     all_panos, all_pano_cls_inds = ([], []) if net.has_panoptic_head else (None, None)
     all_proposals = [] if keep_proposals else None
-    from .tta import augmentation_enabled, augmentation_list
-    test_aug = augmentation_list() if augmentation_enabled() else None
+    from .tta import augmentation_list, bbox_vote_params, eager_path_enabled
+    test_aug = augmentation_list() if eager_path_enabled() else None     # (box voting alone: the base augmentation, eagerly)
+    bbox_vote = bbox_vote_params()
     if test_aug is not None and keep_proposals:
-        raise ValueError('keep_proposals with test-time augmentation: there is no single proposal list to keep')
+        raise ValueError('keep_proposals with test-time augmentation or box voting: there is no single proposal list to keep')
     if keep_proposals:
         model.keep_proposals = True
     depth = max(1, min(int(in_flight), getattr(model, 'graph_slots', 1))) if hasattr(model, 'forward_async') else 1
@@ -196,6 +203,8 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
         results['all_proposals'] = all_proposals
     if test_aug is not None:
         results['test_aug'] = [list(a) for a in test_aug]
+    if bbox_vote is not None:
+        results['bbox_vote'] = list(bbox_vote)
     return results, times
 
 
@@ -379,15 +388,22 @@ def main(argv=None):
     if args.score_instances and config.dataset.dataset != 'Cityscapes':     # (no model is built: the heads do not matter)
         raise SystemExit('--score_instances scores instance prediction files against the Cityscapes gtFine instanceIds maps: it needs '
                          'dataset.dataset = Cityscapes (dataset=%s)' % config.dataset.dataset)
-    from .tta import augmentation_enabled, augmentation_list
-    if augmentation_enabled() and not (args.eval_only or args.score_panoptic or args.score_ssegs or args.score_instances):
-        if args.eval_proposals:
+    from .tta import augmentation_enabled, augmentation_list, bbox_vote_params, eager_path_enabled
+    if eager_path_enabled() and not (args.eval_only or args.score_panoptic or args.score_ssegs or args.score_instances):
+        if args.eval_proposals and augmentation_enabled():
             raise SystemExit('--eval_proposals with test-time augmentation (--aug_scales / --aug_flip) is refused: the detections come from '
                              'the union of every augmentation\'s proposals, so there is no single proposal list to score')
+        if args.eval_proposals:
+            raise SystemExit('--eval_proposals with box voting (--bbox_vote) is refused: voting runs on the eager path of the test-time '
+                             'augmentation, which keeps no single proposal list to score')
         try:
             augmentation_list()
         except ValueError as e:
             raise SystemExit('--aug_scales / --aug_flip: %s' % e)
+        try:
+            bbox_vote_params()
+        except ValueError as e:
+            raise SystemExit('--bbox_vote_thresh: %s' % e)
     vis_mask = bool(config.test.get('vis_mask', False))
     if vis_mask and not (net.has_rcnn and net.has_mask_head):
         raise SystemExit('--vis_mask (config.test.vis_mask) draws the detections and their instance masks: it needs network.has_rcnn and '

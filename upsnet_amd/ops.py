@@ -1910,3 +1910,11 @@ def tta_mask_merge(logits, flip):
     """tta.py: the augmentations' mask logits averaged, flipped ones mirrored left to right."""
     from . import tta as impl
     return impl.mask_merge(logits, flip)
+
+
+def box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_thresh, vote_iou_thresh, reg_weights,
+             num_rois_dev=None, clip_boxes=True):
+    """tta.py: score-weighted box voting on the output of mask_roi, voted [cap,5] (csrc/box_vote.hip)."""
+    from . import tta as impl
+    return impl.box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_thresh, vote_iou_thresh, reg_weights,
+                         num_rois_dev, clip_boxes)

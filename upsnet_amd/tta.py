@@ -9,6 +9,10 @@ tensors. The three merges are the kernels of csrc/tta.hip (ops.tta_*); everythin
     config.test.aug_scales = [S, ...]     further target sizes beside config.test.scales[0]
     config.test.aug_flip = True           every scale also mirrored left to right
 
+    config.test.bbox_vote = True          box voting (csrc/box_vote.hip): every kept detection box becomes the
+                                          score-weighted mean of the candidates of its class above test.score_thresh whose IoU with
+                                          it is >= test.bbox_vote_thresh; on its own it runs this path with the base augmentation alone
+
 The run is eager: no HIP graph, one image in flight. All outputs are in the base frame (the first augmentation, the plain forward's
 input), so evaluate.post_image takes them with the base im_info. Whether the augmentations raise PQ has not been measured: no trained
 checkpoint exists here."""
@@ -25,7 +29,7 @@ MAX_AUG = ops.TTA_MAX_AUG
 MAX_UNION_ROWS = 8192     # candidate rows the device detection selection takes (csrc/detect.hip)
 
 
-# ------------------------------------------------------------------------------------------------ the four launches (csrc/tta.hip)
+# ------------------------------------------------------------------------- the four merge launches (csrc/tta.hip), the vote (csrc/box_vote.hip)
 def _tta_count(num_aug, what):
     if not 1 <= num_aug <= MAX_AUG:
         raise ValueError("%s: 1..%d augmentations (got %d)" % (what, MAX_AUG, num_aug))
@@ -114,10 +118,53 @@ def mask_merge(logits, flip):
     return out
 
 
+def box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_thresh, vote_iou_thresh, reg_weights,
+             num_rois_dev=None, clip_boxes=True):
+    """Score-weighted box voting (csrc/box_vote.hip) on the output of mask_roi: boxes [cap,5], cls [cap] int64, num device
+    int32, with the rois / bbox_delta / cls_prob / im_info / reg_weights / num_rois_dev / clip_boxes the selection was given. Returns
+    voted [cap,5]: row k < num is the mean of the class-cls[k] candidates with cls_prob > vote_score_thresh and IoU >= vote_iou_thresh
+    with boxes[k], weighted by cls_prob; rows from num on are copies. One launch, no host read."""
+    require_cuda(rois, bbox_delta, cls_prob, im_info, boxes, cls, num)
+    rois, bbox_delta, cls_prob, boxes, cls = f32c(rois), f32c(bbox_delta), f32c(cls_prob), f32c(boxes), cls.contiguous()
+    N, C = cls_prob.shape
+    cap = boxes.shape[0]
+    if tuple(rois.shape) != (N, 5) or bbox_delta.dim() != 2 or tuple(bbox_delta.shape) != (N, 4 * C):
+        raise ValueError("box_vote: rois %s / bbox_delta %s do not go with cls_prob %s (class-wise deltas: [N,5], [N,4C], [N,C])"
+                         % (tuple(rois.shape), tuple(bbox_delta.shape), (N, C)))
+    if boxes.dim() != 2 or boxes.shape[1] != 5 or tuple(cls.shape) != (cap,) or cls.dtype != torch.int64:
+        raise ValueError("box_vote: boxes must be [cap,5] and cls int64 [cap], got %s and %s %s" % (tuple(boxes.shape), cls.dtype, tuple(cls.shape)))
+    if num.dtype != torch.int32 or num.numel() != 1 or (num_rois_dev is not None and (num_rois_dev.dtype != torch.int32 or num_rois_dev.numel() != 1)):
+        raise ValueError("box_vote: the counts must be one int32 each")
+    voted = torch.empty((cap, 5), dtype=torch.float32, device=boxes.device)
+    check(lib().upsnet_box_vote(stream(), ptr(rois), ptr(bbox_delta), ptr(cls_prob), N, ptr(num_rois_dev), C,
+                                ptr(f32c(im_info.reshape(-1))), int(bool(clip_boxes)), float_array(reg_weights), float(vote_score_thresh),
+                                float(vote_iou_thresh), ptr(boxes) if cap else None, ptr(cls) if cap else None, ptr(num), cap,
+                                ptr(voted) if cap else None), "box_vote")
+    return voted
+
+
 # ------------------------------------------------------------------------------------------------ the augmented forward
 def augmentation_enabled(cfg=None):
     t = (config if cfg is None else cfg).test
     return bool(list(t.get('aug_scales', []) or [])) or bool(t.get('aug_flip', False))
+
+
+def bbox_vote_params(cfg=None):
+    """(vote_score_thresh, vote_iou_thresh) when config.test.bbox_vote is on, else None. The score threshold is always
+    test.score_thresh, for the class-wise and the panoptic selection alike."""
+    t = (config if cfg is None else cfg).test
+    if not t.get('bbox_vote', False):
+        return None
+    iou = float(t.get('bbox_vote_thresh', 0.8))
+    if not iou > 0.0:
+        raise ValueError("test.bbox_vote_thresh must be a positive IoU (got %r)" % (t.get('bbox_vote_thresh'),))
+    return float(t.score_thresh), iou
+
+
+def eager_path_enabled(cfg=None):
+    """Whether the evaluation run goes through forward_tta: test-time augmentation, or box voting (which lives on that path only; on
+    its own it runs the base augmentation alone)."""
+    return augmentation_enabled(cfg) or bool((config if cfg is None else cfg).test.get('bbox_vote', False))
 
 
 def augmentation_list(cfg=None):
@@ -161,6 +208,7 @@ def forward_tta(model, image_u8_bgr, device=None, return_parts=False):
     tensors, the merged tensors, the selections and the final boxes (what the tests check each merge from)."""
     from .dataset.blob import get_image_blob
     augs = augmentation_list()
+    vote = bbox_vote_params()
     if getattr(model, 'keep_proposals', False):
         raise ValueError("keep_proposals (--eval_proposals) with test-time augmentation: there is no single proposal list to keep")
     if isinstance(image_u8_bgr, np.ndarray):
@@ -190,11 +238,22 @@ def forward_tta(model, image_u8_bgr, device=None, return_parts=False):
                                                       [s[3] for s in stages], r, wr, flips)
         det_boxes, det_scores, det_cls, det_src, det_num = model.mask_roi.forward_padded(rois, delta, prob, im_info0, n_rois)
         pan_boxes, pan_scores, pan_cls, pan_src, pan_num = model.mask_roi_panoptic.forward_padded(rois, delta, prob, im_info0, n_rois)
+        det_boxes_prevote, pan_boxes_prevote = det_boxes, pan_boxes
+        if vote is not None:
+            # both kept lists voted on the union, before the dedup: it pairs rows by (source ROI, class), and such rows get
+            # the same voted box from either list, so extra_boxes come out voted and "same ROI, same class, same mask logits" holds
+            w = config.network.bbox_reg_weights
+            im0 = torch.from_numpy(im_infos[0].copy()).to(rois.device, non_blocking=True)
+            det_boxes = ops.box_vote(rois, delta, prob, im0, det_boxes, det_cls, det_num, vote[0], vote[1], w, n_rois,
+                                     clip_boxes=bool(model.mask_roi.clip_boxes))
+            pan_boxes = ops.box_vote(rois, delta, prob, im0, pan_boxes, pan_cls, pan_num, vote[0], vote[1], w, n_rois,
+                                     clip_boxes=bool(model.mask_roi_panoptic.clip_boxes))
         pan_row, extra_boxes, extra_num = ops.mask_roi_dedup(det_src, det_cls, det_num, pan_src, pan_cls, pan_boxes, pan_num)
         n_det, n_pan, n_extra = torch.cat([det_num, pan_num, extra_num]).tolist()
         check_count(n_det), check_count(n_pan)
         det_boxes, det_scores, det_cls = det_boxes[:n_det], det_scores[:n_det], det_cls[:n_det]
         pan_boxes, pan_scores, pan_cls = pan_boxes[:n_pan], pan_scores[:n_pan], pan_cls[:n_pan]
+        det_boxes_prevote, pan_boxes_prevote = det_boxes_prevote[:n_det], pan_boxes_prevote[:n_pan]
 
         boxes = torch.cat([det_boxes, extra_boxes[:n_extra]], 0) if n_extra else det_boxes
         n = boxes.shape[0]
@@ -215,7 +274,8 @@ def forward_tta(model, image_u8_bgr, device=None, return_parts=False):
                  merged_score=score, merged_rois=rois, merged_delta=delta, merged_prob=prob, merged_n_rois=n_rois,
                  merged_mask_logits=mask_score, boxes=boxes, n_det=n_det, n_pan=n_pan, n_extra=n_extra,
                  det_boxes=det_boxes, det_scores=det_scores, det_cls=det_cls, pan_boxes=pan_boxes, pan_scores=pan_scores,
-                 pan_cls=pan_cls, pan_row=pan_row, extra_boxes=extra_boxes)
+                 pan_cls=pan_cls, pan_row=pan_row, extra_boxes=extra_boxes, det_boxes_prevote=det_boxes_prevote,
+                 pan_boxes_prevote=pan_boxes_prevote, bbox_vote=vote)
     return out, parts
 
 
