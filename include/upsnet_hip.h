@@ -1129,6 +1129,27 @@ int upsnet_box_vote(void *stream, const float *rois, const float *bbox_delta, co
                     float vote_score_thresh, float vote_iou_thresh, const float *boxes, const int64_t *cls, const int *num, int cap,
                     float *voted);
 
+/* ============================== Soft detection selection ============================== */
+
+/* upsnet_mask_roi_ex, class-wise, with soft-NMS in place of the hard NMS (Detectron's TEST.SOFT_NMS; the reference's own call sites,
+ * bbox_transform.py:271-288, are unreachable). Inputs and outputs as upsnet_mask_roi_ex with class_agnostic = 0:
+ * cap = upsnet_mask_roi_capacity(num_rois, num_classes, 0); num_rois_dev is clamped to 0..num_rois.
+ *   Per class c = 1..C-1: the candidates are the rows r < n with cls_prob[r,c] > score_thresh, ascending r, box = the class-c decode
+ *   (+ clip) of row r, score = cls_prob[r,c]; on that list cpu_soft_nms(dets, sigma, Nt = nms_thresh, threshold = floor, method)
+ *   (cpu_nms.pyx:91-196, bit-identical; method 0 hard, 1 linear, 2 gaussian). The class's result is rows 0..N'-1 of the returned
+ *   array in that order: box, DECAYED score, source row. The flat list in (class ascending, soft-NMS order) then goes through the
+ *   top-max_det rule of upsnet_mask_roi on the decayed scores (max_det > 0 and more than max_det rows: keep score >= the max_det-th
+ *   largest, order preserved), the dummy row when nothing survives and the zero rows up to max(max_det, 256).
+ *   A class's state is LDS-resident: it holds at most 4096 candidates. A class with more keeps its first 4096 and the count comes
+ *   out NEGATIVE (the overflow convention of upsnet_mask_roi); with num_rois <= 4096 this cannot happen.
+ * Two launches (one workgroup per class, then the finalize); nothing is synchronised or allocated. Refused before any launch: a null
+ * pointer, num_rois < 1 or > 8192, num_classes < 2, method outside 0..2, sigma not > 0 with method 2, a NaN nms_thresh or floor. */
+size_t upsnet_mask_roi_soft_workspace_bytes(int num_rois, int num_classes);
+int upsnet_mask_roi_soft(void *stream, const float *rois, const float *bbox_delta, const float *cls_prob, int num_rois,
+                         const int *num_rois_dev, int num_classes, const float *im_info, int clip_boxes, float score_thresh,
+                         float nms_thresh, int max_det, const float reg_weights_host[4], int method, float sigma, float floor_thresh,
+                         float *boxes_out, float *scores_out, int64_t *cls_out, int *src_out, int *num_out, void *workspace);
+
 #ifdef __cplusplus
 }
 #endif

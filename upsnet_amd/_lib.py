@@ -179,6 +179,8 @@ _SIGNATURES = {
     "upsnet_tta_boxes_to_aug": (c_int, [P, c_int, P, P, P, P, c_int, P]),
     "upsnet_tta_mask_merge": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
     "upsnet_box_vote": (c_int, [P, P, P, P, c_int, P, c_int, P, c_int, P, c_float, c_float, P, P, P, c_int, P]),
+    "upsnet_mask_roi_soft_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "upsnet_mask_roi_soft": (c_int, [P, P, P, P, c_int, P, c_int, P, c_int, c_float, c_float, c_int, P, c_int, c_float, c_float, P, P, P, P, P, P]),
 }
 
 _lib = None

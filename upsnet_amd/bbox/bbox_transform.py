@@ -71,3 +71,20 @@ def bbox_overlaps(boxes, query_boxes):
     area_b = (b[:, 2] - b[:, 0] + 1) * (b[:, 3] - b[:, 1] + 1)
     area_q = (q[:, 2] - q[:, 0] + 1) * (q[:, 3] - q[:, 1] + 1)
     return inter / (area_b[:, None] + area_q[None, :] - inter)
+
+
+def soft_nms(dets, sigma=0.5, overlap_thresh=0.3, score_thresh=0.001, method='linear'):
+    """Detectron's soft-NMS wrapper with the reference's signature (bbox_transform.py:271-288, which calls an undefined cython_nms):
+    dets [n,5] float32 (x1, y1, x2, y2, score) -> (dets', keep), the rescored survivors in cpu_soft_nms's order and their input
+    rows. Runs on the device (ops.soft_nms)."""
+    if dets.shape[0] == 0:
+        return dets, []
+    numbering = ('hard', 'linear', 'gaussian')          # cpu_soft_nms's method argument
+    if method not in numbering:
+        raise ValueError('soft_nms: method must be one of %s (got %r)' % (numbering, method))
+    import torch
+    from .. import ops
+    t = torch.from_numpy(np.ascontiguousarray(dets, dtype=np.float32)).cuda()
+    out, keep = ops.soft_nms(t, np.float32(sigma), np.float32(overlap_thresh), np.float32(score_thresh), numbering.index(method))
+    keep = keep.cpu().numpy()
+    return out[:len(keep)].cpu().numpy(), keep

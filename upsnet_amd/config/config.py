@@ -93,6 +93,14 @@ config.test.aug_flip = False
 # (no aug_scales / aug_flip) the evaluation run takes the eager path with the base augmentation alone.
 config.test.bbox_vote = False
 config.test.bbox_vote_thresh = 0.8
+# soft-NMS in the class-wise detection selection of the augmented (eager) path (csrc/detect.hip mroi_soft_kernel; Detectron's
+# TEST.SOFT_NMS): a candidate that overlaps a kept one stays with a decayed score ('linear': x (1 - IoU) above test.nms_thresh;
+# 'gaussian': x exp(-IoU^2 / sigma)) and is dropped only below soft_nms_score_thresh. The panoptic selection stays hard NMS. On its
+# own (no aug_scales / aug_flip) the evaluation run takes the eager path with the base augmentation alone.
+config.test.soft_nms = False
+config.test.soft_nms_method = 'linear'
+config.test.soft_nms_sigma = 0.5
+config.test.soft_nms_score_thresh = 0.0001
 
 
 def _merge(dst, src):

@@ -87,6 +87,13 @@ def parse_args(description='', argv=None):
                         'its class that overlap it (box voting, on the device); the run is the eager one of the test-time augmentation')
     parser.add_argument('--bbox_vote_thresh', type=float, default=None, metavar='T',
                         help='with --bbox_vote: sets config.test.bbox_vote_thresh, the IoU from which a candidate votes (default 0.8)')
+    parser.add_argument('--soft_nms', action='store_true',
+                        help='sets config.test.soft_nms: the class-wise detection selection keeps overlapping candidates with a decayed '
+                        'score instead of dropping them (soft-NMS, on the device); the run is the eager one of the test-time augmentation')
+    parser.add_argument('--soft_nms_method', choices=('linear', 'gaussian'), default=None, metavar='M',
+                        help='with --soft_nms: sets config.test.soft_nms_method, linear (default) or gaussian')
+    parser.add_argument('--soft_nms_sigma', type=float, default=None, metavar='S',
+                        help='with --soft_nms: sets config.test.soft_nms_sigma, the width of the gaussian decay (default 0.5)')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)
@@ -102,6 +109,13 @@ def parse_args(description='', argv=None):
         if not config.test.get('bbox_vote', False):
             parser.error('--bbox_vote_thresh sets the IoU threshold of --bbox_vote, which is missing')
         config.test.bbox_vote_thresh = float(args.bbox_vote_thresh)
+    if args.soft_nms:
+        config.test.soft_nms = True
+    for name in ('soft_nms_method', 'soft_nms_sigma'):
+        if getattr(args, name) is not None:
+            if not config.test.get('soft_nms', False):
+                parser.error('--%s is a parameter of --soft_nms, which is missing' % name)
+            config.test[name] = getattr(args, name)
     if rest:    # (the reference re-parses strictly, parse_args.py:32; an option neither parser knows is reported, not swallowed)
         parser.error('unrecognized arguments: %s' % ' '.join(rest))
     return args

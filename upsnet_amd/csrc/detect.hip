@@ -7,6 +7,7 @@
 // workgroup applies the global top-max_det rule (radix select of the max_det-th largest score, `>=`
 // keep, order preserved) and writes the result, including the reference's dummy ROI when empty.
 #include "common.h"
+#include "soft_nms_trips.h"
 #include "sort.h"
 #include "upsnet_hip.h"
 
@@ -270,6 +271,150 @@ extern "C" int upsnet_mask_roi(void *stream, const float *rois, const float *bbo
     return upsnet_mask_roi_ex(stream, rois, bbox_delta, cls_prob, num_rois, num_rois_dev, num_classes, im_info, class_agnostic, 1,
                               score_thresh, nms_thresh, max_det, reg_weights, boxes_out, scores_out, cls_out, src_out, num_out,
                               workspace);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Soft detection selection (Detectron's TEST.SOFT_NMS on the class-wise selection). ONE workgroup per class builds the
+// class's candidate list in ROI order straight into the LDS structure-of-arrays of the soft-NMS (decode on the fly, ordered compaction
+// with ballots), runs the sequential trips there (snms_lds_trips, the body soft_nms_lds_kernel runs) and writes the survivors -- box,
+// DECAYED score, source row, class -- compacted at rows 0..N'-1 of the class's workspace slice with an identity keep list, so that
+// mroi_finalize_kernel applies the top-max_det rule, the dummy row, the zero fill and the overflow marker exactly as on the hard path.
+// A class holds at most SNMS_LDS_MAX candidates (its state is LDS-resident): a class with more keeps its first SNMS_LDS_MAX and sets
+// the status word, which the finalize turns into a negative count. T = 64 up to 1024 rows (no real barriers), 256 above.
+template <int T>
+__global__ void __launch_bounds__(T)
+mroi_soft_kernel(const float *__restrict__ rois, const float *__restrict__ delta, const float *__restrict__ prob, const int num_rois,
+                 const int *__restrict__ num_rois_dev, const int C, const float *__restrict__ im_info, const int clip,
+                 const float score_thresh, const float wx, const float wy, const float ww, const float wh, const int nmax,
+                 const int cap, const float sigma, const float Nt, const float floor_thresh, const int method,
+                 float *__restrict__ cboxes, float *__restrict__ cscores, int *__restrict__ csrc, int *__restrict__ ccls,
+                 int *__restrict__ keep_idx, int *__restrict__ keep_cnt, int *__restrict__ status)
+{
+    constexpr int W = T / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    __shared__ SnmsScratch<T> scratch;
+    __shared__ int s_cnt[W];
+    const SnmsState s = snms_carve(smem_raw, cap);
+    const int p = blockIdx.x, c = p + 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int N = min(max(num_rois_dev ? *num_rois_dev : num_rois, 0), num_rois);
+    const int limit = min(nmax, SNMS_LDS_MAX);      // (<= cap)
+    const float im_h = im_info[0], im_w = im_info[1];
+    // ---- 1. the class's candidates, rows ascending, into the LDS state
+    int cnt = 0;
+    bool overflow = false;
+    for (int base = 0; base < N; base += T) {
+        const int r = base + tid;
+        float sc = 0.f;
+        bool flag = false;
+        if (r < N) { sc = prob[(long)r * C + c]; flag = sc > score_thresh; }
+        const unsigned long long bal = __ballot(flag);
+        int pos = cnt + __builtin_popcountll(bal & ((1ULL << lane) - 1ULL)), tot = __builtin_popcountll(bal);
+        if (W > 1) {
+            if (lane == 0) s_cnt[wave] = tot;
+            __syncthreads();
+            tot = 0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) { const int v = s_cnt[w]; if (w < wave) pos += v; tot += v; }
+            __syncthreads();
+        }
+        if (flag) {
+            if (pos < limit) {
+                const float *rr = rois + (long)r * 5;
+                const float *d = delta + (long)r * 4 * C + 4 * c;
+                float o[4];
+                ups_decode_clip(rr[1], rr[2], rr[3], rr[4], d[0], d[1], d[2], d[3], wx, wy, ww, wh, im_h, im_w, clip != 0, o);
+                s.x1[pos] = o[0]; s.y1[pos] = o[1]; s.x2[pos] = o[2]; s.y2[pos] = o[3]; s.sc[pos] = sc;
+                s.ind[pos] = r;
+            } else {
+                overflow = true;
+            }
+        }
+        cnt += tot;
+    }
+    if (overflow) atomicOr(status, 1);
+    __syncthreads();
+    // ---- 2. the trips
+    const int kept = snms_lds_trips<T>(s, scratch, min(cnt, limit), sigma, Nt, floor_thresh, method);
+    // ---- 3. survivors in the reference's order, identity keep list
+    const long row0 = (long)p * nmax;
+    for (int q = tid; q < kept; q += T) {
+        float *b = cboxes + (row0 + q) * 4;
+        b[0] = s.x1[q]; b[1] = s.y1[q]; b[2] = s.x2[q]; b[3] = s.y2[q];
+        cscores[row0 + q] = s.sc[q];
+        csrc[row0 + q] = s.ind[q];
+        ccls[row0 + q] = c;
+        keep_idx[row0 + q] = q;
+    }
+    if (tid == 0) keep_cnt[p] = kept;
+}
+
+struct MroiSoftPlan { size_t boxes, scores, src, cls, keep, keepcnt, status, flat, total; };
+static MroiSoftPlan mroi_soft_plan(int P, int nmax)
+{
+    MroiSoftPlan m; size_t o = 0;
+    m.boxes = o; o += al256((size_t)P * nmax * 16);
+    m.scores = o; o += al256((size_t)P * nmax * 4);
+    m.src = o; o += al256((size_t)P * nmax * 4);
+    m.cls = o; o += al256((size_t)P * nmax * 4);
+    m.keep = o; o += al256((size_t)P * nmax * 4);
+    m.keepcnt = o; o += al256((size_t)P * 4);
+    m.status = o; o += 256;
+    m.flat = o; o += al256((size_t)P * nmax * 4);
+    m.total = o + 256;
+    return m;
+}
+
+extern "C" size_t upsnet_mask_roi_soft_workspace_bytes(int N, int C)
+{
+    if (N < 1 || C < 2 || N > 8192) return 256;
+    int P, nmax;
+    mroi_dims(N, C, 0, &P, &nmax);
+    return mroi_soft_plan(P, nmax).total;
+}
+
+extern "C" int upsnet_mask_roi_soft(void *stream, const float *rois, const float *bbox_delta, const float *cls_prob, int num_rois,
+                                    const int *num_rois_dev, int num_classes, const float *im_info, int clip_boxes, float score_thresh,
+                                    float nms_thresh, int max_det, const float reg_weights[4], int method, float sigma, float floor_thresh,
+                                    float *boxes_out, float *scores_out, int64_t *cls_out, int *src_out, int *num_out, void *workspace)
+{
+    UPS_REQUIRE(rois && bbox_delta && cls_prob && im_info && reg_weights && boxes_out && scores_out && cls_out && src_out &&
+                    num_out && workspace, "mask_roi_soft: null pointer");
+    UPS_REQUIRE(num_rois >= 1 && num_classes >= 2, "mask_roi_soft: need at least one roi and two classes");
+    UPS_REQUIRE(num_rois <= 8192, "mask_roi_soft: %d rois exceed the 8192 supported", num_rois);
+    UPS_REQUIRE(method >= 0 && method <= 2, "mask_roi_soft: method must be 0 (hard), 1 (linear) or 2 (gaussian), got %d", method);
+    UPS_REQUIRE(method != 2 || sigma > 0.f, "mask_roi_soft: the gaussian method needs sigma > 0 (got %g)", (double)sigma);   // (NaN fails too)
+    UPS_REQUIRE(nms_thresh == nms_thresh && floor_thresh == floor_thresh, "mask_roi_soft: nms_thresh / floor is NaN");
+    int P, nmax;
+    mroi_dims(num_rois, num_classes, 0, &P, &nmax);
+    const MroiSoftPlan m = mroi_soft_plan(P, nmax);
+    unsigned char *ws = (unsigned char *)workspace;
+    float *cboxes = (float *)(ws + m.boxes), *cscores = (float *)(ws + m.scores);
+    int *csrc = (int *)(ws + m.src), *ccls = (int *)(ws + m.cls);
+    int *keep = (int *)(ws + m.keep), *keepcnt = (int *)(ws + m.keepcnt), *status = (int *)(ws + m.status);
+    hipStream_t st = (hipStream_t)stream;
+    if (ups_zero_async(status, sizeof(int), st)) return 1;
+    // threads and LDS from the most candidates a class can hold: one wavefront up to 1024 rows, four above (T * SNMS_KMAX positions)
+    const int rows = nmax < SNMS_LDS_MAX ? nmax : SNMS_LDS_MAX;
+    const int cap = (rows + 3) & ~3;
+    const size_t smem = snms_lds_bytes(cap);
+#define MROI_SOFT_ARGS rois, bbox_delta, cls_prob, num_rois, num_rois_dev, num_classes, im_info, clip_boxes, score_thresh, reg_weights[0], \
+        reg_weights[1], reg_weights[2], reg_weights[3], nmax, cap, sigma, nms_thresh, floor_thresh, method, cboxes, cscores, csrc, ccls, keep, \
+        keepcnt, status
+    if (rows <= 64 * SNMS_KMAX) {
+        hipLaunchKernelGGL(mroi_soft_kernel<64>, dim3(P), dim3(64), smem, st, MROI_SOFT_ARGS);
+    } else {
+        static std::atomic<unsigned long long> attr_dev{0};
+        UPS_ONCE_PER_DEVICE(attr_dev, UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mroi_soft_kernel<256>),
+                                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                                        (int)snms_lds_bytes(SNMS_LDS_MAX))));
+        hipLaunchKernelGGL(mroi_soft_kernel<256>, dim3(P), dim3(256), smem, st, MROI_SOFT_ARGS);
+    }
+#undef MROI_SOFT_ARGS
+    UPS_CHECK_LAUNCH("mroi_soft_kernel");
+    hipLaunchKernelGGL(mroi_finalize_kernel, dim3(1), dim3(DET_T), (size_t)(P + 1) * sizeof(int), st, P, nmax, max_det, cboxes, cscores, csrc, ccls, keep,
+                       keepcnt, boxes_out, scores_out, cls_out, src_out, num_out, status, (unsigned *)(ws + m.flat));
+    UPS_CHECK_LAUNCH("mroi_finalize_kernel");
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

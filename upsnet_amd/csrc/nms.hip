@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "soft_nms_trips.h"
 #include "sort.h"
 #include "upsnet_hip.h"
 
@@ -528,171 +529,35 @@ extern "C" int upsnet_nms_host(int *keep_out, int *num_out, const float *boxes_h
 
 // ---------------------------------------------------------------------------------------------
 // Soft-NMS (cpu_nms.pyx:91-196), batched: ONE workgroup per problem (RPN level / class), P problems per launch.
-// The outer loop is sequential by definition; a trip is: arg-max over [i, N) (first position of the maximum, :113-118), swap
-// (:120-135), re-score of (i, N) (:147-180) and the reference's "swap with last" compaction (:184-193) restated as: k-th hole
-// (ascending) <- k-th survivor from the end (descending), with N' = N - #removed.
+// The outer loop is sequential by definition; the trips (arg-max, swap, re-score, "swap with last" compaction) and their arithmetic
+// are snms_lds_trips / snms_rescore of soft_nms_trips.h, shared with the soft detection selection (detect.hip).
 //
-// The state of a problem -- x1/y1/x2/y2/score/index as structure-of-arrays -- lives in LDS (29 bytes per box: 1024 boxes =
-// 29 KiB, 4096 = 116 KiB of the CU's 160 KiB); problems up to 1024 boxes run on ONE wavefront (every "barrier" is free, ranks
+// The state of a problem -- x1/y1/x2/y2/score/index as structure-of-arrays -- lives in LDS (28 bytes per box: 1024 boxes =
+// 28 KiB, 4096 = 112 KiB of the CU's 160 KiB); problems up to 1024 boxes run on ONE wavefront (every "barrier" is free, ranks
 // come from ballots), up to 4096 on four. A trip costs a few hundred cycles instead of the ~10 global-memory round trips of the
 // r01 kernel (kept below for n > 4096).
-//
-// Arithmetic: Cython widens the literal in `x2 - x1 + 1` to the C double 1.0, so `area` and `ua` are evaluated in double from
-// fp32 differences and rounded once (see oracle/c/upsnet_oracle.c orc_soft_nms; pinned against the compiled reference).
-#define SNMS_KMAX 16     // chunks of T positions per trip: T * SNMS_KMAX >= nmax
-#define SNMS_LDS_MAX 4096
-
-__device__ static inline bool snms_rescore(const float tx1, const float ty1, const float tx2, const float ty2, const float bx1,
-                                           const float by1, const float bx2, const float by2, const float sigma, const float Nt,
-                                           const int method, float *score)
-{
-    const float area = (float)(((double)(bx2 - bx1) + 1.0) * ((double)(by2 - by1) + 1.0));
-    const float iw = (float)((double)(fminf(tx2, bx2) - fmaxf(tx1, bx1)) + 1.0);
-    if (!(iw > 0)) return false;
-    const float ih = (float)((double)(fminf(ty2, by2) - fmaxf(ty1, by1)) + 1.0);
-    if (!(ih > 0)) return false;
-    const float ua = (float)(((((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0)) + (double)area) - (double)(iw * ih));
-    const float ov = iw * ih / ua;
-    float weight;
-    if (method == 1) weight = ov > Nt ? (float)(1.0 - (double)ov) : 1.0f;
-    else if (method == 2) weight = (float)exp((double)(-(ov * ov) / sigma));
-    else weight = ov > Nt ? 0.0f : 1.0f;
-    *score = weight * *score;
-    return true;
-}
-
 template <int T>
 __global__ void __launch_bounds__(T)
 soft_nms_lds_kernel(float *__restrict__ boxes_g, int64_t *__restrict__ inds_g, const int *__restrict__ counts, const int nmax,
                     const int cap, const float sigma, const float Nt, const float threshold, const int method,
                     int *__restrict__ n_out)
 {
-    constexpr int W = T / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float *x1 = reinterpret_cast<float *>(smem_raw), *y1 = x1 + cap, *x2 = y1 + cap, *y2 = x2 + cap, *sc = y2 + cap;
-    int *ind = reinterpret_cast<int *>(sc + cap);
-    unsigned short *hole = reinterpret_cast<unsigned short *>(ind + cap), *mover = hole + cap;
-    __shared__ int tab[3][SNMS_KMAX][W];
-    __shared__ float s_val[W];
-    __shared__ int s_pos[W];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ SnmsScratch<T> scratch;
+    const SnmsState s = snms_carve(smem_raw, cap);
+    const int p = blockIdx.x, tid = threadIdx.x;
     float *bg = boxes_g + (size_t)p * nmax * 5;
     int64_t *ig = inds_g + (size_t)p * nmax;
     const int n = counts ? min(counts[p], nmax) : nmax;
     for (int q = tid; q < n; q += T) {
-        x1[q] = bg[q * 5 + 0]; y1[q] = bg[q * 5 + 1]; x2[q] = bg[q * 5 + 2]; y2[q] = bg[q * 5 + 3]; sc[q] = bg[q * 5 + 4];
-        ind[q] = q;
+        s.x1[q] = bg[q * 5 + 0]; s.y1[q] = bg[q * 5 + 1]; s.x2[q] = bg[q * 5 + 2]; s.y2[q] = bg[q * 5 + 3]; s.sc[q] = bg[q * 5 + 4];
+        s.ind[q] = q;
     }
     __syncthreads();
-    const u64 lt = (1ULL << lane) - 1ULL;
-    int N = n;
-    for (int i = 0; i < N; ++i) {
-        // ---- arg-max over [i, N): first position holding the maximum score (a thread walks ascending positions, `>` keeps the first)
-        float bv = -INFINITY; int bp = 0x7fffffff;
-        for (int q = i + tid; q < N; q += T) { const float v = sc[q]; if (v > bv) { bv = v; bp = q; } }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            const float ov = __shfl_xor(bv, d, 64); const int op = __shfl_xor(bp, d, 64);
-            if (ov > bv || (ov == bv && op < bp)) { bv = ov; bp = op; }
-        }
-        if (W > 1) {
-            if (lane == 0) { s_val[wave] = bv; s_pos[wave] = bp; }
-            __syncthreads();
-            bv = s_val[0]; bp = s_pos[0];
-#pragma unroll
-            for (int w = 1; w < W; ++w) { const float ov = s_val[w]; const int op = s_pos[w]; if (ov > bv || (ov == bv && op < bp)) { bv = ov; bp = op; } }
-        }
-        if (!(sc[i] < bv)) bp = i;   // the reference starts from maxpos = i and moves only on a strictly larger score
-        __syncthreads();
-        if (tid == 0 && bp != i) {
-            float t;
-            t = x1[i]; x1[i] = x1[bp]; x1[bp] = t;  t = y1[i]; y1[i] = y1[bp]; y1[bp] = t;
-            t = x2[i]; x2[i] = x2[bp]; x2[bp] = t;  t = y2[i]; y2[i] = y2[bp]; y2[bp] = t;
-            t = sc[i]; sc[i] = sc[bp]; sc[bp] = t;
-            const int ti = ind[i]; ind[i] = ind[bp]; ind[bp] = ti;
-        }
-        __syncthreads();
-        const float tx1 = x1[i], ty1 = y1[i], tx2 = x2[i], ty2 = y2[i];
-        // ---- re-score (i, N); chunk k covers positions i+1+k*T .. +T-1, bit k of `rem` = "my position of chunk k falls below threshold"
-        const int len = N - (i + 1);
-        const int K = (len + T - 1) / T;
-        unsigned rem = 0;
-        int my_removed = 0;
-        for (int k = 0; k < K; ++k) {
-            const int q = i + 1 + k * T + tid;
-            bool r = false;
-            if (q < N) {
-                float ns = sc[q];
-                if (snms_rescore(tx1, ty1, tx2, ty2, x1[q], y1[q], x2[q], y2[q], sigma, Nt, method, &ns)) { sc[q] = ns; r = ns < threshold; }
-            }
-            const u64 m = __ballot(r);
-            if (r) rem |= 1u << k;
-            if (W > 1) { if (lane == 0) tab[0][k][wave] = __builtin_popcountll(m); }
-            else my_removed += __builtin_popcountll(m);
-        }
-        int R = my_removed;
-        if (W > 1) {
-            __syncthreads();
-            R = 0;
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int w = 0; w < W; ++w) R += tab[0][k][w];
-        }
-        if (R == 0) { if (W > 1) __syncthreads(); continue; }
-        const int Nn = N - R;
-        // ---- holes (removed, position < Nn) ranked ascending; movers (survivors at positions >= Nn) ranked ascending, used descending
-        int hole_base = 0, mover_base = 0;
-        if (W > 1) {
-            for (int k = 0; k < K; ++k) {
-                const int q = i + 1 + k * T + tid;
-                const bool r = (rem >> k) & 1u;
-                const u64 mh = __ballot(q < Nn && r), mm = __ballot(q >= Nn && q < N && !r);
-                if (lane == 0) { tab[1][k][wave] = __builtin_popcountll(mh); tab[2][k][wave] = __builtin_popcountll(mm); }
-            }
-            __syncthreads();
-        }
-        int n_holes = 0, n_movers = 0;
-        if (W > 1) {
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int w = 0; w < W; ++w) { n_holes += tab[1][k][w]; n_movers += tab[2][k][w]; }
-        } else {
-            for (int k = 0; k < K; ++k) {
-                const int q = i + 1 + k * T + tid;
-                const bool r = (rem >> k) & 1u;
-                n_holes += __builtin_popcountll(__ballot(q < Nn && r));
-                n_movers += __builtin_popcountll(__ballot(q >= Nn && q < N && !r));
-            }
-        }
-        for (int k = 0; k < K; ++k) {
-            const int q = i + 1 + k * T + tid;
-            const bool r = (rem >> k) & 1u;
-            const bool ish = q < Nn && r, ism = q >= Nn && q < N && !r;
-            const u64 mh = __ballot(ish), mm = __ballot(ism);
-            int hb = hole_base, mb = mover_base;
-            if (W > 1) {
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    if (w < wave) { hb += tab[1][k][w]; mb += tab[2][k][w]; }
-                    hole_base += tab[1][k][w]; mover_base += tab[2][k][w];
-                }
-            } else {
-                hole_base += __builtin_popcountll(mh); mover_base += __builtin_popcountll(mm);
-            }
-            if (ish) hole[hb + __builtin_popcountll(mh & lt)] = (unsigned short)q;
-            if (ism) mover[n_movers - 1 - (mb + __builtin_popcountll(mm & lt))] = (unsigned short)q;
-        }
-        __syncthreads();
-        for (int j = tid; j < n_holes; j += T) {   // n_holes == n_movers
-            const int dst = hole[j], src = mover[j];
-            x1[dst] = x1[src]; y1[dst] = y1[src]; x2[dst] = x2[src]; y2[dst] = y2[src]; sc[dst] = sc[src]; ind[dst] = ind[src];
-        }
-        __syncthreads();
-        N = Nn;
-    }
+    const int N = snms_lds_trips<T>(s, scratch, n, sigma, Nt, threshold, method);
     for (int q = tid; q < n; q += T) {
-        bg[q * 5 + 0] = x1[q]; bg[q * 5 + 1] = y1[q]; bg[q * 5 + 2] = x2[q]; bg[q * 5 + 3] = y2[q]; bg[q * 5 + 4] = sc[q];
-        ig[q] = ind[q];
+        bg[q * 5 + 0] = s.x1[q]; bg[q * 5 + 1] = s.y1[q]; bg[q * 5 + 2] = s.x2[q]; bg[q * 5 + 3] = s.y2[q]; bg[q * 5 + 4] = s.sc[q];
+        ig[q] = s.ind[q];
     }
     if (tid == 0) n_out[p] = N;
 }
@@ -840,7 +705,7 @@ extern "C" int upsnet_soft_nms_batched(void *stream, float *boxes, int64_t *inds
     if (nmax <= SNMS_LDS_MAX) {
         const int T = nmax <= 64 * SNMS_KMAX ? 64 : 256;
         const int cap = (nmax + 3) & ~3;
-        const size_t smem = (size_t)cap * (5 * sizeof(float) + sizeof(int) + 2 * sizeof(unsigned short));
+        const size_t smem = snms_lds_bytes(cap);
         if (T == 64) {
             hipLaunchKernelGGL(soft_nms_lds_kernel<64>, dim3(P), dim3(64), smem, st, boxes, inds, counts, nmax, cap, sigma, Nt,
                                threshold, method, n_out);

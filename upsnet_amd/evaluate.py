@@ -7,7 +7,7 @@
                                   [--vis_panoptic {flat,overlay,both} [--vis_panoptic_min_area N]]
                                   [--write_instances [--instances_1bit]] [--eval_boundary [--boundary_dilation_ratio R]]
                                   [--eval_boundary_pq [--boundary_pq_dilation_ratio R]] [--aug_scales S [S ...]] [--aug_flip]
-                                  [--bbox_vote [--bbox_vote_thresh T]]
+                                  [--bbox_vote [--bbox_vote_thresh T]] [--soft_nms [--soft_nms_method M] [--soft_nms_sigma S]]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>] [--eval_boundary_pq ...]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
     python -m upsnet_amd.evaluate --cfg <yaml> --score_instances <folder>
@@ -57,6 +57,12 @@ DESIGN 4.21): every kept detection box, class-wise and panoptic, becomes the sco
 `test.score_thresh` whose IoU with it is >= T (default 0.8); scores, classes and order stay. Voting lives on the eager path of the
 augmentation: on its own it runs that path with the base augmentation alone; the results pickle also carries 'bbox_vote',
 [score_thresh, T]; `--eval_proposals` is refused with it as well.
+`--soft_nms [--soft_nms_method linear|gaussian] [--soft_nms_sigma S]` (or `test.soft_nms` / `test.soft_nms_method` / `test.soft_nms_sigma` /
+`test.soft_nms_score_thresh` in the yaml) turns on soft-NMS in the class-wise detection selection (csrc/detect.hip): a
+candidate that overlaps a kept one stays with a decayed score and is dropped only below `test.soft_nms_score_thresh` (0.0001); the
+detection scores written are the decayed ones; the panoptic selection stays hard NMS. It lives on the same eager path (on its own: the
+base augmentation alone), comes before the voting, and the results pickle also carries 'soft_nms', [method, sigma, floor];
+`--eval_proposals` is refused with it too.
 One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
@@ -142,11 +148,12 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
     all_ssegs = [] if net.has_fcn_head else None
     all_panos, all_pano_cls_inds = ([], []) if net.has_panoptic_head else (None, None)
     all_proposals = [] if keep_proposals else None
-    from .tta import augmentation_list, bbox_vote_params, eager_path_enabled
-    test_aug = augmentation_list() if eager_path_enabled() else None     # (box voting alone: the base augmentation, eagerly)
+    from .tta import augmentation_list, bbox_vote_params, eager_path_enabled, soft_nms_params
+    test_aug = augmentation_list() if eager_path_enabled() else None     # (box voting / soft-NMS alone: the base augmentation, eagerly)
     bbox_vote = bbox_vote_params()
+    soft_nms = soft_nms_params()
     if test_aug is not None and keep_proposals:
-        raise ValueError('keep_proposals with test-time augmentation or box voting: there is no single proposal list to keep')
+        raise ValueError('keep_proposals with test-time augmentation, box voting or soft-NMS: there is no single proposal list to keep')
     if keep_proposals:
         model.keep_proposals = True
     depth = max(1, min(int(in_flight), getattr(model, 'graph_slots', 1))) if hasattr(model, 'forward_async') else 1
@@ -205,6 +212,8 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
         results['test_aug'] = [list(a) for a in test_aug]
     if bbox_vote is not None:
         results['bbox_vote'] = list(bbox_vote)
+    if soft_nms is not None:
+        results['soft_nms'] = list(soft_nms)
     return results, times
 
 
@@ -388,11 +397,14 @@ def main(argv=None):
     if args.score_instances and config.dataset.dataset != 'Cityscapes':     # (no model is built: the heads do not matter)
         raise SystemExit('--score_instances scores instance prediction files against the Cityscapes gtFine instanceIds maps: it needs '
                          'dataset.dataset = Cityscapes (dataset=%s)' % config.dataset.dataset)
-    from .tta import augmentation_enabled, augmentation_list, bbox_vote_params, eager_path_enabled
+    from .tta import augmentation_enabled, augmentation_list, bbox_vote_params, eager_path_enabled, soft_nms_params
     if eager_path_enabled() and not (args.eval_only or args.score_panoptic or args.score_ssegs or args.score_instances):
         if args.eval_proposals and augmentation_enabled():
             raise SystemExit('--eval_proposals with test-time augmentation (--aug_scales / --aug_flip) is refused: the detections come from '
                              'the union of every augmentation\'s proposals, so there is no single proposal list to score')
+        if args.eval_proposals and config.test.get('soft_nms', False):
+            raise SystemExit('--eval_proposals with soft-NMS (--soft_nms) is refused: the soft selection runs on the eager path of the '
+                             'test-time augmentation, which keeps no single proposal list to score')
         if args.eval_proposals:
             raise SystemExit('--eval_proposals with box voting (--bbox_vote) is refused: voting runs on the eager path of the test-time '
                              'augmentation, which keeps no single proposal list to score')
@@ -404,6 +416,10 @@ def main(argv=None):
             bbox_vote_params()
         except ValueError as e:
             raise SystemExit('--bbox_vote_thresh: %s' % e)
+        try:
+            soft_nms_params()
+        except ValueError as e:
+            raise SystemExit('--soft_nms: %s' % e)
     vis_mask = bool(config.test.get('vis_mask', False))
     if vis_mask and not (net.has_rcnn and net.has_mask_head):
         raise SystemExit('--vis_mask (config.test.vis_mask) draws the detections and their instance masks: it needs network.has_rcnn and '

@@ -1918,3 +1918,12 @@ def box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_th
     from . import tta as impl
     return impl.box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_thresh, vote_iou_thresh, reg_weights,
                          num_rois_dev, clip_boxes)
+
+
+def mask_roi_soft(rois, bbox_delta, cls_prob, im_info, score_thresh, nms_thresh, max_det, reg_weights, method, sigma, floor,
+                  num_rois_dev=None, clip_boxes=True):
+    """tta.py: the class-wise detection selection with soft-NMS, (boxes [cap,5], scores [cap] decayed, cls [cap] int64, src [cap] int32,
+    num device int32) like mask_roi (csrc/detect.hip mroi_soft_kernel)."""
+    from . import tta as impl
+    return impl.mask_roi_soft(rois, bbox_delta, cls_prob, im_info, score_thresh, nms_thresh, max_det, reg_weights, method, sigma, floor,
+                              num_rois_dev, clip_boxes)

@@ -13,6 +13,10 @@ tensors. The three merges are the kernels of csrc/tta.hip (ops.tta_*); everythin
                                           score-weighted mean of the candidates of its class above test.score_thresh whose IoU with
                                           it is >= test.bbox_vote_thresh; on its own it runs this path with the base augmentation alone
 
+    config.test.soft_nms = True           soft-NMS in the class-wise selection (csrc/detect.hip): overlapping candidates
+                                          stay with a decayed score (test.soft_nms_method / _sigma / _score_thresh); on its own it
+                                          runs this path with the base augmentation alone
+
 The run is eager: no HIP graph, one image in flight. All outputs are in the base frame (the first augmentation, the plain forward's
 input), so evaluate.post_image takes them with the base im_info. Whether the augmentations raise PQ has not been measured: no trained
 checkpoint exists here."""
@@ -23,7 +27,7 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import check, f32c, float_array, int_array, lib, nhwc, ptr, ptr_array, require_cuda, stream
 from .config.config import config
-from .operators.modules.mask_roi import check_count
+from .operators.modules.mask_roi import check_count, check_count_soft
 
 MAX_AUG = ops.TTA_MAX_AUG
 MAX_UNION_ROWS = 8192     # candidate rows the device detection selection takes (csrc/detect.hip)
@@ -143,6 +147,40 @@ def box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_th
     return voted
 
 
+SOFT_NMS_METHODS = {'linear': 1, 'gaussian': 2}      # cpu_soft_nms's numbering (0 is the hard rule)
+
+
+def mask_roi_soft(rois, bbox_delta, cls_prob, im_info, score_thresh, nms_thresh, max_det, reg_weights, method, sigma, floor,
+                  num_rois_dev=None, clip_boxes=True):
+    """The class-wise detection selection with soft-NMS (csrc/detect.hip mroi_soft_kernel): per class cpu_soft_nms(sigma,
+    Nt = nms_thresh, threshold = floor, method 0 hard / 1 linear / 2 gaussian) on the candidates above score_thresh, then the
+    top-max_det rule on the decayed scores. Returns fixed-capacity (boxes [cap,5], scores [cap], cls [cap] int64, src [cap] int32, num
+    device int32) as ops.mask_roi; a negative num reports a class of more than 4096 candidates. Two launches, no host read."""
+    require_cuda(rois, bbox_delta, cls_prob, im_info)
+    rois, bbox_delta, cls_prob = f32c(rois), f32c(bbox_delta), f32c(cls_prob)
+    if cls_prob.dim() != 2:
+        raise ValueError("mask_roi_soft: cls_prob must be [N,C], got %s" % (tuple(cls_prob.shape),))
+    N, C = cls_prob.shape
+    if tuple(rois.shape) != (N, 5) or tuple(bbox_delta.shape) != (N, 4 * C):
+        raise ValueError("mask_roi_soft: rois %s / bbox_delta %s do not go with cls_prob %s (class-wise deltas: [N,5], [N,4C], [N,C])"
+                         % (tuple(rois.shape), tuple(bbox_delta.shape), (N, C)))
+    if num_rois_dev is not None and (num_rois_dev.dtype != torch.int32 or num_rois_dev.numel() != 1):
+        raise ValueError("mask_roi_soft: the row count must be one int32")
+    dev = rois.device
+    cap = lib().upsnet_mask_roi_capacity(max(N, 1), max(C, 2), 0)
+    boxes = torch.empty((cap, 5), dtype=torch.float32, device=dev)
+    scores = torch.empty((cap,), dtype=torch.float32, device=dev)
+    cls = torch.empty((cap,), dtype=torch.int64, device=dev)
+    src = torch.empty((cap,), dtype=torch.int32, device=dev)
+    num = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws = torch.empty((int(lib().upsnet_mask_roi_soft_workspace_bytes(N, C)),), dtype=torch.uint8, device=dev)
+    check(lib().upsnet_mask_roi_soft(stream(), ptr(rois), ptr(bbox_delta), ptr(cls_prob), N, ptr(num_rois_dev), C,
+                                     ptr(f32c(im_info.reshape(-1))), int(bool(clip_boxes)), float(score_thresh), float(nms_thresh),
+                                     int(max_det), float_array(reg_weights), int(method), float(sigma), float(floor), ptr(boxes),
+                                     ptr(scores), ptr(cls), ptr(src), ptr(num), ptr(ws)), "mask_roi_soft")
+    return boxes, scores, cls, src, num
+
+
 # ------------------------------------------------------------------------------------------------ the augmented forward
 def augmentation_enabled(cfg=None):
     t = (config if cfg is None else cfg).test
@@ -161,10 +199,28 @@ def bbox_vote_params(cfg=None):
     return float(t.score_thresh), iou
 
 
+def soft_nms_params(cfg=None):
+    """(method, sigma, floor) when config.test.soft_nms is on, else None: method in cpu_soft_nms's numbering (1 linear,
+    2 gaussian), floor = test.soft_nms_score_thresh, the score below which a decayed candidate is dropped."""
+    t = (config if cfg is None else cfg).test
+    if not t.get('soft_nms', False):
+        return None
+    name = t.get('soft_nms_method', 'linear')
+    if name not in SOFT_NMS_METHODS:
+        raise ValueError("test.soft_nms_method must be one of %s (got %r)" % (sorted(SOFT_NMS_METHODS), name))
+    sigma, floor = float(t.get('soft_nms_sigma', 0.5)), float(t.get('soft_nms_score_thresh', 0.0001))
+    if not sigma > 0.0:
+        raise ValueError("test.soft_nms_sigma must be positive (got %r)" % (t.get('soft_nms_sigma'),))
+    if not floor >= 0.0:
+        raise ValueError("test.soft_nms_score_thresh must not be negative (got %r)" % (t.get('soft_nms_score_thresh'),))
+    return SOFT_NMS_METHODS[name], sigma, floor
+
+
 def eager_path_enabled(cfg=None):
-    """Whether the evaluation run goes through forward_tta: test-time augmentation, or box voting (which lives on that path only; on
-    its own it runs the base augmentation alone)."""
-    return augmentation_enabled(cfg) or bool((config if cfg is None else cfg).test.get('bbox_vote', False))
+    """Whether the evaluation run goes through forward_tta: test-time augmentation, or box voting or soft-NMS (which live on that path
+    only; on their own they run the base augmentation alone)."""
+    t = (config if cfg is None else cfg).test
+    return augmentation_enabled(cfg) or bool(t.get('bbox_vote', False)) or bool(t.get('soft_nms', False))
 
 
 def augmentation_list(cfg=None):
@@ -209,6 +265,7 @@ def forward_tta(model, image_u8_bgr, device=None, return_parts=False):
     from .dataset.blob import get_image_blob
     augs = augmentation_list()
     vote = bbox_vote_params()
+    soft = soft_nms_params()
     if getattr(model, 'keep_proposals', False):
         raise ValueError("keep_proposals (--eval_proposals) with test-time augmentation: there is no single proposal list to keep")
     if isinstance(image_u8_bgr, np.ndarray):
@@ -236,7 +293,9 @@ def forward_tta(model, image_u8_bgr, device=None, return_parts=False):
         score = ops.tta_seg_merge([s[1] for s in stages], q, wr, flips, cell)
         rois, delta, prob, n_rois = ops.tta_roi_union([s[2] for s in stages], [s[4] for s in stages], [s[5] for s in stages],
                                                       [s[3] for s in stages], r, wr, flips)
-        det_boxes, det_scores, det_cls, det_src, det_num = model.mask_roi.forward_padded(rois, delta, prob, im_info0, n_rois)
+        # with soft-NMS the class-wise selection keeps the union's overlapping candidates with decayed scores; the
+        # panoptic selection stays hard (the panoptic head wants a non-overlapping instance set)
+        det_boxes, det_scores, det_cls, det_src, det_num = model.mask_roi.forward_padded(rois, delta, prob, im_info0, n_rois, soft_nms=soft)
         pan_boxes, pan_scores, pan_cls, pan_src, pan_num = model.mask_roi_panoptic.forward_padded(rois, delta, prob, im_info0, n_rois)
         det_boxes_prevote, pan_boxes_prevote = det_boxes, pan_boxes
         if vote is not None:
@@ -250,7 +309,7 @@ def forward_tta(model, image_u8_bgr, device=None, return_parts=False):
                                      clip_boxes=bool(model.mask_roi_panoptic.clip_boxes))
         pan_row, extra_boxes, extra_num = ops.mask_roi_dedup(det_src, det_cls, det_num, pan_src, pan_cls, pan_boxes, pan_num)
         n_det, n_pan, n_extra = torch.cat([det_num, pan_num, extra_num]).tolist()
-        check_count(n_det), check_count(n_pan)
+        (check_count if soft is None else check_count_soft)(n_det), check_count(n_pan)
         det_boxes, det_scores, det_cls = det_boxes[:n_det], det_scores[:n_det], det_cls[:n_det]
         pan_boxes, pan_scores, pan_cls = pan_boxes[:n_pan], pan_scores[:n_pan], pan_cls[:n_pan]
         det_boxes_prevote, pan_boxes_prevote = det_boxes_prevote[:n_det], pan_boxes_prevote[:n_pan]
@@ -275,7 +334,7 @@ def forward_tta(model, image_u8_bgr, device=None, return_parts=False):
                  merged_mask_logits=mask_score, boxes=boxes, n_det=n_det, n_pan=n_pan, n_extra=n_extra,
                  det_boxes=det_boxes, det_scores=det_scores, det_cls=det_cls, pan_boxes=pan_boxes, pan_scores=pan_scores,
                  pan_cls=pan_cls, pan_row=pan_row, extra_boxes=extra_boxes, det_boxes_prevote=det_boxes_prevote,
-                 pan_boxes_prevote=pan_boxes_prevote, bbox_vote=vote)
+                 pan_boxes_prevote=pan_boxes_prevote, bbox_vote=vote, soft_nms=soft)
     return out, parts
 
 
