@@ -1150,6 +1150,42 @@ int upsnet_mask_roi_soft(void *stream, const float *rois, const float *bbox_delt
                          float nms_thresh, int max_det, const float reg_weights_host[4], int method, float sigma, float floor_thresh,
                          float *boxes_out, float *scores_out, int64_t *cls_out, int *src_out, int *num_out, void *workspace);
 
+/* ============================== Panoptic tracking across frames ============================== */
+
+/* One step of the tracker: associates the thing segments of frame `frame` (pan_2ch uint8 [H,W,3], channel 0 category with 255 =
+ * VOID, channel 1 instance; a thing segment is (c, i) with c != 255, i >= 1) with the tracks the per-pixel memory remembers. The
+ * reference has no tracking; the rule is this project's own (csrc/pan_track.hip, restated in tests/pan_track_ref.py):
+ *   counts A_cur[c,i], A_mem[c,j], I[c,i,j] (same category only); candidates I > 0 and (double)I >= iou_thresh * (double)(A_cur +
+ *   A_mem - I); per category greedy by IoU descending (I1 U2 against I2 U1 in int64, ties by ascending (i, j)); unmatched segments in
+ *   ascending (c, i) take the first id of n_c mod 255 + 1, ... that is not live (in memory at the start of the step or assigned
+ *   earlier in it) and leave n_c just past it, or -- all 255 live -- take over the unassigned memory track with the oldest frame index
+ *   (smallest id on ties; n_c stays); out_2ch: thing pixels (c, id, 0), all others copied; memory: a pixel under a thing takes
+ *   (track, frame); any other entry is cleared when its track was assigned in this step or frame - s > max_age.
+ * memory: uint16 [H*W], c << 8 | j, 0 = none; zeroed by the caller before the first step. workspace:
+ * upsnet_pan_track_workspace_bytes(H, W) bytes, ZEROED ONCE; every step leaves its count cells zero. The ints from
+ * upsnet_pan_track_stamp_offset() bytes on are the tracker's state (stamp[65536]: frame index + 1 of a track's last assignment --
+ * all memory pixels of a track share it --, cursor[256], scratch): zeroing them and `memory` resets the tracker.
+ * The step's table has upsnet_pan_track_table_ints(H, W) ints: [0] = number of rows, [1] = frame, rows of 8 ints from [8] on, one per
+ * current thing segment in ascending (c, i): c, i, id, matched, I, U, area, taken over (unmatched: I = 0, U = area). Frame t fills
+ * the table at byte upsnet_pan_track_table_offset() + (t & 1) * 4 * table_ints of the workspace, so it outlives the next step.
+ * host_table (may be NULL): pinned host memory; the head and the first min(host_rows, rows) rows are copied into it asynchronously
+ * on `stream`. Three launches and the copy; nothing is synchronised or allocated.
+ * Refused before any launch: a null pointer, H * W outside 1..2^24, iou_thresh outside [1/16, 1] (memory tracks are disjoint, so a
+ * segment has at most 1 / iou_thresh <= 16 candidates, which bounds the LDS candidate list at 4080 per category), max_age < 0. */
+size_t upsnet_pan_track_workspace_bytes(int height, int width);
+size_t upsnet_pan_track_stamp_offset(void);
+size_t upsnet_pan_track_table_ints(int height, int width);
+size_t upsnet_pan_track_table_offset(void);
+int upsnet_pan_track_step(void *stream, const unsigned char *pan_2ch, int height, int width, double iou_thresh, int max_age, int frame,
+                          void *workspace, unsigned short *memory, unsigned char *out_2ch, int *host_table, int host_rows);
+
+/* Frame-stable colours of a 2-channel map, a pure function of (category, instance). mode 0: (R, G, B) = (category, instance, 1), VOID
+ * (0,0,0). mode 1: stuff takes its category colour, a thing the offset rule of upsnet_pan_format with ordinal := instance and the
+ * first attempt whose colour is not (0,0,0), no taken set. cat_table as in upsnet_pan_format (may be NULL in mode 0); an unknown
+ * category is painted (0,0,0) in mode 1. One launch. */
+int upsnet_pan_stable_colors(void *stream, const unsigned char *pred_2ch, int height, int width, const int *cat_table, int mode,
+                             unsigned char *rgb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,12 @@ _SIGNATURES = {
     "upsnet_box_vote": (c_int, [P, P, P, P, c_int, P, c_int, P, c_int, P, c_float, c_float, P, P, P, c_int, P]),
     "upsnet_mask_roi_soft_workspace_bytes": (c_size_t, [c_int, c_int]),
     "upsnet_mask_roi_soft": (c_int, [P, P, P, P, c_int, P, c_int, P, c_int, c_float, c_float, c_int, P, c_int, c_float, c_float, P, P, P, P, P, P]),
+    "upsnet_pan_track_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "upsnet_pan_track_stamp_offset": (c_size_t, []),
+    "upsnet_pan_track_table_ints": (c_size_t, [c_int, c_int]),
+    "upsnet_pan_track_table_offset": (c_size_t, []),
+    "upsnet_pan_track_step": (c_int, [P, P, c_int, c_int, c_double, c_int, c_int, P, P, P, P, c_int]),
+    "upsnet_pan_stable_colors": (c_int, [P, P, c_int, c_int, P, c_int, P]),
 }
 
 _lib = None

@@ -18,6 +18,13 @@ instance); `ordinal` counts the segments of one category from 0; the taken set s
     and distinct per id (67 is odd).
 ColorGenerator is the host statement of the rule; the device (pan_color_kernel) is held to it by tests/test_pan_format_gpu.py.
 
+Frame-stable mode (`stable_ids=True`, opt-in; for maps whose instance numbers are track ids, dataset/pan_track.py): colours and ids are
+pure functions of (category, instance), so a track looks the same in every frame of a sequence. The PNG colour is (R, G, B) =
+(category, instance, 1), VOID (0,0,0): unique within an image and decodable without the JSON, and segments_info[].id = R + 256 G +
+65536 B follows from it. The picture colour (stable_color; what pan_vis blends in) is the category colour for stuff and, for a thing,
+the offset rule above with ordinal := instance and the first attempt whose colour is not (0,0,0); there is no taken set, so two
+segments of an image may share a picture colour. The default mode is unchanged by this.
+
 Deviations from the reference: `bbox` is the reference's [x_min, y_min, x_max - x_min, y_max - y_min] (one less than COCO's width and
 height; PQ does not read it); one colour generator per image (ids only have to be unique within an image); every annotation of
 pred.json also carries `image_id` and `file_name`; invalid input raises ValueError before any launch, a segment whose category is not
@@ -95,6 +102,23 @@ def color_attempt(base, cat_id, ordinal, attempt):
     return tuple(min(255, max(0, b + d)) for b, d in zip(base, offset))
 
 
+def stable_color(cat_id, instance, entry):
+    """The frame-stable picture colour of (category, instance): the host statement of pan_stable_kernel's mode 1."""
+    base = tuple(category_color(cat_id, entry))
+    if entry['isthing'] == 0:
+        return list(base)
+    for attempt in range(CUBE):
+        color = color_attempt(base, cat_id, instance, attempt)
+        if color != (0, 0, 0):
+            return list(color)
+    raise RuntimeError("unreachable: the +-30 cube holds a non-zero offset")
+
+
+def stable_id_color(cat_id, instance):
+    """The frame-stable PNG colour of (category, instance): (category, instance, 1); VOID (category 255) is (0,0,0)."""
+    return [0, 0, 0] if int(cat_id) == 255 else [int(cat_id), int(instance), 1]
+
+
 class ColorGenerator(object):
     """The colour rule on the host, one object per image; get_color(category id) in ascending key order. KeyError for a category
     that is not in the table."""
@@ -136,11 +160,12 @@ class PanopticFormatter(object):
     stream and starts its one device-to-host copy (RGB map, table header and the first FAST_ROWS rows) into pinned memory without
     synchronising; finish() waits for that copy alone. An image of more than FAST_ROWS segments costs a second copy."""
 
-    def __init__(self, categories, device=None):
+    def __init__(self, categories, device=None, stable_ids=False):
         self.cat_table_host = category_table(categories)
         self.device = torch.device(device) if device is not None else None
         self.num_images = 0
         self._state = None
+        self.stable_ids = bool(stable_ids)     # frame-stable ids and colours (the module's docstring); the default path is untouched
 
     def _dev_state(self):
         if self._state is None:
@@ -171,6 +196,9 @@ class PanopticFormatter(object):
         table = p.buf[p.offset:].view(torch.int32)
         check(lib().upsnet_pan_format(stream(), ptr(pred_2ch), H, W, ptr(st['cat_table']), ptr(st['ws']), ptr(p.buf), ptr(table)),
               "pan_format")
+        if self.stable_ids:     # the table (areas, boxes) stays; the id map is repainted as (category, instance, 1)
+            from .. import ops
+            ops.pan_stable_colors(pred_2ch, None, 0, p.buf[:H * W * 3])
         self.num_images += 1
         nfast = p.offset + 4 * (HEAD + ROW * FAST_ROWS)
         p.host = torch.empty((nfast,), dtype=torch.uint8, pin_memory=True)
@@ -202,6 +230,9 @@ class PanopticFormatter(object):
         else:   # (beyond the rows that travelled with the map: a second copy, noise-like maps only)
             rows = p.buf[first:first + 4 * ROW * n].cpu().numpy()
         rows = rows.view(np.int32).reshape(n, ROW).tolist()
+        if self.stable_ids:
+            for r in rows:
+                r[6] = (r[0] >> 8) + 256 * (r[0] & 255) + 65536
         segments_info = [{'id': r[6], 'category_id': r[0] >> 8, 'iscrowd': 0, 'bbox': [r[2], r[3], r[4] - r[2], r[5] - r[3]], 'area': r[1]}
                          for r in rows]
         rgb = p.buf[:H * W * 3].view(H, W, 3)
@@ -222,11 +253,12 @@ def _save_png(array, path):
     Image.fromarray(array).save(path)
 
 
-def write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=None):
+def write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=None, stable_ids=False):
     """Write output_dir/pan_2ch/<name>.png (the 2-channel maps), output_dir/pan/<name>.png (the panoptic PNGs) and
     output_dir/pred.json ({'annotations': [{'image_id', 'file_name', 'segments_info'}]}); name = png_name(images[i]['file_name']),
     image_id = image_ids[i] if given, else images[i]['id']. Returns the annotations. ValueError before any launch: counts that do
-    not match, an image without file_name (or id), two images of one output name, a map that is not uint8 [H,W,3]."""
+    not match, an image without file_name (or id), two images of one output name, a map that is not uint8 [H,W,3]. stable_ids: the
+    frame-stable ids and colours of the module's docstring (for tracked maps)."""
     preds, images = list(pred_pans_2ch), list(images)
     if len(preds) != len(images):
         raise ValueError("%d predictions for %d images" % (len(preds), len(images)))
@@ -242,7 +274,7 @@ def write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=None
     ids = list(image_ids) if image_ids is not None else [im['id'] for im in images]
     for pred in preds:
         _check_image('pred_2ch', pred)
-    fmt = PanopticFormatter(categories)
+    fmt = PanopticFormatter(categories, stable_ids=stable_ids)
     for sub in ('pan_2ch', 'pan'):
         for name in names:
             os.makedirs(os.path.dirname(os.path.join(output_dir, sub, name)), exist_ok=True)

@@ -66,9 +66,10 @@ class PanopticRenderer(object):
     returns (picture uint8 [H,W,3] device tensor, info int32 [2] device tensor: segments that qualified for a label, labels drawn,
     the formatter's handle); the handle's finish() raises the KeyError of an unknown category."""
 
-    def __init__(self, categories, device=None):
+    def __init__(self, categories, device=None, stable_ids=False):
         self.names_host, self.lens_host = name_table(categories)
-        self.formatter = PanopticFormatter(categories, device)
+        self.formatter = PanopticFormatter(categories, device, stable_ids=stable_ids)
+        self.stable_ids = bool(stable_ids)     # overlay: segments blended in pan_format.stable_color, the same in every frame
         self._state = None
 
     def _dev_state(self):
@@ -119,7 +120,12 @@ class PanopticRenderer(object):
                 raise ValueError("out must be a contiguous uint8 device tensor of shape %s" % ((H, W, 3),))
             info = torch.empty((2,), dtype=torch.int32, device=dev)
             overlay = mode == 'overlay'
-            check(lib().upsnet_pan_vis(stream(), MODES[mode], ptr(pred_2ch), ptr(handle.buf) if overlay else None,
+            colours = handle.buf
+            if overlay and self.stable_ids:
+                from .. import ops
+                colours = ops.pan_stable_colors(pred_2ch, self.formatter._state['cat_table'], 1,
+                                                torch.empty((H, W, 3), dtype=torch.uint8, device=dev))
+            check(lib().upsnet_pan_vis(stream(), MODES[mode], ptr(pred_2ch), ptr(colours) if overlay else None,
                                        ptr(table) if overlay else None, ptr(image) if overlay else None, H, W,
                                        ptr(self.formatter._state['cat_table']), ptr(st['names']), ptr(st['lens']), label_min_area,
                                        ptr(st['ws']), ptr(out), ptr(info)), "pan_vis")
@@ -138,12 +144,13 @@ def render_panoptic(pred_2ch, categories, image=None, mode='overlay', label_min_
     return out
 
 
-def vis_panoptic(pred_pans_2ch, images, categories, output_dir, mode, image_paths=None, label_min_area=1024):
+def vis_panoptic(pred_pans_2ch, images, categories, output_dir, mode, image_paths=None, label_min_area=1024, stable_ids=False):
     """Write one picture per prediction: mode 'overlay' to output_dir/vis/<name>, 'flat' to output_dir/vis_flat/<name>, name =
     png_name(images[i]['file_name']) as write_panoptic names its files. image_paths[i] is the photograph of prediction i (overlay
     only). Image i + k is decoded ahead on a bounded thread pool, picture i is copied back through pinned memory while picture i + 1
     is drawn, and its PNG is written by a bounded pool. Returns the written paths. ValueError before any launch: counts that do not
-    match, an image without file_name, two images of one output name, overlay without image_paths."""
+    match, an image without file_name, two images of one output name, overlay without image_paths. stable_ids: segments in their
+    frame-stable colours (pan_format's docstring; for tracked maps)."""
     _check_mode(mode)
     preds, images = list(pred_pans_2ch), list(images)
     if len(preds) != len(images):
@@ -159,7 +166,7 @@ def vis_panoptic(pred_pans_2ch, images, categories, output_dir, mode, image_path
         raise ValueError("two images share one output name: %s" % sorted(n for n in set(names) if names.count(n) > 1)[:5])
     for pred in preds:
         _check_image('pred_2ch', pred)
-    renderer = PanopticRenderer(categories)
+    renderer = PanopticRenderer(categories, stable_ids=stable_ids)
     paths = [os.path.join(output_dir, FOLDERS[mode], name) for name in names]
     for path in paths:
         os.makedirs(os.path.dirname(path), exist_ok=True)

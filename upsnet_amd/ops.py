@@ -1927,3 +1927,45 @@ def mask_roi_soft(rois, bbox_delta, cls_prob, im_info, score_thresh, nms_thresh,
     from . import tta as impl
     return impl.mask_roi_soft(rois, bbox_delta, cls_prob, im_info, score_thresh, nms_thresh, max_det, reg_weights, method, sigma, floor,
                               num_rois_dev, clip_boxes)
+
+
+def pan_track_step(pan_2ch, iou_thresh, max_age, frame, workspace, memory, out, host_table=None):
+    """One tracker step on the device (include/upsnet_hip.h, csrc/pan_track.hip): pan_2ch uint8 [H,W,3]; memory int16 [H,W] holding
+    the uint16 track keys (c << 8 | j, 0 = none), updated in place; workspace: upsnet_pan_track_workspace_bytes(H, W) bytes, zeroed
+    once; out: uint8 [H,W,3], the tracked map; host_table: pinned int32 host memory that takes the table's head (8 ints) and its first
+    rows (8 ints each), as many as fit, by an asynchronous copy (None: no copy). Three launches, no host synchronisation, no allocation
+    (dataset/pan_track.PanopticTracker owns the buffers)."""
+    require_cuda(pan_2ch, workspace, memory, out)
+    if pan_2ch.dtype != torch.uint8 or pan_2ch.dim() != 3 or pan_2ch.shape[2] != 3 or not pan_2ch.is_contiguous():
+        raise ValueError("pan_track_step: pan_2ch must be contiguous uint8 [H,W,3], got %s %s" % (tuple(pan_2ch.shape), pan_2ch.dtype))
+    H, W = int(pan_2ch.shape[0]), int(pan_2ch.shape[1])
+    if out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous():
+        raise ValueError("pan_track_step: out must be contiguous uint8 [%d,%d,3], got %s %s" % (H, W, tuple(out.shape), out.dtype))
+    if memory.dtype != torch.int16 or tuple(memory.shape) != (H, W) or not memory.is_contiguous():
+        raise ValueError("pan_track_step: memory must be a contiguous int16 [%d,%d] tensor, got %s %s" % (H, W, tuple(memory.shape), memory.dtype))
+    need = int(lib().upsnet_pan_track_workspace_bytes(H, W))
+    if need == 0 or workspace.numel() * workspace.element_size() < need:
+        raise ValueError("pan_track_step: workspace too small for (or no workspace exists for) a frame of %d x %d" % (H, W))
+    host_rows = 0
+    if host_table is not None:
+        if host_table.is_cuda or not host_table.is_pinned() or host_table.dtype != torch.int32 or host_table.numel() < 8 \
+                or not host_table.is_contiguous():
+            raise ValueError("pan_track_step: host_table must be contiguous pinned int32 host memory of at least 8 ints")
+        host_rows = (host_table.numel() - 8) // 8
+    check(lib().upsnet_pan_track_step(stream(), ptr(pan_2ch), H, W, float(iou_thresh), int(max_age), int(frame), ptr(workspace),
+                                      ptr(memory), ptr(out), ptr(host_table), host_rows), "pan_track_step")
+    return out
+
+
+def pan_stable_colors(pred_2ch, cat_table, mode, out):
+    """Frame-stable colours of a 2-channel map (csrc/pan_track.hip): mode 0 the PNG colour (category, instance, 1), mode 1 the picture
+    colour of (category, instance) from cat_table (int32 [256] device tensor, pan_format.category_table; None in mode 0), painted into
+    out, H * W * 3 contiguous uint8."""
+    require_cuda(pred_2ch, cat_table, out)
+    if pred_2ch.dtype != torch.uint8 or pred_2ch.dim() != 3 or pred_2ch.shape[2] != 3 or not pred_2ch.is_contiguous():
+        raise ValueError("pan_stable_colors: pred_2ch must be contiguous uint8 [H,W,3], got %s %s" % (tuple(pred_2ch.shape), pred_2ch.dtype))
+    H, W = int(pred_2ch.shape[0]), int(pred_2ch.shape[1])
+    if out.dtype != torch.uint8 or out.numel() != H * W * 3 or not out.is_contiguous():
+        raise ValueError("pan_stable_colors: out must be a contiguous uint8 tensor of %d bytes" % (H * W * 3))
+    check(lib().upsnet_pan_stable_colors(stream(), ptr(pred_2ch), H, W, ptr(cat_table), int(mode), ptr(out)), "pan_stable_colors")
+    return out
