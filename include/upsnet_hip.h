@@ -1186,6 +1186,63 @@ int upsnet_pan_track_step(void *stream, const unsigned char *pan_2ch, int height
 int upsnet_pan_stable_colors(void *stream, const unsigned char *pred_2ch, int height, int width, const int *cat_table, int mode,
                              unsigned char *rgb);
 
+/* ============================== Video metrics of tracked sequences: VPQ and STQ ============================== */
+
+/* Video Panoptic Quality (Kim et al., Video Panoptic Segmentation, CVPR 2020) and Segmentation and Tracking Quality (Weber et al.,
+ * STEP, NeurIPS 2021 datasets track). The reference has no video metric: the rules are this project's restatement of the published
+ * definitions (csrc/video_eval.hip; restated in plain numpy in tests/video_pq_ref.py), never compared with a build of either tool.
+ *
+ * Per sequence. Prediction: one tracked 2-channel map per frame (uint8 [H,W,3], channel 0 category with 255 = VOID, channel 1
+ * instance); a predicted TUBE is a key c << 8 | j with c != 255 (stuff: j = 0). Ground truth: one panoptic RGB map per frame (id = R +
+ * 256 G + 65536 B, 0 = VOID) whose ids mean the same object in every frame, and the SEQUENCE TABLE: the union of the frames' segments
+ * in ascending id, at most max_gt rows (id, category, iscrowd). Areas are always pixel counts. A GT pixel whose id is 0 or not in the
+ * table is IGNORED.
+ *
+ * VPQ. For every window length n of `windows` (ascending, unique, each in 1..8) and every start s in 0..frames - n, summed over the n
+ * frames: area_p[key], area_g[row], void[key] (pixels of the key on ignored GT), inter[row][key] counted only where cat(row) ==
+ * cat(key). Then as _pq_compute_single_core treats one image:
+ *   TP  non-crowd rows in ascending id, every key with inter > 0: iou = (double)inter / (double)(area_p + area_g - inter - void);
+ *       iou > 0.5: tp[c]++, iou_sum[c] += iou, both matched;
+ *   FN  every unmatched non-crowd row with area_g > 0 in the window: fn[c]++;
+ *   FP  every unmatched key with area_p > 0 in the window: ign = void[key] + the sum of inter over ALL crowd rows of the key's
+ *       category (a stated choice; upsnet_pq_accumulate keeps the reference's last-crowd-row rule); skipped iff (double)ign /
+ *       (double)area_p > 0.5, else fp[c]++.
+ * iou_sum accumulates in float64 in a fixed order: sequences in the order added, windows by ascending start, rows by ascending id.
+ * tp / fp / fn / iou are [num_windows][256]; PQ per window length and the mean over `windows` are the host's (dataset/video_pq.py).
+ *
+ * STQ. Per sequence, over non-ignored pixels only, GT row r of category c_g, pred key (c_p, j):
+ *   semantic     conf[c_g][c_p]++, pred VOID in column 255, crowd rows with their category, accumulated over all sequences; IoU_c =
+ *                conf[c][c] / (row sum + column sum - conf[c][c]) for the categories whose denominator is > 0, iou their mean;
+ *   association  GT tracks: thing, non-crowd rows; pred tracks: keys of a thing category; G[r] pixels of the GT track, P[key] pixels
+ *                of the pred track on neither ignored nor thing-crowd GT, I[r][key] their joint pixels WHATEVER the categories;
+ *                aq_sum = sum over r in ascending id of (1.0 / G[r]) * (sum over keys with I > 0 in ascending key of I * ((double)I /
+ *                (double)(G + P - I))), float64; AQ = sum of aq_sum / max(number of GT tracks with G > 0, 1); STQ = sqrt(AQ * iou).
+ * The device delivers the sequence's integer cells; the float64 operations of STQ run on the host from them.
+ *
+ * upsnet_video_eval_frame queues one frame: ONE pass over the pixels whatever `windows` is, the compaction of the frame's cells into
+ * a ring of the last max_window frames and into the sequence-level table, and the window pass of every window that ends at this
+ * frame -- three launches, no host read. table: device int [2 * num_rows + num_crowd]: per row in ascending id (id, category | iscrowd
+ * << 8), then the indices of the crowd rows. windows: HOST ints. frame counts from 0 within the sequence; `sequence` and `frame` only
+ * name the place in an error. cat_known uint8 [256]. status [2]: [0] bits 1 / 2 / 4: the frame table, the sequence table was full, a
+ * window held more than 8192 list entries -- counts were dropped and the result is void (the caller raises); [1] starts as INT64_MAX
+ * and takes the minimum of sequence << 32 | frame << 8 | category over pred categories that are not known.
+ * upsnet_video_eval_end delivers the sequence: sequence_out (device, upsnet_video_eval_sequence_ints() ints): [0] = number of cells,
+ * then from [2] on pairs (cell + 1, count), in arbitrary order; cell = kind << 28 | index with kind 0 JOINT (row << 16 | key), 1 AREA_P
+ * (key), 2 VOID (key), 3 AREA_G (row), JOINT cells of every category pair. host_out (pinned, may be NULL) takes a copy, asynchronously.
+ * workspace: upsnet_video_eval_workspace_bytes(max_gt, H, W, max_window) bytes (0: arguments out of range), ZEROED ONCE; the frame
+ * tables are zero after every frame and all of it is zero after upsnet_video_eval_end. The frame table is sized from H * W (one slot
+ * per 16 pixels, at least 4096); a sequence holds at most 32768 distinct cells and frames * H * W < 2^31 pixels.
+ * Refused before any launch: a null pointer, H * W outside 1..2^24, max_gt outside 0..4096, more rows than max_gt, windows that are
+ * not ascending, unique and in 1..max_window <= 8. */
+size_t upsnet_video_eval_workspace_bytes(int max_gt, int height, int width, int max_window);
+size_t upsnet_video_eval_sequence_ints(void);
+int upsnet_video_eval_frame(void *stream, const unsigned char *pred_2ch, const unsigned char *gt_rgb, int height, int width,
+                            const int *table, int num_rows, int num_crowd, int max_gt, const int *windows, int num_windows, int max_window,
+                            int frame, int sequence, const unsigned char *cat_known, void *workspace, int64_t *tp, int64_t *fp, int64_t *fn,
+                            double *iou, uint64_t *status);
+int upsnet_video_eval_end(void *stream, int height, int width, int max_gt, int max_window, void *workspace, int *sequence_out,
+                          int *host_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1969,3 +1969,67 @@ def pan_stable_colors(pred_2ch, cat_table, mode, out):
         raise ValueError("pan_stable_colors: out must be a contiguous uint8 tensor of %d bytes" % (H * W * 3))
     check(lib().upsnet_pan_stable_colors(stream(), ptr(pred_2ch), H, W, ptr(cat_table), int(mode), ptr(out)), "pan_stable_colors")
     return out
+
+
+def video_eval_workspace(max_gt, height, width, max_window, device):
+    """Zeroed workspace of video_eval_frame / video_eval_end for sequences of height x width frames, at most max_gt (0..4096) rows in the
+    sequence table and windows of at most max_window (1..8) frames; video_eval_end leaves all of it zero again."""
+    nbytes = int(lib().upsnet_video_eval_workspace_bytes(int(max_gt), int(height), int(width), int(max_window)))
+    if nbytes == 0:
+        raise ValueError("video_eval_workspace: max_gt %d outside 0..4096, frame size %dx%d outside 1..2^24 pixels or max_window %d outside 1..8"
+                         % (max_gt, height, width, max_window))
+    return torch.zeros((nbytes,), dtype=torch.uint8, device=device)
+
+
+def _video_eval_check_workspace(what, workspace, max_gt, H, W, max_window):
+    need = int(lib().upsnet_video_eval_workspace_bytes(int(max_gt), H, W, int(max_window)))
+    if need == 0 or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError("%s: workspace too small for (or no workspace exists for) max_gt %d, a frame of %d x %d and max_window %d"
+                         % (what, max_gt, H, W, max_window))
+
+
+def video_eval_frame(pred_2ch, gt_rgb, table, num_rows, num_crowd, max_gt, windows, frame, sequence, cat_known, workspace, tp, fp, fn,
+                     iou, status):
+    """One frame of a tracked sequence into the VPQ / STQ counts (include/upsnet_hip.h, csrc/video_eval.hip): pred_2ch / gt_rgb uint8
+    [H,W,3]; table int32 [2 * num_rows + num_crowd] (per row in ascending id: id, category | iscrowd << 8; then the crowd rows);
+    windows: ascending host ints in 1..8; tp / fp / fn int64 [len(windows), 256], iou float64 [len(windows), 256], status int64 [2].
+    Three launches, no host synchronisation, no allocation."""
+    require_cuda(pred_2ch, gt_rgb, table, cat_known, workspace, tp, fp, fn, iou, status)
+    if pred_2ch.dtype != torch.uint8 or gt_rgb.dtype != torch.uint8 or pred_2ch.dim() != 3 or pred_2ch.shape[2] != 3 \
+            or tuple(pred_2ch.shape) != tuple(gt_rgb.shape):
+        raise ValueError("video_eval_frame: pred_2ch %s %s and gt_rgb %s %s must both be uint8 [H,W,3]"
+                         % (tuple(pred_2ch.shape), pred_2ch.dtype, tuple(gt_rgb.shape), gt_rgb.dtype))
+    windows = [int(n) for n in windows]
+    nw = len(windows)
+    if not 1 <= nw <= 8 or any(not 1 <= n <= 8 for n in windows) or any(b <= a for a, b in zip(windows, windows[1:])):
+        raise ValueError("video_eval_frame: windows must be ascending, unique and in 1..8, got %s" % (windows,))
+    num_rows, num_crowd = int(num_rows), int(num_crowd)
+    if table.dtype != torch.int32 or not table.is_contiguous() or table.numel() != 2 * num_rows + num_crowd or not 0 <= num_crowd <= num_rows:
+        raise ValueError("video_eval_frame: table must be contiguous int32 of 2 * %d + %d ints, got %s %s"
+                         % (num_rows, num_crowd, tuple(table.shape), table.dtype))
+    for t, dt, n in ((cat_known, torch.uint8, 256), (tp, torch.int64, nw * 256), (fp, torch.int64, nw * 256), (fn, torch.int64, nw * 256),
+                     (iou, torch.float64, nw * 256), (status, torch.int64, 2)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise ValueError("video_eval_frame: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
+    pred_2ch, gt_rgb = pred_2ch.contiguous(), gt_rgb.contiguous()
+    H, W = int(pred_2ch.shape[0]), int(pred_2ch.shape[1])
+    _video_eval_check_workspace("video_eval_frame", workspace, max_gt, H, W, windows[-1])
+    check(lib().upsnet_video_eval_frame(stream(), ptr(pred_2ch), ptr(gt_rgb), H, W, ptr(table) if table.numel() else None, num_rows, num_crowd,
+                                        int(max_gt), int_array(windows), nw, windows[-1], int(frame), int(sequence), ptr(cat_known),
+                                        ptr(workspace), ptr(tp), ptr(fp), ptr(fn), ptr(iou), ptr(status)), "video_eval_frame")
+
+
+def video_eval_end(height, width, max_gt, max_window, workspace, sequence_out, host_out=None):
+    """The end of a sequence (csrc/video_eval.hip): the sequence-level cells into sequence_out (device int32,
+    upsnet_video_eval_sequence_ints() ints: [0] their number, pairs (cell + 1, count) from [2] on), copied asynchronously into
+    host_out (pinned int32 of the same size; None: no copy); the workspace is all zero afterwards. Two launches and the copy."""
+    require_cuda(workspace, sequence_out)
+    ints = int(lib().upsnet_video_eval_sequence_ints())
+    if sequence_out.dtype != torch.int32 or sequence_out.numel() != ints or not sequence_out.is_contiguous():
+        raise ValueError("video_eval_end: sequence_out must be contiguous int32 of %d ints, got %s %s" % (ints, tuple(sequence_out.shape), sequence_out.dtype))
+    if host_out is not None and (host_out.is_cuda or not host_out.is_pinned() or host_out.dtype != torch.int32 or host_out.numel() != ints
+                                 or not host_out.is_contiguous()):
+        raise ValueError("video_eval_end: host_out must be contiguous pinned int32 host memory of %d ints" % ints)
+    _video_eval_check_workspace("video_eval_end", workspace, max_gt, int(height), int(width), max_window)
+    check(lib().upsnet_video_eval_end(stream(), int(height), int(width), int(max_gt), int(max_window), ptr(workspace), ptr(sequence_out),
+                                      ptr(host_out)), "video_eval_end")

@@ -2,7 +2,7 @@
 
     python -m upsnet_amd.sequence --cfg <yaml> (--weight_path <pth> | --synthetic_weights) --frames <folder> --out <dir>
                                   --panoptic_categories <json> [--track_iou T] [--track_max_age N] [--combined]
-                                  [--vis_panoptic {flat,overlay,both}] [--in-flight N]
+                                  [--vis_panoptic {flat,overlay,both}] [--in-flight N] [--video_gt <folder> [--vpq_windows N [N ...]]]
     python -m upsnet_amd.sequence --cfg <yaml> --track_only <folder of pan_2ch PNGs> --out <dir> --panoptic_categories <json> [...]
 
 No annotation JSON is needed. The image files directly in --frames, sorted by name, are one sequence (named after the folder); every
@@ -21,6 +21,10 @@ serials (track_id) go on counting, so a track_id names one object of one sequenc
   vis/, vis_flat/       with --vis_panoptic: the pictures, every track in one colour throughout
 --track_only tracks an already written prediction (for instance results/pans_unified/pan_2ch of an evaluation run) without building
 the model; the photographs are not there, so of the pictures only 'flat' can be drawn. One rank only.
+--video_gt <folder> scores every sequence, once it is tracked and written, against <folder>/<sequence>/gt.json and
+<folder>/<sequence>/pan/<frame>.png (VPQ and STQ on the device; upsnet_amd/video_eval.py says how the frames
+pair and re-scores written runs); --vpq_windows sets the window lengths (default 1 2 3 4). Then <out>/video_scores.json is written and
+the summary logged. Without --video_gt nothing else is written than above.
 """
 import argparse
 import json
@@ -95,8 +99,9 @@ def load_pan_2ch(path):
     return np.ascontiguousarray(im[:, :, :3])
 
 
-def track_and_write(tracker, name, pans, file_names, categories, out_dir, vis=None, image_paths=None):
-    """Track one sequence's 2-channel maps and write its files under out_dir; returns (annotations, tracks)."""
+def track_and_write(tracker, name, pans, file_names, categories, out_dir, vis=None, image_paths=None, score=None):
+    """Track one sequence's 2-channel maps and write its files under out_dir; returns (annotations, tracks). score(name, tracked maps,
+    file names), if given, is called once everything is written."""
     from .dataset.pan_format import write_panoptic
     from .dataset.pan_vis import vis_panoptic
     tracker.reset()
@@ -127,6 +132,8 @@ def track_and_write(tracker, name, pans, file_names, categories, out_dir, vis=No
     for mode in {'flat': ('flat',), 'overlay': ('overlay',), 'both': ('flat', 'overlay')}.get(vis, ()):
         vis_panoptic(tracked, images, categories, out_dir, mode, image_paths=image_paths, stable_ids=True)
     logger.info('sequence %s: %d frames, %d tracks, written to %s', name, len(tracked), len(tracks), os.path.abspath(out_dir))
+    if score is not None:
+        score(name, tracked, file_names)
     return annotations, tracks
 
 
@@ -145,11 +152,13 @@ def parse_args(argv=None):
     p.add_argument('--combined', action='store_true', help='track get_combined_pan_result (detections + semantic map) instead of the panoptic head')
     p.add_argument('--vis_panoptic', choices=('flat', 'overlay', 'both'), default=None, help='also draw the tracked maps')
     p.add_argument('--in-flight', type=int, default=1, help='images in flight (1 = the reference loop)')
-    return p.parse_args(argv)
+    from .video_eval import add_arguments, check_arguments
+    add_arguments(p)
+    return check_arguments(p, p.parse_args(argv))
 
 
 def main(argv=None):
-    """Returns {'sequences': [(name, output folder, annotations, tracks)]}."""
+    """Returns {'sequences': [(name, output folder, annotations, tracks)]}, with --video_gt also 'video_scores': the summary."""
     args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(asctime)-15s | %(message)s')
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -190,13 +199,27 @@ def main(argv=None):
         categories = json.load(f)['categories']
     tracker = PanopticTracker(iou_thresh=args.track_iou, max_age=args.track_max_age)
     done = []
+    score, finish = None, lambda res: res
+    if args.video_gt:
+        from . import video_eval
+        from .dataset.video_pq import VideoPanopticEvaluator
+        if not os.path.isdir(args.video_gt):
+            raise SystemExit('--video_gt: no folder at %s' % args.video_gt)
+        evaluator, scored = VideoPanopticEvaluator(categories, windows=args.vpq_windows), []
+
+        def score(name, tracked, file_names):
+            scored.append((name, video_eval.score_sequence(evaluator, name, tracked, file_names, args.video_gt)))
+
+        def finish(res):
+            res['video_scores'] = video_eval.write_scores(evaluator, args.video_gt, scored, os.path.join(args.out, 'video_scores.json'))
+            return res
     if args.track_only:
         for name, paths in sequences:
             pans = [load_pan_2ch(p) for p in paths]
             out_dir = os.path.join(args.out, name)
             done.append((name, out_dir) + track_and_write(tracker, name, pans, [os.path.basename(p) for p in paths], categories, out_dir,
-                                                          vis=args.vis_panoptic))
-        return {'sequences': done}
+                                                          vis=args.vis_panoptic, score=score))
+        return finish({'sequences': done})
     from .evaluate import panoptic_predictions, run_inference
     from .upsnet_end2end_test import init_distributed, load_checkpoint_model
     _, _, device = init_distributed()
@@ -212,8 +235,8 @@ def main(argv=None):
         pans = panoptic_predictions(seq, results, args.combined)
         out_dir = os.path.join(args.out, name)
         done.append((name, out_dir) + track_and_write(tracker, name, pans, [e['file_name'] for e in seq.roidb], categories, out_dir,
-                                                      vis=args.vis_panoptic, image_paths=paths))
-    return {'sequences': done}
+                                                      vis=args.vis_panoptic, image_paths=paths, score=score))
+    return finish({'sequences': done})
 
 
 if __name__ == '__main__':
