@@ -1243,6 +1243,61 @@ int upsnet_video_eval_frame(void *stream, const unsigned char *pred_2ch, const u
 int upsnet_video_eval_end(void *stream, int height, int width, int max_gt, int max_window, void *workspace, int *sequence_out,
                           int *host_out);
 
+/* ============================== MOTS measures of tracked sequences ============================== */
+
+/* sMOTSA, MOTSA, MOTSP, IDS, Frag and MT / PT / ML (Voigtlaender et al., MOTS: Multi-Object Tracking and Segmentation, CVPR 2019).
+ * The reference has no video metric: the rules are this project's restatement of the published definitions (csrc/mots_eval.hip;
+ * restated in plain numpy in tests/mots_ref.py), never compared with a build of mots_tools.
+ *
+ * Per sequence. Prediction, ground truth and the SEQUENCE TABLE are exactly those of upsnet_video_eval_frame: a tracked 2-channel map
+ * and a panoptic RGB map (id = R + 256 G + 65536 B) per frame, the table the union of the frames' segments in ascending id. The scored
+ * categories are the THING categories. For a thing category c at frame t:
+ *   GT objects   the non-crowd rows of category c; a row is PRESENT at t iff it has at least one pixel in frame t;
+ *   ignore(c)    the GT pixels whose id is 0 or not in the table, plus the pixels of every crowd row of category c (crowd rows of
+ *                other categories and stuff rows are not ignore);
+ *   hypotheses   the keys c << 8 | j with at least one pixel in frame t, whatever j;
+ *   match        row r and key k of the same category match iff 3 * I > A_g + A_p in int64: IoU > 0.5 on the whole masks (ignore pixels
+ *                are not taken out of the union). Each row and each key has at most one partner: I <= A_p gives 2 * I > A_g, and two
+ *                disjoint keys cannot each cover more than half of one row (and the same with the sides exchanged);
+ *   counts       per match tp[c]++ and soft[c] += (double)I / (double)(A_g + A_p - I); per present, unmatched row fn[c]++; per present
+ *                row gt_masks[c]++; per unmatched key fp[c]++, unless 2 * ign > A_p, ign the key's pixels on ignore(c): then
+ *                fp_ignored[c]++ instead;
+ *   identity     per row, `last` is the key it last matched, in any earlier frame, across gaps and absences; a match with `last` set
+ *                and different from k: ids[c]++; then last = k;
+ *   fragments    per row, `gap` is set when the row is present and unmatched after it has been matched at least once; a match with
+ *                `gap` set: frag[c]++, and gap is cleared;
+ *   coverage     present[r] and tracked[r] count frames; at the end of the sequence every row with present > 0 is MT iff 5 * tracked
+ *                > 4 * present, ML iff 5 * tracked < present, else PT.
+ * soft accumulates in float64 in a fixed order: sequences in the order added, frames in order, rows by ascending id. MOTSA = (tp - fp -
+ * ids) / max(gt_masks, 1), sMOTSA = (soft - fp - ids) / max(gt_masks, 1), MOTSP = soft / max(tp, 1) are the host's (dataset/mots.py).
+ *
+ * upsnet_mots_eval_frame queues one frame: one pass over the pixels, the match pass over the frame's cells and the row-state pass --
+ * three launches, no host read. table: device int [2 * num_rows]: per row in ascending id (id, category | iscrowd << 8 | isthing << 9).
+ * cat_info uint8 [256]: bit 0 the category is known, bit 1 it is a thing. counts: int64 [7][256] = tp, fp, fn, gt_masks, ids, frag,
+ * fp_ignored; soft: double [256]. frame counts from 0 within the sequence and also selects one of two list headers by its parity, so
+ * frames must be queued in order; `sequence` only names the place in an error. status [2]: [0] bit 1: the frame table was full -- counts
+ * were dropped and the result is void (the caller raises); [1] starts as INT64_MAX and takes the minimum of sequence << 32 | frame << 8
+ * | category over pred categories that are not known.
+ * upsnet_mots_eval_end ends the sequence: mtl int64 [3][256] takes MT, PT, ML per category (added); one launch.
+ * workspace: upsnet_mots_eval_workspace_bytes(max_gt, H, W) bytes (0: arguments out of range), ZEROED ONCE; everything but the four
+ * state words per row is zero after every frame and all of it is zero after upsnet_mots_eval_end. The frame table is sized from H * W
+ * (one slot per 16 pixels, at least 4096).
+ * Refused before any launch: a null pointer, H * W outside 1..2^24, max_gt outside 0..4096, more rows than max_gt, frame outside
+ * 0..2^24-1, sequence outside 0..2^30-1, a workspace that is not 8-byte aligned. */
+size_t upsnet_mots_eval_workspace_bytes(int max_gt, int height, int width);
+int upsnet_mots_eval_frame(void *stream, const unsigned char *pred_2ch, const unsigned char *gt_rgb, int height, int width,
+                           const int *table, int num_rows, int max_gt, int frame, int sequence, const unsigned char *cat_info,
+                           void *workspace, int64_t *counts, double *soft, uint64_t *status);
+int upsnet_mots_eval_end(void *stream, int height, int width, const int *table, int num_rows, int max_gt, void *workspace, int64_t *mtl);
+
+/* COCO RLE of every thing segment of one 2-channel map (a key c << 8 | i with c != 255 and i >= 1, as in upsnet_pan_track_step): the
+ * positions p = x * height + y of the column-major flattening at which the membership of the key changes, the wrap from one column's
+ * last pixel to the next column's first counting as adjacent; a segment that holds pixel 0 has a change at 0, none is reported at
+ * height * width. pairs[i] = key << 24 | p for i < min(*count, cap), in arbitrary order (sorting them gives every segment's positions in
+ * ascending order, segments by ascending key); *count is the number of changes even when it exceeds cap, so the caller grows pairs and
+ * calls again. One memset and one launch. Refused before any launch: a null pointer, height * width outside 1..2^24, cap < 0. */
+int upsnet_pan_rle_transitions(void *stream, const unsigned char *pan_2ch, int height, int width, int cap, int64_t *pairs, int *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,10 @@ _SIGNATURES = {
     "upsnet_video_eval_sequence_ints": (c_size_t, []),
     "upsnet_video_eval_frame": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "upsnet_video_eval_end": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    "upsnet_mots_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "upsnet_mots_eval_frame": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "upsnet_mots_eval_end": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P]),
+    "upsnet_pan_rle_transitions": (c_int, [P, P, c_int, c_int, c_int, P, P]),
 }
 
 _lib = None

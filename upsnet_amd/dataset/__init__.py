@@ -3,3 +3,4 @@ from .coco import coco
 from .boundary import boundary_dilation, mask_to_boundary
 from .pan_track import PanopticTracker, track_sequence
 from .video_pq import VideoPanopticEvaluator
+from .mots import MOTSEvaluator

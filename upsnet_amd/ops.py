@@ -2033,3 +2033,73 @@ def video_eval_end(height, width, max_gt, max_window, workspace, sequence_out, h
     _video_eval_check_workspace("video_eval_end", workspace, max_gt, int(height), int(width), max_window)
     check(lib().upsnet_video_eval_end(stream(), int(height), int(width), int(max_gt), int(max_window), ptr(workspace), ptr(sequence_out),
                                       ptr(host_out)), "video_eval_end")
+
+
+def mots_eval_workspace_bytes(max_gt, height, width):
+    """Bytes of the workspace of mots_eval_frame / mots_eval_end for sequences of height x width frames and at most max_gt (0..4096)
+    rows in the sequence table: a uint8 tensor of the caller's (dataset/mots.py), zeroed once; mots_eval_end leaves all of it zero again."""
+    nbytes = int(lib().upsnet_mots_eval_workspace_bytes(int(max_gt), int(height), int(width)))
+    if nbytes == 0:
+        raise ValueError("mots_eval_workspace_bytes: max_gt %d outside 0..4096 or frame size %dx%d outside 1..2^24 pixels" % (max_gt, height, width))
+    return nbytes
+
+
+def _mots_eval_check(what, workspace, table, num_rows, max_gt, H, W):
+    need = int(lib().upsnet_mots_eval_workspace_bytes(int(max_gt), H, W))
+    if need == 0 or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError("%s: workspace too small for (or no workspace exists for) max_gt %d and a frame of %d x %d" % (what, max_gt, H, W))
+    if table.dtype != torch.int32 or not table.is_contiguous() or table.numel() != 2 * num_rows or not 0 <= num_rows <= max_gt:
+        raise ValueError("%s: table must be contiguous int32 of 2 * %d ints with at most max_gt %d rows, got %s %s"
+                         % (what, num_rows, max_gt, tuple(table.shape), table.dtype))
+
+
+def mots_eval_frame(pred_2ch, gt_rgb, table, num_rows, max_gt, frame, sequence, cat_info, workspace, counts, soft, status):
+    """One frame of a tracked sequence into the MOTS counts (include/upsnet_hip.h, csrc/mots_eval.hip): pred_2ch / gt_rgb uint8 [H,W,3];
+    table int32 [2 * num_rows] (per row in ascending id: id, category | iscrowd << 8 | isthing << 9); cat_info uint8 [256] (bit 0 known,
+    bit 1 thing); counts int64 [7, 256] (tp, fp, fn, gt_masks, ids, frag, fp_ignored), soft float64 [256], status int64 [2].
+    Three launches, no host synchronisation, no allocation."""
+    require_cuda(pred_2ch, gt_rgb, table, cat_info, workspace, counts, soft, status)
+    if pred_2ch.dtype != torch.uint8 or gt_rgb.dtype != torch.uint8 or pred_2ch.dim() != 3 or pred_2ch.shape[2] != 3 \
+            or tuple(pred_2ch.shape) != tuple(gt_rgb.shape):
+        raise ValueError("mots_eval_frame: pred_2ch %s %s and gt_rgb %s %s must both be uint8 [H,W,3]"
+                         % (tuple(pred_2ch.shape), pred_2ch.dtype, tuple(gt_rgb.shape), gt_rgb.dtype))
+    num_rows = int(num_rows)
+    for t, dt, n in ((cat_info, torch.uint8, 256), (counts, torch.int64, 7 * 256), (soft, torch.float64, 256), (status, torch.int64, 2)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise ValueError("mots_eval_frame: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
+    pred_2ch, gt_rgb = pred_2ch.contiguous(), gt_rgb.contiguous()
+    H, W = int(pred_2ch.shape[0]), int(pred_2ch.shape[1])
+    _mots_eval_check("mots_eval_frame", workspace, table, num_rows, max_gt, H, W)
+    check(lib().upsnet_mots_eval_frame(stream(), ptr(pred_2ch), ptr(gt_rgb), H, W, ptr(table) if table.numel() else None, num_rows, int(max_gt),
+                                       int(frame), int(sequence), ptr(cat_info), ptr(workspace), ptr(counts), ptr(soft), ptr(status)),
+          "mots_eval_frame")
+
+
+def mots_eval_end(height, width, table, num_rows, max_gt, workspace, mtl):
+    """The end of a sequence (csrc/mots_eval.hip): MT / PT / ML of its rows added into mtl (int64 [3, 256]); the workspace is all zero
+    afterwards. One launch."""
+    require_cuda(table, workspace, mtl)
+    if mtl.dtype != torch.int64 or mtl.numel() != 3 * 256 or not mtl.is_contiguous():
+        raise ValueError("mots_eval_end: mtl must be contiguous int64 of 768 words, got %s %s" % (tuple(mtl.shape), mtl.dtype))
+    num_rows = int(num_rows)
+    _mots_eval_check("mots_eval_end", workspace, table, num_rows, max_gt, int(height), int(width))
+    check(lib().upsnet_mots_eval_end(stream(), int(height), int(width), ptr(table) if table.numel() else None, num_rows, int(max_gt),
+                                     ptr(workspace), ptr(mtl)), "mots_eval_end")
+
+
+def pan_rle_transitions(pan_2ch, pairs, count):
+    """COCO RLE of every thing segment (category != 255, instance >= 1) of one 2-channel map (csrc/mots_eval.hip): pairs (int64
+    [cap], the caller's) takes the words key << 24 | p in arbitrary order, p the column-major positions at which the key's membership
+    changes; count (int32 [1]) takes their number, even when it exceeds cap -- the caller then grows pairs and calls again
+    (dataset/mots.py: segment_transitions). A memset and one launch, no host synchronisation, no allocation."""
+    require_cuda(pan_2ch, pairs, count)
+    if pan_2ch.dtype != torch.uint8 or pan_2ch.dim() != 3 or pan_2ch.shape[2] != 3 or not pan_2ch.is_contiguous():
+        raise ValueError("pan_rle_transitions: pan_2ch must be contiguous uint8 [H,W,3], got %s %s" % (tuple(pan_2ch.shape), pan_2ch.dtype))
+    H, W = int(pan_2ch.shape[0]), int(pan_2ch.shape[1])
+    if not 0 < H * W <= (1 << 24):
+        raise ValueError("pan_rle_transitions: a map of %d x %d pixels: H * W must lie in 1..2^24" % (H, W))
+    if pairs.dtype != torch.int64 or pairs.dim() != 1 or not pairs.is_contiguous() or count.dtype != torch.int32 or count.numel() != 1:
+        raise ValueError("pan_rle_transitions: pairs must be contiguous int64 [cap] and count int32 [1], got %s %s and %s %s"
+                         % (tuple(pairs.shape), pairs.dtype, tuple(count.shape), count.dtype))
+    cap = int(pairs.numel())
+    check(lib().upsnet_pan_rle_transitions(stream(), ptr(pan_2ch), H, W, cap, ptr(pairs) if cap else None, ptr(count)), "pan_rle_transitions")

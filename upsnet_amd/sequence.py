@@ -25,6 +25,9 @@ the model; the photographs are not there, so of the pictures only 'flat' can be 
 <folder>/<sequence>/pan/<frame>.png (VPQ and STQ on the device; upsnet_amd/video_eval.py says how the frames
 pair and re-scores written runs); --vpq_windows sets the window lengths (default 1 2 3 4). Then <out>/video_scores.json is written and
 the summary logged. Without --video_gt nothing else is written than above.
+The MOTS measures (sMOTSA, MOTSA, MOTSP, IDS, Frag, MT / PT / ML) are opt-in: --eval_mots adds them, against
+--video_gt, as 'mots' in the summary; --mots_gt <folder> scores them alone against <folder>/<sequence>.txt in the MOTS text format
+(frames pair by index) and writes <out>/mots_scores.json; --write_mots writes <out>/<sequence>/mots.txt in that format.
 """
 import argparse
 import json
@@ -158,7 +161,8 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    """Returns {'sequences': [(name, output folder, annotations, tracks)]}, with --video_gt also 'video_scores': the summary."""
+    """Returns {'sequences': [(name, output folder, annotations, tracks)]}, with --video_gt also 'video_scores': the summary, with
+    --mots_gt also 'mots_scores'."""
     args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(asctime)-15s | %(message)s')
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -200,19 +204,15 @@ def main(argv=None):
     tracker = PanopticTracker(iou_thresh=args.track_iou, max_age=args.track_max_age)
     done = []
     score, finish = None, lambda res: res
-    if args.video_gt:
+    if args.video_gt or args.mots_gt or args.write_mots:
         from . import video_eval
-        from .dataset.video_pq import VideoPanopticEvaluator
-        if not os.path.isdir(args.video_gt):
-            raise SystemExit('--video_gt: no folder at %s' % args.video_gt)
-        evaluator, scored = VideoPanopticEvaluator(categories, windows=args.vpq_windows), []
+        scoring = video_eval.Scoring(args, categories)
 
         def score(name, tracked, file_names):
-            scored.append((name, video_eval.score_sequence(evaluator, name, tracked, file_names, args.video_gt)))
+            scoring.add(name, tracked, file_names, os.path.join(args.out, name))
 
         def finish(res):
-            res['video_scores'] = video_eval.write_scores(evaluator, args.video_gt, scored, os.path.join(args.out, 'video_scores.json'))
-            return res
+            return scoring.finish(res, args.out)
     if args.track_only:
         for name, paths in sequences:
             pans = [load_pan_2ch(p) for p in paths]

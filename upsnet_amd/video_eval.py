@@ -13,6 +13,14 @@ so two runs can be compared. Frames pair by the name of their PNG (pan_format.pn
 truth may cover a subset of the predicted frames (Cityscapes-VPS labels every fifth): only those frames are scored, in the order of
 the prediction. A ground-truth frame without a prediction ends the run, naming it.
 Written: <pred>/video_scores.json (or --out): {'video_gt', 'windows', 'sequences': [{'name', 'frames'}], 'summary'}; the summary is logged.
+
+The MOTS measures (sMOTSA, MOTSA, MOTSP, IDS, Frag, MT / PT / ML; dataset/mots.py) are opt-in:
+    --eval_mots          the same frames against the same --video_gt also go through MOTSEvaluator: 'mots' in the summary
+    --mots_gt <folder>   (instead of, or beside, --video_gt) MOTS alone against <folder>/<sequence>.txt in the MOTS text format
+                         (`<frame> <id> <class> <H> <W> <rle>`; class 10 is an ignore region); the frames pair by index;
+                         written: <pred>/mots_scores.json {'mots_gt', 'sequences', 'summary'}
+    --write_mots         writes <pred>/<sequence>/mots.txt, every tracked thing segment in that format (id = category * 1000 + instance);
+                         alone it needs neither a ground truth nor --panoptic_categories
 """
 import argparse
 import json
@@ -31,11 +39,19 @@ def add_arguments(p):
                    help='score the tracked sequences (VPQ, STQ) against <FOLDER>/<sequence>/gt.json and <FOLDER>/<sequence>/pan/<frame>.png')
     p.add_argument('--vpq_windows', type=int, nargs='+', default=None, metavar='N',
                    help='VPQ window lengths in scored frames: ascending, unique, each in 1..8 (default 1 2 3 4)')
+    p.add_argument('--eval_mots', action='store_true',
+                   help="also score the MOTS measures (sMOTSA, MOTSA, MOTSP, IDS, Frag, MT/PT/ML) against --video_gt: 'mots' in the summary")
+    p.add_argument('--mots_gt', type=str, default='', metavar='FOLDER',
+                   help='score the MOTS measures against <FOLDER>/<sequence>.txt (MOTS text format, frames pair by index): mots_scores.json')
+    p.add_argument('--write_mots', action='store_true', help='write every tracked sequence in the MOTS text format: <sequence>/mots.txt')
 
 
 def check_arguments(p, args):
-    """The refusals both commands share (argparse's exit): --vpq_windows without --video_gt, windows that are not ascending in 1..8."""
+    """The refusals both commands share (argparse's exit): --vpq_windows without --video_gt, windows that are not ascending in 1..8,
+    --eval_mots without a ground truth."""
     from .dataset.video_pq import check_windows
+    if args.eval_mots and not args.video_gt and not args.mots_gt:
+        p.error('--eval_mots scores against a ground truth: it needs --video_gt <folder> or --mots_gt <folder>')
     if args.vpq_windows is not None and not args.video_gt:
         p.error('--vpq_windows sets the windows of the video scores: it needs --video_gt <folder>')
     try:
@@ -90,25 +106,105 @@ def load_png(path, option='--video_gt', what='an RGB panoptic PNG'):
     return np.ascontiguousarray(im[:, :, :3])
 
 
-def score_sequence(evaluator, name, pred_maps, pred_names, video_gt):
-    """Add one tracked sequence (its 2-channel maps, device tensors or numpy arrays, and their file names) to the evaluator; returns
-    the number of frames scored."""
+def score_sequence(evaluator, name, pred_maps, pred_names, video_gt, mots=None):
+    """Add one tracked sequence (its 2-channel maps, device tensors or numpy arrays, and their file names) to the evaluator -- and to
+    `mots`, a MOTSEvaluator, if given: the same frames against the same ground truth --; returns the number of frames scored."""
     from .dataset.pan_format import png_name
     annotations, pan = load_video_gt(video_gt, name)
     pairs = pair_frames(name, pred_names, annotations)
     gts = [load_png(os.path.join(pan, png_name(ann['file_name']))) for _, ann in pairs]
-    try:
-        evaluator.begin_sequence([ann['segments_info'] for _, ann in pairs], name=name)
-        for (k, _), gt in zip(pairs, gts):
-            evaluator.add_frame(pred_maps[k], gt)
-    except ValueError as e:
-        raise SystemExit('--video_gt: sequence %s: %s' % (name, e))
-    evaluator.end_sequence()
+    for ev in (evaluator, mots):
+        if ev is None:
+            continue
+        try:
+            ev.begin_sequence([ann['segments_info'] for _, ann in pairs], name=name)
+            for (k, _), gt in zip(pairs, gts):
+                ev.add_frame(pred_maps[k], gt)
+        except ValueError as e:
+            raise SystemExit('--video_gt: sequence %s: %s' % (name, e))
+        ev.end_sequence()
     return len(pairs)
 
 
-def write_scores(evaluator, video_gt, scored, path):
+def background_category(categories):
+    """The category of the pixels no mask of a MOTS text file covers: the smallest id that is not a thing category."""
+    cats = categories if isinstance(categories, dict) else {el['id']: el for el in categories}
+    return min(c for c in range(255) if cats.get(c, {}).get('isthing') != 1)
+
+
+def score_mots_txt(evaluator, name, pred_maps, mots_gt):
+    """Add one tracked sequence to a MOTSEvaluator against <mots_gt>/<name>.txt, frames paired by index; returns the frames scored."""
+    from .dataset.mots import MOTSText
+    path = os.path.join(mots_gt, name + '.txt')
+    if not os.path.isfile(path):
+        raise SystemExit('--mots_gt: no ground truth of sequence %s at %s' % (name, path))
+    try:
+        text = MOTSText(path, num_frames=len(pred_maps), background_category=background_category(evaluator.categories))
+        evaluator.begin_sequence(text.segments_info, name=name)
+        for t, m in enumerate(pred_maps):
+            evaluator.add_frame(m, text.frame(t))        # (one frame of ground truth at a time, however long the sequence)
+    except ValueError as e:
+        raise SystemExit('--mots_gt: sequence %s: %s' % (name, e))
+    evaluator.end_sequence()
+    return text.num_frames
+
+
+def write_mots_scores(evaluator, mots_gt, scored, path):
     summary = evaluator.summary()
+    with open(path, 'w') as f:
+        json.dump({'mots_gt': os.path.abspath(mots_gt), 'sequences': [{'name': n, 'frames': k} for n, k in scored], 'summary': summary}, f)
+    logger.info('MOTS scores of %d sequences written to %s', len(scored), os.path.abspath(path))
+    return summary
+
+
+class Scoring(object):
+    """What the options of a run ask for after a sequence is tracked: --video_gt (VPQ, STQ; with --eval_mots also MOTS), --mots_gt
+    (MOTS against text files) and --write_mots. The constructor refuses a ground-truth folder that does not exist (SystemExit).
+    add(name, tracked maps, file names, the sequence's folder) once per sequence; finish(result, folder, video_path=None) writes
+    <folder>/video_scores.json (or video_path, the re-scoring command's --out) and <folder>/mots_scores.json and adds 'video_scores' /
+    'mots_scores' to result."""
+
+    def __init__(self, args, categories):
+        self.args = args
+        self.video = self.mots = self.mots_txt = None
+        self.scored, self.scored_txt = [], []
+        for option in ('video_gt', 'mots_gt'):
+            folder = getattr(args, option)
+            if folder and not os.path.isdir(folder):
+                raise SystemExit('--%s: no folder at %s' % (option, folder))
+        if args.video_gt:
+            from .dataset.video_pq import VideoPanopticEvaluator
+            self.video = VideoPanopticEvaluator(categories, windows=args.vpq_windows)
+        if args.video_gt and args.eval_mots:
+            from .dataset.mots import MOTSEvaluator
+            self.mots = MOTSEvaluator(categories)
+        if args.mots_gt:
+            from .dataset.mots import MOTSEvaluator
+            self.mots_txt = MOTSEvaluator(categories)
+
+    def add(self, name, maps, file_names, seq_dir):
+        if self.args.write_mots:
+            from .dataset.mots import write_mots_txt
+            os.makedirs(seq_dir, exist_ok=True)
+            write_mots_txt(os.path.join(seq_dir, 'mots.txt'), maps)
+        if self.video is not None:
+            self.scored.append((name, score_sequence(self.video, name, maps, file_names, self.args.video_gt, mots=self.mots)))
+        if self.mots_txt is not None:
+            self.scored_txt.append((name, score_mots_txt(self.mots_txt, name, maps, self.args.mots_gt)))
+
+    def finish(self, result, folder, video_path=None):
+        if self.video is not None:
+            result['video_scores'] = write_scores(self.video, self.args.video_gt, self.scored,
+                                                  video_path or os.path.join(folder, 'video_scores.json'), mots=self.mots)
+        if self.mots_txt is not None:
+            result['mots_scores'] = write_mots_scores(self.mots_txt, self.args.mots_gt, self.scored_txt, os.path.join(folder, 'mots_scores.json'))
+        return result
+
+
+def write_scores(evaluator, video_gt, scored, path, mots=None):
+    summary = evaluator.summary()
+    if mots is not None:
+        summary['mots'] = mots.summary()
     with open(path, 'w') as f:
         json.dump({'video_gt': os.path.abspath(video_gt), 'windows': list(evaluator.windows),
                    'sequences': [{'name': n, 'frames': k} for n, k in scored], 'summary': summary}, f)
@@ -142,27 +238,26 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    """Returns the summary."""
+    """Returns the summary (with --mots_gt alone, that of the MOTS measures; with --write_mots alone, None)."""
     args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(asctime)-15s | %(message)s')
     if not args.pred:
         raise SystemExit('--pred <out folder of a sequence run> is required')
-    if not args.video_gt:
-        raise SystemExit('--video_gt <folder> is required')
-    if not args.panoptic_categories or not os.path.isfile(args.panoptic_categories):
-        raise SystemExit("--panoptic_categories: no panoptic JSON at %r (its 'categories' say which are things)" % args.panoptic_categories)
-    if not os.path.isdir(args.video_gt):
-        raise SystemExit('--video_gt: no folder at %s' % args.video_gt)
+    if not args.video_gt and not args.mots_gt and not args.write_mots:
+        raise SystemExit('--video_gt <folder> is required (or --mots_gt <folder>: the MOTS measures alone; or --write_mots: no scores)')
+    categories = None
+    if args.video_gt or args.mots_gt:          # (writing the text files needs no category table)
+        if not args.panoptic_categories or not os.path.isfile(args.panoptic_categories):
+            raise SystemExit("--panoptic_categories: no panoptic JSON at %r (its 'categories' say which are things)" % args.panoptic_categories)
+        with open(args.panoptic_categories, 'r') as f:
+            categories = json.load(f)['categories']
+    scoring = Scoring(args, categories)
     sequences = discover_predictions(args.pred)
-    with open(args.panoptic_categories, 'r') as f:
-        categories = json.load(f)['categories']
-    from .dataset.video_pq import VideoPanopticEvaluator
-    evaluator = VideoPanopticEvaluator(categories, windows=args.vpq_windows)
-    scored = []
     for name, paths in sequences:
         maps = [load_png(p, '--pred', 'a 2-channel panoptic map (an RGB PNG)') for p in paths]
-        scored.append((name, score_sequence(evaluator, name, maps, [os.path.basename(p) for p in paths], args.video_gt)))
-    return write_scores(evaluator, args.video_gt, scored, args.out or os.path.join(args.pred, 'video_scores.json'))
+        scoring.add(name, maps, [os.path.basename(p) for p in paths], os.path.join(args.pred, name))
+    res = scoring.finish({}, args.pred, args.out or None)
+    return res.get('video_scores', res.get('mots_scores'))
 
 
 if __name__ == '__main__':
