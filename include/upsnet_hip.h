@@ -1139,7 +1139,9 @@ int upsnet_box_vote(void *stream, const float *rois, const float *bbox_delta, co
  *   (cpu_nms.pyx:91-196, bit-identical; method 0 hard, 1 linear, 2 gaussian). The class's result is rows 0..N'-1 of the returned
  *   array in that order: box, DECAYED score, source row. The flat list in (class ascending, soft-NMS order) then goes through the
  *   top-max_det rule of upsnet_mask_roi on the decayed scores (max_det > 0 and more than max_det rows: keep score >= the max_det-th
- *   largest, order preserved), the dummy row when nothing survives and the zero rows up to max(max_det, 256).
+ *   largest, order preserved), the dummy row when nothing survives and the zero rows up to max(max_det, 256). Of the four outputs
+ *   the rows below max(|*num_out|, min(cap, max(max_det, 256))) are defined -- the selection, the dummy row, zero rows --, the rows
+ *   from there on are unspecified (upsnet_mask_roi_ex's sentence about rows >= *num_out holds from that row on only).
  *   A class's state is LDS-resident: it holds at most 4096 candidates. A class with more keeps its first 4096 and the count comes
  *   out NEGATIVE (the overflow convention of upsnet_mask_roi); with num_rois <= 4096 this cannot happen.
  * Two launches (one workgroup per class, then the finalize); nothing is synchronised or allocated. Refused before any launch: a null
@@ -1228,7 +1230,8 @@ int upsnet_pan_stable_colors(void *stream, const unsigned char *pred_2ch, int he
  * and takes the minimum of sequence << 32 | frame << 8 | category over pred categories that are not known.
  * upsnet_video_eval_end delivers the sequence: sequence_out (device, upsnet_video_eval_sequence_ints() ints): [0] = number of cells,
  * then from [2] on pairs (cell + 1, count), in arbitrary order; cell = kind << 28 | index with kind 0 JOINT (row << 16 | key), 1 AREA_P
- * (key), 2 VOID (key), 3 AREA_G (row), JOINT cells of every category pair. host_out (pinned, may be NULL) takes a copy, asynchronously.
+ * (key), 2 VOID (key), 3 AREA_G (row), JOINT cells of every category pair. [1] and the ints past the last pair are unspecified
+ * (the caller reads 2 + 2 * [0] ints). host_out (pinned, may be NULL) takes a copy, asynchronously.
  * workspace: upsnet_video_eval_workspace_bytes(max_gt, H, W, max_window) bytes (0: arguments out of range), ZEROED ONCE; the frame
  * tables are zero after every frame and all of it is zero after upsnet_video_eval_end. The frame table is sized from H * W (one slot
  * per 16 pixels, at least 4096); a sequence holds at most 32768 distinct cells and frames * H * W < 2^31 pixels.

@@ -1,6 +1,7 @@
 """CPU: tests/memguard.py itself -- poison fill, torch's own shapes and strides, band violations with their call site, the patch undone
-on every exit -- and the coverage check: every allocating entry point of the package has a case in tests/test_poisoned_memory_gpu.py or
-a reasoned exclusion."""
+on every exit, nested guards -- and the coverage check: every function of the package that allocates (found by reading every file of
+the package, not a fixed list) has a case in tests/test_poisoned_memory_gpu.py or a reasoned exclusion, and nothing allocates by a
+call the guard does not route."""
 import ast
 import os
 import sys
@@ -131,42 +132,99 @@ def test_patch_is_undone_on_exit_and_on_exception(fake_module):
     assert g.count == 0
 
 
+def test_a_nested_guard_joins_an_adopting_one(fake_module):
+    """What the sweep relies on for test bodies that poison their own allocations: under an adopting guard an inner poisoned() routes
+    to the outer guard and takes its pattern, and yields the inner block's own count, records and band check; without adopt= nothing
+    changes."""
+    with memguard.poisoned('B', modules=(), adopt=True) as outer:
+        for asked in 'AB':
+            with memguard.poisoned(asked, modules=('memguard_fake_mod',)) as inner:
+                t = fake_module.alloc((4,), dtype=torch.int32)
+                u = fake_module.alloc((2,), dtype=torch.float32)
+                assert inner.count == 2 and len(inner.records) == 2 and inner.pattern == 'B'
+            assert fake_module.torch is torch
+            assert bool((memguard.bits(t) == 0x00).all()) and bool((memguard.bits(u) == 0x7F).all())
+        assert outer.count == 4 and len(outer.records) == 4
+        with pytest.raises(AssertionError, match="alloc"):
+            with memguard.poisoned('A', modules=('memguard_fake_mod',)):
+                t = fake_module.alloc((4,), dtype=torch.int32)
+                _raw(t)[memguard.GUARD + 16] = 0
+        _raw(t)[memguard.GUARD + 16] = memguard.GUARD_BYTE
+    assert not memguard._ACTIVE and fake_module.torch is torch
+    with memguard.poisoned('B', modules=()) as outer:
+        with memguard.poisoned('A', modules=('memguard_fake_mod',)) as inner:
+            t = fake_module.alloc((4,), dtype=torch.int32)
+        assert inner is not outer and outer.count == 0 and inner.count == 1 and bool((memguard.bits(t) == 0xFF).all())
+    assert not memguard._ACTIVE and fake_module.torch is torch
+
+
 # ---------------------------------------------------------------- coverage of the allocating entry points
-ALLOC_FILES = ('upsnet_amd/ops.py', 'upsnet_amd/dataset/coco_eval.py', 'upsnet_amd/dataset/rle.py')
-ALLOC_CALLS = {'empty', '_ws', '_nhwc_out'}
-
-
 def allocating_functions():
-    """({'module.qualname'} of every function / method in ALLOC_FILES that calls torch.empty, _ws or _nhwc_out (the two helpers
-    excluded), {'module.qualname'} of every function / method there)."""
-    found, every = set(), set()
-    for rel in ALLOC_FILES:
-        mod = os.path.splitext(os.path.basename(rel))[0]
-        with open(os.path.join(ROOT, rel)) as f:
-            tree = ast.parse(f.read())
+    """({'module.qualname'} of every function / method of the package that allocates (memguard.scan_package), {'module.qualname'} of
+    every function / method of the package), with the module's last name component as `module`, as the case table spells it."""
+    every, found, _ = memguard.scan_package()
+    short = {m: m.rsplit('.', 1)[-1] for m in found}
+    assert len(set(short.values())) == len(short), "two allocating modules share a file name: %s" % sorted(short)
+    names = set(short.values())
+    flat_found = {short[m] + '.' + q for m, qs in found.items() for q in qs}
+    flat_every = {m.rsplit('.', 1)[-1] + '.' + q for m, qs in every.items() if m in short or m.rsplit('.', 1)[-1] not in names for q in qs}
+    return flat_found, flat_every
 
-        def visit(node, prefix):
-            for ch in ast.iter_child_nodes(node):
-                if isinstance(ch, ast.ClassDef):
-                    visit(ch, prefix + ch.name + '.')
-                elif isinstance(ch, ast.FunctionDef):
-                    every.add(mod + '.' + prefix + ch.name)
-                    for n in ast.walk(ch):
-                        if isinstance(n, ast.Call):
-                            fn = n.func
-                            name = fn.attr if (isinstance(fn, ast.Attribute) and isinstance(fn.value, ast.Name) and fn.value.id == 'torch') \
-                                else (fn.id if isinstance(fn, ast.Name) else None)
-                            if name in ALLOC_CALLS and ch.name not in ('_ws', '_nhwc_out'):
-                                found.add(mod + '.' + prefix + ch.name)
-                                break
-        visit(tree, '')
-    return found, every
+
+def test_the_guard_patches_every_allocating_module():
+    import test_poisoned_memory_gpu as sweep
+    _, found, _ = memguard.scan_package()
+    assert len(found) >= 22, sorted(found)
+    assert set(memguard.MODULES) | set(memguard.UNGUARDED) == set(found) and not set(memguard.MODULES) & set(memguard.UNGUARDED)
+    assert {'upsnet_amd.ops', 'upsnet_amd.tta', 'upsnet_amd.group_norm', 'upsnet_amd.models.hipconv', 'upsnet_amd.dataset.pan_track',
+            'upsnet_amd.dataset.mots'} <= set(memguard.MODULES)
+    for m in memguard.UNGUARDED:        # left unpatched only where nothing of the module is swept
+        names = {m.rsplit('.', 1)[-1] + '.' + q for q in found[m]}
+        assert names <= set(sweep.EXCLUDED), "%s is not guarded, but not all of it is excluded: %s" % (m, sorted(names - set(sweep.EXCLUDED)))
+    assert sorted(sweep._ENTRY_MODULES.values()) == sorted(memguard.MODULES)
+    assert all(full.rsplit('.', 1)[-1] == short for short, full in sweep._ENTRY_MODULES.items())
+    for m in memguard.MODULES:          # the patch replaces the module's global `torch`: a function-local import would escape it
+        assert __import__(m, fromlist=['_']).__dict__.get('torch') is torch, "%s has no module-level `import torch`" % m
+
+
+def test_no_uninitialised_allocation_escapes_the_proxy():
+    """torch.empty_like, torch.empty_strided and Tensor.new_empty are not routed through the guard: the package must not call them."""
+    calls = memguard.scan_package()[2]
+    assert not calls, "uninitialised allocations that the guard does not route (use torch.empty): %s" % "; ".join(calls)
+
+
+def test_the_scan_names_what_it_finds(tmp_path, monkeypatch):
+    pkg = tmp_path / 'upsnet_amd' / 'sub'
+    pkg.mkdir(parents=True)
+    (tmp_path / 'upsnet_amd' / '__init__.py').write_text("")
+    (pkg / 'mod.py').write_text(
+        "import torch\n"
+        "def _ws(n):\n    return torch.empty(n)\n"
+        "def pinned(n):\n    return torch.empty(n, pin_memory=True)\n"
+        "def plain(n):\n    return torch.zeros(n)\n"
+        "class K:\n"
+        "    def a(self, n):\n        return torch.empty((n,), device='cuda')\n"
+        "    def b(self, n):\n        return _ws(n)\n"
+        "    def c(self, x):\n        return torch.empty_like(x)\n"
+        "def d(x):\n    y = x.new_empty((3,))\n    return torch.empty_strided((2,), (1,))\n"
+        "def e(n, c, dev):\n    return ops._nhwc_out(n, c, 2, 2, dev)\n"
+        "def f(n, dev):\n    return impl._ws(n, dev)\n"
+        "def g(a):\n    return np.empty_like(a)\n"
+        "class L:\n"
+        "    def h(self):\n        return self._ws.numel()\n")
+    monkeypatch.setattr(memguard, 'ROOT', str(tmp_path))
+    every, found, unrouted = memguard.scan_package()
+    assert found == {'upsnet_amd.sub.mod': {'K.a', 'K.b', 'e', 'f'}}      # (a helper called as an attribute counts; numpy's empty_like and a tensor
+    # attribute named _ws do not)
+    assert every == {'upsnet_amd.sub.mod': {'_ws', 'pinned', 'plain', 'K.a', 'K.b', 'K.c', 'd', 'e', 'f', 'g', 'L.h'}}
+    rel = os.path.join('upsnet_amd', 'sub', 'mod.py')
+    assert unrouted == [rel + ':14: torch.empty_like', rel + ':16: x.new_empty', rel + ':17: torch.empty_strided']
 
 
 def test_every_allocating_entry_point_has_a_poisoned_case():
     import test_poisoned_memory_gpu as sweep
     found, every = allocating_functions()
-    assert len(found) > 60, sorted(found)
+    assert len(found) >= 102, sorted(found)
     covered = set()
     for c in sweep.CASES:
         covered.update(c.entries)

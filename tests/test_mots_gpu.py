@@ -298,6 +298,29 @@ def test_workspace_is_zero_again_and_a_second_sequence_scores_as_on_a_fresh_eval
     assert_equal_to_ref(both, ev.summary(), ref_run([a, b], ref.CATEGORIES))
 
 
+def test_a_used_evaluator_takes_sequences_of_other_sizes_like_a_fresh_one():
+    """One evaluator over 65 x 129, 37 x 53 and 65 x 129 again (other content; the workspace is replaced at each change of size, the
+    accumulators and the status are kept): after every sequence the integer counts it added are those of a fresh evaluator on that
+    sequence alone, bit for bit, and the totals -- the float64 soft sum included -- are the restatement's over all three."""
+    from upsnet_amd.dataset.mots import MOTSEvaluator
+    seqs = [ref.blob_sequence(41, 65, 129, 4, switch_at=2), ref.blob_sequence(42, 37, 53, 5, switch_at=1), ref.blob_sequence(43, 65, 129, 3, switch_at=1)]
+    ev = MOTSEvaluator(ref.CATEGORIES)
+    before = ev.raw()
+    for k, seq in enumerate(seqs):
+        feed(ev, [seq])
+        assert not bool(ev.workspace().any()) and tuple(ev._ws_shape) == seq[0][0].shape[:2]
+        after = ev.raw()
+        fresh = MOTSEvaluator(ref.CATEGORIES)
+        feed(fresh, [seq])
+        alone = fresh.raw()
+        for name in ref.COUNTS + ('mt', 'pt', 'ml'):
+            assert np.array_equal(after[name] - before[name], alone[name]), (k, name)
+        if k == 0:
+            assert np.array_equal(words(after['soft']), words(alone['soft']))
+        before = after
+    assert_equal_to_ref(ev.raw(), ev.summary(), ref_run(seqs, ref.CATEGORIES))
+
+
 def test_refusals_leave_the_state_untouched():
     from upsnet_amd.dataset.mots import MOTSEvaluator
     preds, gts, infos = ref.blob_sequence(31, 37, 53, 5, switch_at=2)

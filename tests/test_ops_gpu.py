@@ -567,6 +567,33 @@ def test_mask_roi_bitexact(U, N, C, agn, thresh, peaky):
     config.dataset.num_classes = 9
 
 
+@pytest.mark.parametrize("n,C,ms,K,layout", [(5, 9, 28, 7, 'nchw'), (5, 9, 28, 7, 'nhwc'), (1, 2, 28, 1, 'nchw'), (37, 81, 7, 300, 'nhwc'),
+                                            (6, 9, 13, 9, 'nchw'), (4, 3, 28, 5, 'bf16')])
+def test_mask_logit_gather_bitexact(U, n, C, ms, K, layout):
+    """pan_logit[k] = mask_logit[clamp(row[k]), clamp(cls[k])] against plain indexing of the same tensor (a copy of floats: exact).
+    Rows and classes below 0 and past the end are among the indices; NCHW and channels_last sources, a bf16 source (widened first),
+    planes of 49 and 169 elements (fewer than one workgroup's threads) and of 784 (more), more outputs than source rows, and K= given
+    explicitly below row's length."""
+    g = torch.Generator().manual_seed(n * 1000 + C * 10 + K)
+    src = torch.randn((n, C, ms, ms), generator=g).cuda()
+    if layout == 'nhwc':
+        src = src.contiguous(memory_format=torch.channels_last)
+    elif layout == 'bf16':
+        src = src.to(torch.bfloat16)
+    row = torch.randint(-2, n + 2, (K,), generator=g).to(torch.int32).cuda()
+    cls = torch.randint(-2, C + 2, (K,), generator=g).cuda()
+    if K >= 4:
+        row[:4] = torch.tensor([0, n - 1, -1, n], dtype=torch.int32)
+        cls[:4] = torch.tensor([C - 1, 0, C, -1])
+    want = src.float()[row.long().clamp(0, n - 1), cls.clamp(0, C - 1)].unsqueeze(1)
+    got = U.mask_logit_gather(src, row, cls)
+    assert got.shape == (K, 1, ms, ms) and got.dtype == torch.float32 and got.is_contiguous()
+    assert torch.equal(got.view(torch.int32), want.contiguous().view(torch.int32))
+    if K > 2:
+        head = U.mask_logit_gather(src, row, cls, K=K - 2)
+        assert head.shape == (K - 2, 1, ms, ms) and torch.equal(head.view(torch.int32), want[:K - 2].contiguous().view(torch.int32))
+
+
 # ------------------------------------------------------------------ panoptic head
 def _pan_inputs(rng, m, S, C, H, W, ms=28):
     fcn = rng.normal(0, 3, size=(1, S, H, W)).astype(np.float32)

@@ -292,6 +292,32 @@ def test_workspace_is_zero_again_and_a_second_sequence_scores_as_on_a_fresh_eval
     assert_equal_to_ref(both, ev.summary(), ref_run([a, b], ref.CATEGORIES, (1, 2, 3, 4)))
 
 
+def test_a_used_evaluator_takes_sequences_of_other_sizes_like_a_fresh_one():
+    """One evaluator over 65 x 129, 37 x 53 and 65 x 129 again (other content; the workspace is replaced at each change of size, the
+    accumulators, seq_out and the pinned buffers are kept): after every sequence the integer counts and the confusion cells it added
+    and its aq_sum are those of a fresh evaluator on that sequence alone, bit for bit, and the totals -- the float64 iou sums included --
+    are the restatement's over all three."""
+    from upsnet_amd.dataset.video_pq import VideoPanopticEvaluator
+    seqs = [ref.blob_sequence(41, 65, 129, 4, switch_at=2), ref.blob_sequence(42, 37, 53, 5, switch_at=1), ref.blob_sequence(43, 65, 129, 3, switch_at=1)]
+    ev = VideoPanopticEvaluator(ref.CATEGORIES)
+    before = ev.raw()
+    for k, seq in enumerate(seqs):
+        feed(ev, [seq])
+        assert not bool(ev.workspace().any()) and tuple(ev._ws_shape) == seq[0][0].shape[:2]
+        after = ev.raw()
+        fresh = VideoPanopticEvaluator(ref.CATEGORIES)
+        feed(fresh, [seq])
+        alone = fresh.raw()
+        for name in ('tp', 'fp', 'fn', 'conf'):
+            assert np.array_equal(after[name] - before[name], alone[name]), (k, name)
+        assert after['num_tracks'] - before['num_tracks'] == alone['num_tracks']
+        assert words(after['aq_sums'][-1:]).tolist() == words(alone['aq_sums']).tolist(), k
+        if k == 0:
+            assert np.array_equal(words(after['iou']), words(alone['iou']))
+        before = {n: (v.copy() if isinstance(v, np.ndarray) else v) for n, v in after.items()}
+    assert_equal_to_ref(ev.raw(), ev.summary(), ref_run(seqs, ref.CATEGORIES, (1, 2, 3, 4)))
+
+
 def test_refusals_leave_the_state_untouched():
     from upsnet_amd.dataset.video_pq import VideoPanopticEvaluator
     preds, gts, infos = ref.blob_sequence(31, 37, 53, 5, switch_at=2)
