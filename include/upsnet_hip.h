@@ -392,6 +392,19 @@ int upsnet_conv1x1_siblings_nhwc_f32(void *stream, const float *x, float *out_a,
 /* development knob: waves per workgroup of the 32-pixel form of upsnet_conv1x1_pair_nhwc_f32 (8: two per SIMD, default; 4). */
 void upsnet_conv1x1_pair32_tuning(int waves);
 
+/* Residency table (csrc/residency.h): at most `cap` workgroups of a kernel per CU, so that a kernel of another stream -- the other image
+ * in flight -- can live on the CU beside it. kernel: 0 conv1x1_frag (every mode), 1 conv1x1_pair, 2 conv1x1_pair32, 3 conv1x1_ksw,
+ * 4 conv_wino16<.,32,64>, 5 conv_wino16<.,32,32>, 6 dcn_fused_f32; -1: all of them. cap: 0 the plain launch (the state after loading),
+ * 1..8, or -1: the measured default of that kernel. The launcher enforces a cap by asking for more dynamic LDS than the kernel uses
+ * (160 KiB per CU, 1280-byte granules); kernel code and results do not change by a bit. A cap at or above what the kernel's own
+ * registers / LDS admit adds nothing. The model sets (-1, -1) while it captures the graphs of two or more images in flight and (-1, 0)
+ * afterwards; eager launches are never capped.
+ * upsnet_residency_pad_bytes: the dynamic LDS added for `cap` to a workgroup of static_lds + dynamic_lds bytes (the launchers' arithmetic).
+ * upsnet_residency_last_dynamic_lds: dynamic LDS of the most recent launch of a covered kernel (tests). */
+int upsnet_residency_tuning(int kernel, int cap);
+size_t upsnet_residency_pad_bytes(int cap, size_t static_lds, size_t dynamic_lds);
+int upsnet_residency_last_dynamic_lds(void);
+
 /* 3x3 / stride 1 / pad 1 convolution (+ bias, ReLU) of up to 5 NHWC maps sharing weights by Winograd F(4x4, 3x3) (csrc/conv_wino36.hip,
  * r11 / r12): 36 multiplies per 16 outputs, 0.5625 of the F(2x2) kernel's matrix work. Interpolation points {0, 3/4, -3/4, 3/2, -3/2, inf}:
  * within rtol = atol = 1e-4 of float64 on the model's layers, measured worst error 0.07-0.15 of that bound at the model's shapes (3-4x the

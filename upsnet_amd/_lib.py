@@ -47,6 +47,9 @@ _SIGNATURES = {
     "upsnet_conv1x1_tuning": (None, [c_int]),
     "upsnet_conv1x1_siblings_nhwc_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_int, c_int]),
     "upsnet_conv1x1_pair32_tuning": (None, [c_int]),
+    "upsnet_residency_tuning": (c_int, [c_int, c_int]),
+    "upsnet_residency_pad_bytes": (c_size_t, [c_int, c_size_t, c_size_t]),
+    "upsnet_residency_last_dynamic_lds": (c_int, []),
     "upsnet_conv1x1_splitk_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "upsnet_conv1x1_frag_nhwc_f32_splitk": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_int, P]),
     "upsnet_conv1x1_ksw_packed_weight_floats": (ctypes.c_size_t, [c_int, c_int]),

@@ -21,6 +21,7 @@
 #include "upsnet_hip.h"
 
 #include "conv_params.h"
+#include "residency.h"
 
 // corner descriptor of one (pixel, tap), kept small (4-5 registers) because the deformable instances are register-bound:
 // BYTE offset of the top-left corner (clamped, always loadable; advances by one channel slab per fetch), the bilinear
@@ -517,6 +518,24 @@ static int conv_launch(hipStream_t st, ConvParams &p)
 static int g_force_tile = 0;
 extern int g_wino_tm;
 extern "C" void upsnet_conv_tuning(int winograd_tiles, int force_tile) { g_wino_tm = winograd_tiles; g_force_tile = force_tile; }
+
+// Residency table (residency.h): workgroups per CU each multi-workgroup-per-CU kernel is held to by its launcher. All 0 = the launches
+// as they always were. g_res_default: the caps the model turns on while it captures the graphs of two or more images in flight --
+// chosen by end-to-end measurement, family by family (profiles/residency_sweep.txt); a family that did not win
+// stays at 0. Only the 32-pixel pair kernel won: one workgroup per CU, +1.0 % (its 256 workgroups at 1024x2048 are one per CU).
+int g_res_cap[RES_NKERNELS] = {0, 0, 0, 0, 0, 0, 0};
+static const int g_res_default[RES_NKERNELS] = {0, 0, 1, 0, 0, 0, 0};   // indexed by ResKernel
+extern "C" int upsnet_residency_tuning(int kernel, int cap)
+{
+    UPS_REQUIRE(kernel >= -1 && kernel < RES_NKERNELS, "residency_tuning: kernel must be -1 (all) or 0..%d", RES_NKERNELS - 1);
+    UPS_REQUIRE(cap >= -1 && cap <= RES_MAX_CAP, "residency_tuning: cap must be -1 (the measured default), 0 (off) or 1..%d", RES_MAX_CAP);
+    for (int k = 0; k < RES_NKERNELS; ++k)
+        if (kernel < 0 || kernel == k) g_res_cap[k] = cap < 0 ? g_res_default[k] : cap;
+    return 0;
+}
+int g_res_last_dynamic = 0;
+extern "C" int upsnet_residency_last_dynamic_lds(void) { return g_res_last_dynamic; }
+extern "C" size_t upsnet_residency_pad_bytes(int cap, size_t static_lds, size_t dynamic_lds) { return res_pad_bytes(cap, static_lds, dynamic_lds); }
 
 template <int DEFORM>
 static int conv_dispatch(hipStream_t st, ConvParams &p)

@@ -19,6 +19,7 @@
 // completion so that the stores of one overlap the K walk of the others: 0-4 %, within noise.) Epilogue fused: + bias (folded frozen-BN shift), + residual (optionally read through the FPN's nearest x2
 // upsampling), ReLU, one NHWC store. Fixed accumulation order (bit-repeatable).
 #include "conv_params.h"
+#include "residency.h"
 #include "upsnet_hip.h"
 
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
@@ -338,7 +339,12 @@ static int conv1x1_frag_launch(hipStream_t st, ConvParams &p, int mode)
     if (!bn) bn = (Cout > 64 && (long)p.m_tiles * ((Cout + 127) / 128) >= 512) ? 128 : 64;
     if (Cout <= 64) bn = 64;
     p.n_tiles = (Cout + bn - 1) / bn;
-    const size_t smem = (size_t)2 * 8 * C1_BM * 16;
+    // (no static LDS; beyond the kernel's own 16 KiB only the padding of a residency cap, residency.h -- 4 workgroups per CU by registers)
+    const size_t smem = res_dynamic_lds(RES_CONV1X1_FRAG, 0, (size_t)2 * 8 * C1_BM * 16);
+    static std::atomic<unsigned long long> attr_dev{0};
+#define C1_ATTR(NW, MODE) UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_frag_f32_kernel<NW, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, res_max_dynamic(0)))
+    UPS_ONCE_PER_DEVICE(attr_dev, C1_ATTR(4, 0); C1_ATTR(4, 1); C1_ATTR(4, 2); C1_ATTR(4, 3); C1_ATTR(2, 0); C1_ATTR(2, 1); C1_ATTR(2, 2); C1_ATTR(2, 3));
+#undef C1_ATTR
     p.m_total = (long)p.m_tiles * C1_BM;
     const int grid = 8 * ((p.m_tiles + 7) / 8) * p.n_tiles * (mode == 3 ? p.ksplit : 1);
 #define C1_LAUNCH(NW, MODE) hipLaunchKernelGGL((conv1x1_frag_f32_kernel<NW, MODE>), dim3(grid), dim3(256), smem, st, p)

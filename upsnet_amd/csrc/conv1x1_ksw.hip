@@ -24,6 +24,7 @@
 // fetched from L2 once per 16 RB pixels (32 x 32: 32 B / clk / CU at the full MFMA rate, against 24 for conv1x1_frag), so the 64-pixel
 // kernel keeps the maps it tiles evenly; models/hipconv.py picks per layer (shape only).
 #include "conv_params.h"
+#include "residency.h"
 #include "upsnet_hip.h"
 
 typedef float kfloatx4 __attribute__((ext_vector_type(4)));
@@ -265,8 +266,16 @@ extern "C" int upsnet_conv1x1_ksw_nhwc_f32(void *stream, const float *x, const f
     UPS_REQUIRE((long)(p.n_tiles * (split_n ? 4 : 1) + 1) * cb * (Cin / 16) * 1024 < (1L << 31), "conv1x1_ksw_nhwc_f32: packed weight exceeds 2 GiB");
     const int grid = 8 * ((p.m_tiles + 7) / 8) * p.n_tiles;
     hipStream_t st = (hipStream_t)stream;
-#define KSW_GO(RB, CB, RING, WPE) { if (split_n) hipLaunchKernelGGL((conv1x1_ksw_f32_kernel<RB, CB, RING, WPE, false>), dim3(grid), dim3(256), 0, st, p); \
-                                    else hipLaunchKernelGGL((conv1x1_ksw_f32_kernel<RB, CB, RING, WPE, true>), dim3(grid), dim3(256), 0, st, p); }
+    // The kernel's LDS is static (`red`: 4 waves x 16 PRB rows x (16 CB + 4) floats) and it declares no dynamic LDS: what the launch asks for
+    // is only the padding of a residency cap (residency.h), 0 without one.
+#define KSW_GO(RB, CB, RING, WPE) { const size_t red = (size_t)4 * 16 * (RB > 2 ? 2 : RB) * (16 * CB + 4) * sizeof(float);                                       \
+                                    const size_t pad = res_dynamic_lds(RES_CONV1X1_KSW, red, 0);                                                                  \
+                                    static std::atomic<unsigned long long> attr_dev{0};                                                                          \
+                                    UPS_ONCE_PER_DEVICE(attr_dev,                                                                                                \
+                                        UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_ksw_f32_kernel<RB, CB, RING, WPE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, res_max_dynamic(red))); \
+                                        UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_ksw_f32_kernel<RB, CB, RING, WPE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, res_max_dynamic(red)))); \
+                                    if (split_n) hipLaunchKernelGGL((conv1x1_ksw_f32_kernel<RB, CB, RING, WPE, false>), dim3(grid), dim3(256), pad, st, p); \
+                                    else hipLaunchKernelGGL((conv1x1_ksw_f32_kernel<RB, CB, RING, WPE, true>), dim3(grid), dim3(256), pad, st, p); }
     // RING = 2 everywhere (measured r13, tools/bench_conv1x1_ksw.py, RING 1 / 2 / 3 / 4 / 6 at the occupancy the registers allow: a deeper ring
     // lengthens the prologue and rounds every wave's walk up to more wasted steps; occupancy hides the latency instead)
     if (rb == 1) KSW_GO(1, 4, 2, 6)

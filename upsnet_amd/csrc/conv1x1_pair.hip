@@ -17,6 +17,7 @@
 //   * accumulation order of both GEMMs = that of conv1x1_frag_f32_kernel (K ascending through one accumulator chain per output
 //     element), so out1 and out2 are bit-identical to the two separate launches.
 #include "conv_params.h"
+#include "residency.h"
 #include "upsnet_hip.h"
 
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
@@ -399,24 +400,29 @@ extern "C" int upsnet_conv1x1_pair_nhwc_f32(void *stream, const float *x, const 
     p.M = pixels; p.C0 = C0; p.C1 = C1; p.C2 = C2;
     if (res4) {   // r10: 32-pixel tiles (csrc comment above conv1x1_pair32_f32_kernel)
         if (g_pair32_waves == 8 && C1 % 256 == 0) {      // two waves per SIMD; 66 KiB of LDS (x tile + a 256-channel chunk)
-            const size_t smem8 = (size_t)(8 * (C0 / 32) + 64) * CP32_PITCH * 16;
+            // (no static LDS in either pair kernel: the attribute covers the padding of a residency cap too, residency.h)
+            const size_t smem8 = res_dynamic_lds(RES_CONV1X1_PAIR32, 0, (size_t)(8 * (C0 / 32) + 64) * CP32_PITCH * 16);
             static std::atomic<unsigned long long> attr_dev8{0};
-            UPS_ONCE_PER_DEVICE(attr_dev8, UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_pair32_f32_kernel<8, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem8)));
+            UPS_ONCE_PER_DEVICE(attr_dev8, UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_pair32_f32_kernel<8, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, res_max_dynamic(0))));
             hipLaunchKernelGGL((conv1x1_pair32_f32_kernel<8, 8>), dim3((unsigned)((pixels + 31) / 32)), dim3(512), smem8, (hipStream_t)stream, p);
         } else {
-            const size_t smem32 = (size_t)(8 * (C0 / 32) + 32) * CP32_PITCH * 16;
+            const size_t smem32 = res_dynamic_lds(RES_CONV1X1_PAIR32, 0, (size_t)(8 * (C0 / 32) + 32) * CP32_PITCH * 16);
+            static std::atomic<unsigned long long> attr_dev4{0};
+            UPS_ONCE_PER_DEVICE(attr_dev4, UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_pair32_f32_kernel<8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, res_max_dynamic(0))));
             hipLaunchKernelGGL((conv1x1_pair32_f32_kernel<8, 4>), dim3((unsigned)((pixels + 31) / 32)), dim3(256), smem32, (hipStream_t)stream, p);
         }
         UPS_CHECK_LAUNCH("conv1x1_pair32_f32_kernel");
         return 0;
     }
     const int grid = (int)((pixels + 63) / 64);
-    const size_t smem = (size_t)(8 * (C0 / 32) + 32) * CP_PITCH * 16;
-    if (res3) {   // r10: the res3 stage (128 -> 512 -> 128): x tile 32 KiB + chunk 33 KiB = 65 KiB of LDS, two workgroups per CU
-        static std::atomic<unsigned long long> attr_dev{0};
-        UPS_ONCE_PER_DEVICE(attr_dev, UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_pair_f32_kernel<4, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)));
+    const size_t smem = res_dynamic_lds(RES_CONV1X1_PAIR, 0, (size_t)(8 * (C0 / 32) + 32) * CP_PITCH * 16);
+    static std::atomic<unsigned long long> attr_dev{0};
+    UPS_ONCE_PER_DEVICE(attr_dev,
+        UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_pair_f32_kernel<4, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, res_max_dynamic(0)));
+        UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1x1_pair_f32_kernel<2, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, res_max_dynamic(0))));
+    if (res3)   // r10: the res3 stage (128 -> 512 -> 128): x tile 32 KiB + chunk 33 KiB = 65 KiB of LDS, two workgroups per CU
         hipLaunchKernelGGL((conv1x1_pair_f32_kernel<4, 128>), dim3(grid), dim3(256), smem, (hipStream_t)stream, p);
-    } else
+    else
         hipLaunchKernelGGL((conv1x1_pair_f32_kernel<2, 64>), dim3(grid), dim3(256), smem, (hipStream_t)stream, p);
     UPS_CHECK_LAUNCH("conv1x1_pair_f32_kernel");
     return 0;

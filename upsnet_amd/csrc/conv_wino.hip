@@ -25,6 +25,7 @@
 // LDS: 2 buffers x 64 KiB (double-buffered V), one workgroup per CU; the 32-tile forms: 2 x 32 KiB, two workgroups per CU.
 #include <cstdlib>
 #include "conv_params.h"
+#include "residency.h"
 #include "upsnet_hip.h"
 
 #define WG_STEPS 32          // (xi, h) steps per slab: 16 positions x 2 k-halves of 8 channels; 16 per wave
@@ -362,11 +363,14 @@ static int conv_wino16_launch_tm(hipStream_t st, ConvParams &p)
     for (int i = 0; i < p.nseg; ++i) { p.seg[i].tile_start = tiles; tiles += (int)((p.seg[i].M + TM - 1) / TM); }
     p.m_tiles = tiles;
     p.n_tiles = p.ldw / TN;
-    const size_t smem = 2 * 16 * 4 * TM * 16;
+    // (no static LDS. The 64-tile form owns a CU by construction; the 32-tile forms, two per CU, take a residency cap: residency.h)
+    const size_t own = 2 * 16 * 4 * TM * 16;
+    const size_t smem = TM == 32 ? res_dynamic_lds(TN == 64 ? RES_WINO16_32X64 : RES_WINO16_32X32, 0, own) : own;
+    const int smem_max = TM == 32 ? res_max_dynamic(0) : (int)own;
     static std::atomic<unsigned long long> attr_dev{0};
     UPS_ONCE_PER_DEVICE(attr_dev,
-        UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino16_f32_kernel<false, TM, TN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino16_f32_kernel<true, TM, TN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)));
+        UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino16_f32_kernel<false, TM, TN>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_max));
+        UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino16_f32_kernel<true, TM, TN>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_max)));
     const int grid = 8 * ((p.m_tiles + 7) / 8) * p.n_tiles;
     if (p.ksplit > 1) hipLaunchKernelGGL((conv_wino16_f32_kernel<true, TM, TN>), dim3(grid * p.ksplit), dim3(8 * TM), smem, st, p);
     else hipLaunchKernelGGL((conv_wino16_f32_kernel<false, TM, TN>), dim3(grid), dim3(8 * TM), smem, st, p);

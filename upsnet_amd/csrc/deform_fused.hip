@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "conv_params.h"
+#include "residency.h"
 #include "upsnet_hip.h"
 
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
@@ -437,7 +438,13 @@ static int dcn_fused_launch(void *stream, int nlev, const float *const x[], cons
         p.partial = (float *)workspace;
         p.m_total = p.seg[0].M;
     }
-    const size_t smem = (size_t)2 * DF_ABUF * 16 + (size_t)kh * kw * DF_BM * (16 + 16 + 4);
+    // (no static LDS; the padding of a residency cap on top of the kernel's own buffers: residency.h)
+    const size_t smem = res_dynamic_lds(RES_DCN_FUSED, 0, (size_t)2 * DF_ABUF * 16 + (size_t)kh * kw * DF_BM * (16 + 16 + 4));
+    static std::atomic<unsigned long long> attr_dev{0};
+#define DF_ATTR(MASK, SETS, WPE) UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dcn_fused_f32_kernel<MASK, SETS, WPE>), hipFuncAttributeMaxDynamicSharedMemorySize, res_max_dynamic(0)))
+    UPS_ONCE_PER_DEVICE(attr_dev, DF_ATTR(true, 1, 3); DF_ATTR(false, 1, 3); DF_ATTR(true, 2, 2); DF_ATTR(false, 2, 2); DF_ATTR(true, 3, 4); DF_ATTR(false, 3, 4);
+                        DF_ATTR(true, 3, 3); DF_ATTR(false, 3, 3));
+#undef DF_ATTR
     const int grid = 8 * ((p.m_tiles + 7) / 8) * p.n_tiles * p.ksplit;
     // auto = one corner set, early schedule, at 3 waves per SIMD everywhere. (Two sets -- deeper gather lookahead -- for grids below
     // UPSNET_DCN_SMALL_GRID workgroups was measured on the R101-DCN backbone: 106.6 vs 107.7 img/s, so the default threshold is 0.)

@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
+from .._lib import check, lib
 from ..config.config import config
 from ..operators.modules.mask_removal import MaskRemoval
 from ..operators.modules.mask_roi import MaskROI, check_count
@@ -329,7 +330,12 @@ class resnet_upsnet(resnet_rcnn):
                 sk = _SLOT_STREAMS[sk_key]
             gc_was_on = gc.isenabled()
             gc.disable()   # a collection in the middle of the capture could release device objects (illegal while capturing)
+            # two or more images in flight: the launches recorded into the graph carry the measured residency caps (csrc/residency.h),
+            # so that kernels of the two images can share a CU; eager forwards and the one-slot graph keep the plain launches
+            capped = self.graph_slots >= 2
             try:
+                if capped:
+                    check(lib().upsnet_residency_tuning(-1, -1), 'residency_tuning')
                 # (thread_local: other threads of the process -- e.g. the RCCL watchdog of torch.distributed -- may call the runtime
                 # while this thread captures)
                 with torch.cuda.graph(g, stream=sk, capture_error_mode='thread_local'):
@@ -340,6 +346,8 @@ class resnet_upsnet(resnet_rcnn):
                 self.use_graph = False
                 return None
             finally:
+                if capped:
+                    lib().upsnet_residency_tuning(-1, 0)
                 if gc_was_on:
                     gc.enable()
             host = torch.empty((4,), dtype=out['tail']['counters'].dtype).pin_memory() if out.get('tail') is not None else None
