@@ -1201,6 +1201,29 @@ int upsnet_pan_track_step(void *stream, const unsigned char *pan_2ch, int height
 int upsnet_pan_stable_colors(void *stream, const unsigned char *pred_2ch, int height, int width, const int *cat_table, int mode,
                              unsigned char *rgb);
 
+/* ============================== Connected components of a panoptic map ============================== */
+
+/* Labels the connected components of a 2-channel map (pan_2ch uint8 [H,W,3], channel 0 category with 255 = VOID, channel 1 instance)
+ * and turns small fragments into VOID. The reference has no such step; the rule is this project's own (csrc/pan_components.hip,
+ * restated in tests/pan_components_ref.py):
+ *   - a pixel's key is c << 8 | i (bytes 0 and 1); byte 2 is never read and always preserved;
+ *   - a pixel with c == 255 belongs to no component and is never changed;
+ *   - a component is a maximal set of pixels of equal key connected under `connectivity` (4: edge neighbours, 8: corners too);
+ *   - its label is the smallest linear index y * W + x among its pixels (VOID: -1), its area its pixel count;
+ *   - the main component of a key is the one of largest area, ties to the smaller label;
+ *   - a component is removed iff area < min_area and, with keep_largest != 0, it is not the main component of its key (so with
+ *     keep_largest a key never vanishes entirely; without it small segments go too); min_area == 0 removes nothing;
+ *   - every pixel of a removed component becomes (255, 0, byte 2), the VOID of upsnet_unified_pan_result; every other pixel keeps its
+ *     bytes.
+ * out_2ch may be pan_2ch itself. labels (may be NULL): int32 [H,W], 16-byte aligned, the labels of the INPUT map (a removed component
+ * keeps its label there). stats: int32 [4] = distinct keys, components, components removed, pixels removed (all of the input map).
+ * workspace: upsnet_pan_components_workspace_bytes(H, W) bytes, 16-byte aligned; its contents on entry are ARBITRARY and nothing
+ * depends on an earlier call. Five launches, nothing is synchronised or allocated. Refused before any launch: a null pointer, H * W
+ * outside 1..2^24 (the workspace size is then 0), connectivity other than 4 or 8, min_area < 0, a misaligned buffer. */
+size_t upsnet_pan_components_workspace_bytes(int height, int width);
+int upsnet_pan_components(void *stream, const unsigned char *pan_2ch, int height, int width, int connectivity, int min_area,
+                          int keep_largest, void *workspace, unsigned char *out_2ch, int *labels, int *stats);
+
 /* ============================== Video metrics of tracked sequences: VPQ and STQ ============================== */
 
 /* Video Panoptic Quality (Kim et al., Video Panoptic Segmentation, CVPR 2020) and Segmentation and Tracking Quality (Weber et al.,

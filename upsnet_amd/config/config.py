@@ -101,6 +101,12 @@ config.test.soft_nms = False
 config.test.soft_nms_method = 'linear'
 config.test.soft_nms_sigma = 0.5
 config.test.soft_nms_score_thresh = 0.0001
+# disconnected fragments of the panoptic predictions (csrc/pan_components.hip; the reference has none): with
+# pan_min_component > 0 every connected component (4- or 8-connectivity) of a (category, instance) pair with fewer pixels than that
+# becomes VOID before the maps are scored, written, drawn or tracked; with keep_largest the largest component of a pair always stays.
+config.test.pan_min_component = 0
+config.test.pan_component_connectivity = 8
+config.test.pan_component_keep_largest = True
 
 
 def _merge(dst, src):

@@ -6,6 +6,38 @@ import argparse
 from .config import config, update_config
 
 
+def add_pan_component_arguments(parser, before):
+    """--pan_min_component / --pan_component_connectivity of the evaluation and the sequence command lines."""
+    parser.add_argument('--pan_min_component', type=int, default=None, metavar='N',
+                        help='sets config.test.pan_min_component: every connected component of a (category, instance) pair with fewer '
+                        'than N pixels becomes VOID in the panoptic predictions before they are %s (on the device); the largest '
+                        'component of a pair always stays (test.pan_component_keep_largest); 0 = off' % before)
+    parser.add_argument('--pan_component_connectivity', type=int, default=None, metavar='{4,8}',
+                        help='with --pan_min_component: sets config.test.pan_component_connectivity, 4 or 8 (default 8)')
+
+
+def apply_pan_component_arguments(args, fail):
+    """The two options into config.test, once the yaml is merged; then the resulting values are checked, whichever of the two set them.
+    fail(message) ends the run (parser.error, or a SystemExit): every message names the option or the yaml key."""
+    if args.pan_min_component is not None:
+        if args.pan_min_component < 0:
+            fail('--pan_min_component must be an integer >= 0, got %d' % args.pan_min_component)
+        config.test.pan_min_component = int(args.pan_min_component)
+    if args.pan_component_connectivity is not None:
+        if not config.test.get('pan_min_component', 0):
+            fail('--pan_component_connectivity is a parameter of --pan_min_component, which is missing')
+        if args.pan_component_connectivity not in (4, 8):
+            fail('--pan_component_connectivity must be 4 or 8, got %d' % args.pan_component_connectivity)
+        config.test.pan_component_connectivity = int(args.pan_component_connectivity)
+    n, c = config.test.get('pan_min_component', 0), config.test.get('pan_component_connectivity', 8)
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        fail('test.pan_min_component must be an integer >= 0, got %r' % (n,))
+    if isinstance(c, bool) or c not in (4, 8):
+        fail('test.pan_component_connectivity must be 4 or 8, got %r' % (c,))
+    if not isinstance(config.test.get('pan_component_keep_largest', True), bool):
+        fail('test.pan_component_keep_largest must be true or false, got %r' % (config.test.pan_component_keep_largest,))
+
+
 def parse_args(description='', argv=None):
     parser = argparse.ArgumentParser(description=description)
     parser.add_argument('--cfg', help='experiment configure file name', required=False, type=str, default='')
@@ -94,6 +126,7 @@ def parse_args(description='', argv=None):
                         help='with --soft_nms: sets config.test.soft_nms_method, linear (default) or gaussian')
     parser.add_argument('--soft_nms_sigma', type=float, default=None, metavar='S',
                         help='with --soft_nms: sets config.test.soft_nms_sigma, the width of the gaussian decay (default 0.5)')
+    add_pan_component_arguments(parser, 'scored, written or drawn')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)
@@ -116,6 +149,7 @@ def parse_args(description='', argv=None):
             if not config.test.get('soft_nms', False):
                 parser.error('--%s is a parameter of --soft_nms, which is missing' % name)
             config.test[name] = getattr(args, name)
+    apply_pan_component_arguments(args, parser.error)
     if rest:    # (the reference re-parses strictly, parse_args.py:32; an option neither parser knows is reported, not swallowed)
         parser.error('unrecognized arguments: %s' % ' '.join(rest))
     return args

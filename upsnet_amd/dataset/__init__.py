@@ -4,3 +4,4 @@ from .boundary import boundary_dilation, mask_to_boundary
 from .pan_track import PanopticTracker, track_sequence
 from .video_pq import VideoPanopticEvaluator
 from .mots import MOTSEvaluator
+from .pan_components import clean_panoptic

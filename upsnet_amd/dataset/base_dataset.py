@@ -127,6 +127,22 @@ class BaseDataset(object):
         return ops.combined_pan_result(segs, boxes, masks, id_last_stuff, score_threshold=score_threshold,
                                        fraction_threshold=fraction_threshold, stuff_area_limit=stuff_area_limit)
 
+    def clean_pan_result(self, pans, min_area=None, connectivity=None, keep_largest=None, what='panoptic'):
+        """get_unified_pan_result's / get_combined_pan_result's maps with the disconnected fragments of fewer than min_area pixels
+        turned into VOID (dataset/pan_components.clean_panoptic); the parameters default to config.test.pan_min_component,
+        pan_component_connectivity and pan_component_keep_largest. Logs the components and pixels removed over all maps, once."""
+        from .pan_components import clean_panoptic
+        min_area = config.test.pan_min_component if min_area is None else min_area
+        connectivity = config.test.pan_component_connectivity if connectivity is None else connectivity
+        keep_largest = config.test.pan_component_keep_largest if keep_largest is None else keep_largest
+        cleaned, total = clean_panoptic(pans, min_area, connectivity, keep_largest, return_stats=True)
+        if total is not None:
+            _, comps, gone, pixels = total.cpu().tolist()
+            logger.info('%s: %d of %d connected components (%d pixels) of fewer than %d pixels removed from %d maps (%d-connectivity%s)',
+                        what, gone, comps, pixels, min_area, len(cleaned), connectivity,
+                        ', the largest of every segment kept' if keep_largest else '')
+        return cleaned
+
     def load_panoptic_gt(self):
         """(images, annotations, categories) of self.panoptic_json_file; images yields the uint8 [H,W,3] GT PNGs of
         self.panoptic_gt_folder in the JSON's 'images' order (as the reference loads them), lazily."""

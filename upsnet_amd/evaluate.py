@@ -8,6 +8,7 @@
                                   [--write_instances [--instances_1bit]] [--eval_boundary [--boundary_dilation_ratio R]]
                                   [--eval_boundary_pq [--boundary_pq_dilation_ratio R]] [--aug_scales S [S ...]] [--aug_flip]
                                   [--bbox_vote [--bbox_vote_thresh T]] [--soft_nms [--soft_nms_method M] [--soft_nms_sigma S]]
+                                  [--pan_min_component N [--pan_component_connectivity {4,8}]]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>] [--eval_boundary_pq ...]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
     python -m upsnet_amd.evaluate --cfg <yaml> --score_instances <folder>
@@ -63,6 +64,10 @@ candidate that overlaps a kept one stays with a decayed score and is dropped onl
 detection scores written are the decayed ones; the panoptic selection stays hard NMS. It lives on the same eager path (on its own: the
 base augmentation alone), comes before the voting, and the results pickle also carries 'soft_nms', [method, sigma, floor];
 `--eval_proposals` is refused with it too.
+`--pan_min_component N [--pan_component_connectivity {4,8}]` (or `test.pan_min_component` / `test.pan_component_connectivity` /
+`test.pan_component_keep_largest` in the yaml) removes disconnected fragments from every panoptic result before it is scored, written
+or drawn (csrc/pan_components.hip): a connected component of a (category, instance) pair with fewer than N pixels becomes
+VOID, the largest component of the pair excepted; the results pickle is not changed, so `--eval_only` may try another N.
 One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
@@ -219,17 +224,21 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
 
 def panoptic_predictions(dataset, results, combined, order=None):
     """The 2-channel maps of the results, unified (the panoptic head's) or combined (the heuristic merge), one per entry of `order`
-    (positions in the image list; default: the image list's own order)."""
+    (positions in the image list; default: the image list's own order). With config.test.pan_min_component > 0 the maps pass through
+    dataset.clean_pan_result first (disconnected fragments become VOID): scoring, writing and drawing see the same maps."""
     order = list(range(len(dataset))) if order is None else order
     if not combined:
-        return dataset.get_unified_pan_result([results['all_ssegs'][k] for k in order], [results['all_panos'][k] for k in order],
+        pans = dataset.get_unified_pan_result([results['all_ssegs'][k] for k in order], [results['all_panos'][k] for k in order],
                                               [results['all_pano_cls_inds'][k] for k in order],
                                               stuff_area_limit=config.test.panoptic_stuff_area_limit)
-
-    def ordered(per_class):
-        return [[v[k] for k in order] if c else v for c, v in enumerate(per_class)]
-    return dataset.get_combined_pan_result([results['all_ssegs'][k] for k in order], ordered(results['all_boxes']),
-                                           ordered(results['all_masks']), stuff_area_limit=config.test.panoptic_stuff_area_limit)
+    else:
+        def ordered(per_class):
+            return [[v[k] for k in order] if c else v for c, v in enumerate(per_class)]
+        pans = dataset.get_combined_pan_result([results['all_ssegs'][k] for k in order], ordered(results['all_boxes']),
+                                               ordered(results['all_masks']), stuff_area_limit=config.test.panoptic_stuff_area_limit)
+    if config.test.get('pan_min_component', 0) > 0:
+        pans = dataset.clean_pan_result(pans, what='combined pano result' if combined else 'unified pano result')
+    return pans
 
 
 def ssegs_folder(results_dir, label_ids):

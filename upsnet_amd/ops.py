@@ -1971,6 +1971,62 @@ def pan_stable_colors(pred_2ch, cat_table, mode, out):
     return out
 
 
+def pan_components_workspace(height, width, device):
+    """Workspace of pan_components for maps of height x width pixels. The kernels initialise what they read: its contents never
+    matter, and one workspace serves every map of that size (or a smaller one)."""
+    nbytes = int(lib().upsnet_pan_components_workspace_bytes(int(height), int(width)))
+    if nbytes == 0:
+        raise ValueError("pan_components: a map of %d x %d pixels has no workspace: H * W must lie in 1..2^24" % (height, width))
+    return torch.zeros((nbytes,), dtype=torch.uint8, device=device)
+
+
+def pan_components(pan_2ch, min_area=0, connectivity=8, keep_largest=True, *, want_labels=False, workspace=None, out=None, labels=None):
+    """Connected components of a 2-channel map and the removal of small fragments (include/upsnet_hip.h states the rule;
+    csrc/pan_components.hip). pan_2ch: contiguous uint8 [H,W,3] device tensor. A component (pixels of one (category,
+    instance) key connected under `connectivity`, 4 or 8; category 255 is VOID and in none) of fewer than min_area pixels becomes VOID
+    (255, 0, byte 2 kept) unless keep_largest and it is the largest of its key (ties: the one that starts first). min_area = 0 only
+    labels.
+
+    Returns (out, stats, labels): out uint8 [H,W,3]; stats int32 [4] = distinct keys, components, components removed, pixels removed;
+    labels int32 [H,W] with want_labels (or labels=), else None: the smallest linear index y * W + x of the pixel's component in the
+    INPUT map, -1 for VOID. All device tensors; five launches, nothing waits for the host. workspace= (pan_components_workspace; any
+    contents), out= (may be pan_2ch itself) and labels= are taken instead of being allocated.
+    ValueError before any launch: a wrong dtype, shape or size, connectivity other than 4 or 8, a negative or non-integer min_area."""
+    if pan_2ch.dtype != torch.uint8 or pan_2ch.dim() != 3 or pan_2ch.shape[2] != 3 or not pan_2ch.is_contiguous():
+        raise ValueError("pan_components: pan_2ch must be contiguous uint8 [H,W,3], got %s %s" % (tuple(pan_2ch.shape), pan_2ch.dtype))
+    if connectivity not in (4, 8):
+        raise ValueError("pan_components: connectivity must be 4 or 8, got %r" % (connectivity,))
+    if isinstance(min_area, bool) or int(min_area) != min_area or min_area < 0 or min_area > 0x7fffffff:
+        raise ValueError("pan_components: min_area must be an integer >= 0, got %r" % (min_area,))
+    H, W = int(pan_2ch.shape[0]), int(pan_2ch.shape[1])
+    if H * W == 0 or H * W > (1 << 24):
+        raise ValueError("pan_components: a map of %d x %d pixels: H * W must lie in 1..2^24" % (H, W))
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous()):
+        raise ValueError("pan_components: out must be contiguous uint8 [%d,%d,3], got %s %s" % (H, W, tuple(out.shape), out.dtype))
+    if labels is not None and (labels.dtype != torch.int32 or tuple(labels.shape) != (H, W) or not labels.is_contiguous()
+                               or labels.data_ptr() % 16):
+        raise ValueError("pan_components: labels must be a contiguous, 16-byte aligned int32 [%d,%d] tensor, got %s %s"
+                         % (H, W, tuple(labels.shape), labels.dtype))
+    require_cuda(pan_2ch, workspace, out, labels)      # (after the checks that need no device)
+    need = int(lib().upsnet_pan_components_workspace_bytes(H, W))
+    if workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need
+                                  or workspace.data_ptr() % 16):
+        raise ValueError("pan_components: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least %d bytes for a map "
+                         "of %d x %d" % (need, H, W))
+    dev = pan_2ch.device
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = pan_components_workspace(H, W, dev)
+        if out is None:
+            out = pan_2ch.clone()
+        if labels is None and want_labels:
+            labels = torch.zeros((H, W), dtype=torch.int32, device=dev)
+        stats = torch.zeros((4,), dtype=torch.int32, device=dev)
+        check(lib().upsnet_pan_components(stream(), ptr(pan_2ch), H, W, int(connectivity), int(min_area), int(bool(keep_largest)),
+                                          ptr(workspace), ptr(out), ptr(labels), ptr(stats)), "pan_components")
+    return out, stats, labels
+
+
 def video_eval_workspace(max_gt, height, width, max_window, device):
     """Zeroed workspace of video_eval_frame / video_eval_end for sequences of height x width frames, at most max_gt (0..4096) rows in the
     sequence table and windows of at most max_window (1..8) frames; video_eval_end leaves all of it zero again."""

@@ -3,6 +3,7 @@
     python -m upsnet_amd.sequence --cfg <yaml> (--weight_path <pth> | --synthetic_weights) --frames <folder> --out <dir>
                                   --panoptic_categories <json> [--track_iou T] [--track_max_age N] [--combined]
                                   [--vis_panoptic {flat,overlay,both}] [--in-flight N] [--video_gt <folder> [--vpq_windows N [N ...]]]
+                                  [--pan_min_component N [--pan_component_connectivity {4,8}]]
     python -m upsnet_amd.sequence --cfg <yaml> --track_only <folder of pan_2ch PNGs> --out <dir> --panoptic_categories <json> [...]
 
 No annotation JSON is needed. The image files directly in --frames, sorted by name, are one sequence (named after the folder); every
@@ -21,6 +22,9 @@ serials (track_id) go on counting, so a track_id names one object of one sequenc
   vis/, vis_flat/       with --vis_panoptic: the pictures, every track in one colour throughout
 --track_only tracks an already written prediction (for instance results/pans_unified/pan_2ch of an evaluation run) without building
 the model; the photographs are not there, so of the pictures only 'flat' can be drawn. One rank only.
+--pan_min_component N (or test.pan_min_component in the yaml) turns the connected components of fewer than N pixels into VOID in every
+map before the tracker sees it, the largest of every segment excepted (dataset/pan_components.py), so that a
+stray fragment does not overlap another track; --track_only inputs are cleaned the same way.
 --video_gt <folder> scores every sequence, once it is tracked and written, against <folder>/<sequence>/gt.json and
 <folder>/<sequence>/pan/<frame>.png (VPQ and STQ on the device; upsnet_amd/video_eval.py says how the frames
 pair and re-scores written runs); --vpq_windows sets the window lengths (default 1 2 3 4). Then <out>/video_scores.json is written and
@@ -93,6 +97,9 @@ class FrameSequence(object):
     def get_combined_pan_result(self, *a, **kw):
         return self._base.get_combined_pan_result(*a, **kw)
 
+    def clean_pan_result(self, *a, **kw):
+        return self._base.clean_pan_result(*a, **kw)
+
 
 def load_pan_2ch(path):
     from PIL import Image
@@ -140,6 +147,10 @@ def track_and_write(tracker, name, pans, file_names, categories, out_dir, vis=No
     return annotations, tracks
 
 
+def _exit(message):
+    raise SystemExit(message)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description='UPSNet: panoptic segmentation of frame sequences with instances tracked across frames')
     p.add_argument('--cfg', type=str, default='', help='experiment yaml: the network and its test scales')
@@ -155,6 +166,8 @@ def parse_args(argv=None):
     p.add_argument('--combined', action='store_true', help='track get_combined_pan_result (detections + semantic map) instead of the panoptic head')
     p.add_argument('--vis_panoptic', choices=('flat', 'overlay', 'both'), default=None, help='also draw the tracked maps')
     p.add_argument('--in-flight', type=int, default=1, help='images in flight (1 = the reference loop)')
+    from .config.parse_args import add_pan_component_arguments
+    add_pan_component_arguments(p, 'tracked; also on --track_only inputs')
     from .video_eval import add_arguments, check_arguments
     add_arguments(p)
     return check_arguments(p, p.parse_args(argv))
@@ -182,6 +195,8 @@ def main(argv=None):
     except ValueError as e:
         raise SystemExit('--track_iou / --track_max_age: %s' % e)
     update_config(args.cfg)
+    from .config.parse_args import apply_pan_component_arguments
+    apply_pan_component_arguments(args, _exit)
     net = config.network
     if args.track_only:
         if args.weight_path or args.synthetic_weights or args.combined:
@@ -216,6 +231,9 @@ def main(argv=None):
     if args.track_only:
         for name, paths in sequences:
             pans = [load_pan_2ch(p) for p in paths]
+            if config.test.get('pan_min_component', 0) > 0:
+                from .dataset.base_dataset import BaseDataset
+                pans = BaseDataset().clean_pan_result(pans, what='sequence %s' % name)
             out_dir = os.path.join(args.out, name)
             done.append((name, out_dir) + track_and_write(tracker, name, pans, [os.path.basename(p) for p in paths], categories, out_dir,
                                                           vis=args.vis_panoptic, score=score))
