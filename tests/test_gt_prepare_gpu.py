@@ -55,6 +55,23 @@ def test_kernel_equals_restatement(name):
     _assert_equal(_run(ids), want, name)
 
 
+def test_more_values_than_the_pixel_pass_holds_in_lds():
+    """64 x 64 = one workgroup of the pixel pass, 8 thing labels x 160 instance numbers = 1280 distinct live values on its 4096
+    pixels: more than the 1024 slots of the workgroup's LDS table, so whatever the hash does with them at least 256 values take the
+    global fallback. Capacities that refuse nothing."""
+    from gt_prepare_cases import THING_LABELS
+    from gt_prepare_ref import reference
+    from upsnet_amd.dataset.prepare import label_tables
+    values = np.array([lab * 1000 + k for lab in THING_LABELS for k in range(160)], np.int32)
+    flat = values[np.arange(64 * 64) % len(values)]
+    np.random.default_rng(1024).shuffle(flat)
+    ids = np.ascontiguousarray(flat.reshape(64, 64))
+    assert len(np.unique(ids)) == 1280 > 1024
+    want = reference(ids, label_tables())
+    assert want[2].shape[0] == 1280
+    _assert_equal(_run(ids, seg_capacity=2048, trans_capacity=4 * 64 * 64), want, '1280 values in one workgroup')
+
+
 def test_two_runs_give_identical_bytes():
     for name in ('many_instances', 'checkerboard', '37x53'):
         ids, _ = case(name)

@@ -167,6 +167,23 @@ def test_more_segments_than_travel_with_the_step():
         assert np.array_equal(a[1], b[1]) and a[4] == b[4]
 
 
+def test_more_cells_than_the_count_pass_holds_in_lds():
+    """64 x 64 = one workgroup of the count pass. Every thing key of 16 categories x instances 1..255 on one pixel each, the other 16
+    pixels VOID; the second frame is a permutation of the first. 4080 distinct A_cur cells (and in the second frame as many A_mem
+    cells, plus the joint ones) meet an LDS table of 2048 slots, so whatever the hash does with them, more than half of the cells take
+    the global fallback."""
+    rng = np.random.default_rng(2048)
+    flat = np.full((4096, 3), (255, 0, 0), np.uint8)
+    flat[:4080] = [(c, i, 0) for c in range(16) for i in range(1, 256)]
+    first = flat[rng.permutation(4096)]
+    second = first[rng.permutation(4096)]
+    frames = [np.ascontiguousarray(f.reshape(64, 64, 3)) for f in (first, second)]
+    assert len(np.unique(frames[1].reshape(-1, 3)[:, :2], axis=0)) == 4081 > 2048
+    got = check_against_ref(frames, dict(iou_thresh=0.3, max_age=1))
+    assert len(got[0][1]) == len(got[1][1]) == 4080
+    assert got[1][1][:, 3].sum() > 0 and got[1][1][:, 7].sum() > 0      # matches and take-overs both occur
+
+
 def test_unaligned_input_takes_the_byte_paths():
     frames = ref.blob_sequence(41, 37, 53, 20, 5, [1, 2, 11])
     check_against_ref(frames, dict(iou_thresh=0.3, max_age=1), unaligned=True)

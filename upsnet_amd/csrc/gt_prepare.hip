@@ -11,9 +11,9 @@
 //   instance = a distinct v >= 1000 whose label has a thing row.
 // Integers only, six launches, a workspace that every call leaves zeroed:
 //   gp_seg_kernel     one pass over the pixels, 16 per thread: train-id map, panoptic RGB (v as R + 256 G + 65536 B, ignored -> 0),
-//                     the labelIds cross-check, and the area / bbox of every segment: runs of one value on one row go into an LDS
-//                     table per workgroup, then one global atomic add and four atomic max per distinct value and workgroup
-//                     (pan_seg_kernel's pattern: a full LDS table falls back to the global atomics).
+//                     the labelIds cross-check, and the area / bbox of every segment: runs of one value on one row go into the LDS
+//                     table and the bbox payload of pan_pixels.h (a full LDS table falls back to the global atomics). The walk is
+//                     the kernel's own: its per-pixel outputs are woven into it.
 //   gp_table_kernel   one workgroup: compacts the non-empty values in ascending v into the segment table and the instance list,
 //                     and zeroes every workspace cell it read. More segments than the capacity: flag, rows past it are not written.
 //   gp_trans_kernel   one workgroup per instance, over its bounding box only: tiles of up to 64 columns are read along the rows
@@ -23,14 +23,11 @@
 //                     and fills, so a list can never outgrow its place. No atomics: ascending by construction.
 #include "common.h"
 #include "upsnet_hip.h"
+#include "pan_pixels.h"
 
 #define GP_KEYS 65536             // raw values of a 16-bit PNG
-#define GP_RUN 16                 // pixels per thread in the pixel pass
-#define GP_HASH_BITS 10
+#define GP_HASH_BITS 10           // the pixel pass's LDS table: 1024 values per workgroup, five planes
 #define GP_HASH (1 << GP_HASH_BITS)
-#define GP_PROBES 16
-#define GP_EMPTY 0xffffffffu
-#define GP_INV 0x7fffffff         // minima are kept as the maximum of GP_INV - value
 #define GP_ROW 9                  // v, label, train id, iscrowd, area, x_min, y_min, x_max, y_max
 #define GP_STATUS 8               // segments | instances | transitions | flags | labelIds mismatches | 0 0 0
 #define GP_FLAG_SEGMENTS 1
@@ -44,7 +41,7 @@
 #define GP_TRANS_GRID 1024
 
 struct GpWs {
-    int *area, *nxmin, *nymin, *xmax, *ymax;   // [GP_KEYS] each, zero between calls
+    int *area, *nxmin, *nymin, *xmax, *ymax;   // [GP_KEYS] each, zero between calls: the five planes of pan_pixels.h's bbox payload
     int *inst;                                 // [seg_cap][GP_INST]
     int *cnt;                                  // [seg_cap] transitions per instance
 };
@@ -79,37 +76,6 @@ __device__ static inline void gp_load_labels(int *s_lab, const int *__restrict__
         s_lab[i] = (train_id[i] & 255) | (has_inst[i] != 0) << 8 | ((thing_row[i] + 1) & 255) << 16;
 }
 
-__device__ static inline void gp_global_add(const GpWs &ws, const unsigned key, const int area, const int nx, const int ny, const int xm,
-                                            const int ym)
-{
-    atomicAdd(&ws.area[key], area);
-    atomicMax(&ws.nxmin[key], nx);
-    atomicMax(&ws.nymin[key], ny);
-    atomicMax(&ws.xmax[key], xm);
-    atomicMax(&ws.ymax[key], ym);
-}
-
-// one run of `run` pixels of value key on row y, columns x0 .. x0 + run - 1
-__device__ static inline void gp_flush(unsigned *s_key, int *s_val, const GpWs &ws, const unsigned key, const int run, const int x0, const int y)
-{
-    const int x1 = x0 + run - 1;
-    const unsigned h = (key * 2654435761u) >> (32 - GP_HASH_BITS);
-    for (int p = 0; p < GP_PROBES; ++p) {
-        const unsigned slot = (h + p) & (GP_HASH - 1);
-        unsigned k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k == GP_EMPTY) k = atomicCAS(&s_key[slot], GP_EMPTY, key);
-        if (k == GP_EMPTY || k == key) {
-            atomicAdd(&s_val[slot], run);
-            atomicMax(&s_val[GP_HASH + slot], GP_INV - x0);
-            atomicMax(&s_val[2 * GP_HASH + slot], GP_INV - y);
-            atomicMax(&s_val[3 * GP_HASH + slot], x1);
-            atomicMax(&s_val[4 * GP_HASH + slot], y);
-            return;
-        }
-    }
-    gp_global_add(ws, key, run, GP_INV - x0, GP_INV - y, x1, y);   // LDS table full around this slot (more than ~1000 values)
-}
-
 __global__ void __launch_bounds__(256)
 gp_seg_kernel(const int *__restrict__ ids, const unsigned char *__restrict__ label_ids, const long npix, const int width, const bool vec,
               const int *__restrict__ train_id, const int *__restrict__ has_inst, const int *__restrict__ thing_row, GpWs ws,
@@ -118,16 +84,14 @@ gp_seg_kernel(const int *__restrict__ ids, const unsigned char *__restrict__ lab
     __shared__ unsigned s_key[GP_HASH];
     __shared__ int s_val[5 * GP_HASH];
     __shared__ int s_lab[256];
-    const int t = threadIdx.x;
-    for (int i = t; i < GP_HASH; i += blockDim.x) s_key[i] = GP_EMPTY;
-    for (int i = t; i < 5 * GP_HASH; i += blockDim.x) s_val[i] = 0;
+    pan_lds_clear<GP_HASH_BITS>(s_key, s_val, 5);
     gp_load_labels(s_lab, train_id, has_inst, thing_row);
     __syncthreads();
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * GP_RUN;
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
     if (p0 < npix) {
-        const bool whole = vec && p0 + GP_RUN <= npix;
-        const int cnt = (int)(npix - p0 < GP_RUN ? npix - p0 : GP_RUN);
-        int v[GP_RUN];
+        const bool whole = vec && p0 + PAN_RUN <= npix;
+        const int cnt = (int)(npix - p0 < PAN_RUN ? npix - p0 : PAN_RUN);
+        int v[PAN_RUN];
         unsigned lab[4] = {0, 0, 0, 0};
         if (whole) {
             const int4 *src = (const int4 *)(ids + p0);
@@ -142,7 +106,7 @@ gp_seg_kernel(const int *__restrict__ ids, const unsigned char *__restrict__ lab
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < GP_RUN; ++i) {
+            for (int i = 0; i < PAN_RUN; ++i) {
                 v[i] = i < cnt ? ids[p0 + i] : 0;
                 if (label_ids && i < cnt) lab[i >> 2] |= (unsigned)label_ids[p0 + i] << (8 * (i & 3));
             }
@@ -155,7 +119,7 @@ gp_seg_kernel(const int *__restrict__ ids, const unsigned char *__restrict__ lab
         int run = 0, x0 = 0, ry = 0, mismatch = 0;
         bool range = false, live = false;
 #pragma unroll
-        for (int i = 0; i < GP_RUN; ++i) {
+        for (int i = 0; i < PAN_RUN; ++i) {
             if (i < cnt) {
                 const int raw = v[i];
                 const int label = gp_label(raw);
@@ -169,7 +133,7 @@ gp_seg_kernel(const int *__restrict__ ids, const unsigned char *__restrict__ lab
                 for (int b = 0; b < 3; ++b) o[(3 * i + b) >> 2] |= (c >> (8 * b) & 255u) << (8 * ((3 * i + b) & 3));
                 const unsigned k = (unsigned)raw;
                 if (run == 0 || k != pk || x == 0) {   // a run shares its value and its row
-                    if (run && live) gp_flush(s_key, s_val, ws, pk, run, x0, ry);
+                    if (run && live) pan_box_add<GP_HASH_BITS>(s_key, s_val, ws.area, pk, run, x0, ry);
                     pk = k;
                     run = 0;
                     x0 = x;
@@ -180,7 +144,7 @@ gp_seg_kernel(const int *__restrict__ ids, const unsigned char *__restrict__ lab
                 if (++x == width) { x = 0; ++y; }
             }
         }
-        if (run && live) gp_flush(s_key, s_val, ws, pk, run, x0, ry);
+        if (run && live) pan_box_add<GP_HASH_BITS>(s_key, s_val, ws.area, pk, run, x0, ry);
         if (whole) {
             *(uint4 *)(train_map + p0) = make_uint4(tr[0], tr[1], tr[2], tr[3]);
             uint4 *dst = (uint4 *)(rgb + 3 * p0);
@@ -189,7 +153,7 @@ gp_seg_kernel(const int *__restrict__ ids, const unsigned char *__restrict__ lab
             dst[2] = make_uint4(o[8], o[9], o[10], o[11]);
         } else {
 #pragma unroll
-            for (int i = 0; i < GP_RUN; ++i)
+            for (int i = 0; i < PAN_RUN; ++i)
                 if (i < cnt) {
                     train_map[p0 + i] = (unsigned char)(tr[i >> 2] >> (8 * (i & 3)));
 #pragma unroll
@@ -200,11 +164,7 @@ gp_seg_kernel(const int *__restrict__ ids, const unsigned char *__restrict__ lab
         if (range) atomicOr(&status[3], GP_FLAG_RANGE);
     }
     __syncthreads();
-    for (int i = t; i < GP_HASH; i += blockDim.x) {
-        const unsigned k = s_key[i];
-        if (k != GP_EMPTY)
-            gp_global_add(ws, k, s_val[i], s_val[GP_HASH + i], s_val[2 * GP_HASH + i], s_val[3 * GP_HASH + i], s_val[4 * GP_HASH + i]);
-    }
+    pan_box_drain<GP_HASH_BITS>(s_key, s_val, ws.area);
 }
 
 #define GPT_T 1024
@@ -254,7 +214,7 @@ gp_table_kernel(const int *__restrict__ train_id, const int *__restrict__ has_in
         const int v = t * GPT_PER + j, a = ws.area[v];
         if (a == 0) continue;
         const int label = gp_label(v);
-        const int x_min = GP_INV - ws.nxmin[v], y_min = GP_INV - ws.nymin[v], x_max = ws.xmax[v], y_max = ws.ymax[v];
+        const int x_min = PAN_INV - ws.nxmin[v], y_min = PAN_INV - ws.nymin[v], x_max = ws.xmax[v], y_max = ws.ymax[v];
         ws.area[v] = 0;   // the workspace is zero again for the next image, overflow or not
         ws.nxmin[v] = 0;
         ws.nymin[v] = 0;
@@ -451,7 +411,7 @@ extern "C" int upsnet_gt_prepare(void *stream, const int *ids, const unsigned ch
     hipStream_t st = (hipStream_t)stream;
     const GpWs ws = gp_ws(workspace, seg_capacity);
     const long npix = (long)height * width;
-    const long threads = (npix + GP_RUN - 1) / GP_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const unsigned grid = (unsigned)((threads + 255) / 256);
     const bool vec = (((uintptr_t)ids | (uintptr_t)label_ids | (uintptr_t)train_map | (uintptr_t)rgb) & 15) == 0;
     if (ups_zero_async(status, GP_STATUS * sizeof(int), st)) return 1;

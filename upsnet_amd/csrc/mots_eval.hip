@@ -3,15 +3,14 @@
 // restated in plain numpy in tests/mots_ref.py, never compared with a build of mots_tools). The reference has no video metric.
 //
 // Masks are disjoint on both sides, so a match at IoU > 0.5 is unique and the whole metric is integer counting plus four words of
-// state per GT row. A frame's counts are CELLS kind << 28 | index of an open-addressing hash in global memory, as in video_eval.hip
-// (32-bit cell + 1 claimed by atomicCAS, 0 = empty; the claimer appends its slot to a list, so nothing ever scans the table):
+// state per GT row. A frame's counts are CELLS kind << 28 | index of a global cell table of pan_pixels.h, as in video_eval.hip:
 //   JOINT  row << 16 | key   pixels of the scored GT row (thing, non-crowd) under a pred key of the SAME category
 //   AREA_P key               pixels of the pred key (every key whose category is not a known stuff category)
 //   IGN    key               pixels of the key on its category's ignore region: GT id 0 or not in the table, or a crowd row of its category
 //   AREA_G row               pixels of the scored GT row
 // Per frame, three launches:
-//   mots_hist_kernel   ONE pass over the pixels: 16 pixels per thread (pq_eval.h's loads), equal (row, key) neighbours merged, cells
-//                      pre-aggregated in an LDS hash per workgroup, one global atomic per distinct cell and workgroup
+//   mots_hist_kernel   ONE pass over the pixels: the pixel pass of pan_pixels.h (pair walk, LDS hash per workgroup, one global atomic
+//                      per distinct cell and workgroup)
 //   mots_match_kernel  one thread per cell of the frame's list: a JOINT cell looks its two areas up and applies 3 I > A_g + A_p in
 //                      int64 (the row's partner goes into the row scratch, the key's bit into the matched set); an AREA_P cell looks
 //                      its IGN count up and joins the frame's key list with its exemption flag; unknown categories are reported
@@ -20,7 +19,7 @@
 //                      count the unmatched keys (FP, or exempt) and leave the frame table, both lists and the matched set zero
 // and one per sequence (mots_end_kernel): MT / PT / ML of every row that was present, and every part of the workspace zero again.
 // The two list lengths are double-buffered by the frame's parity: a frame's match pass clears the pair of the frame before, whose
-// last reader ended with the launch before. A full table (MOTS_PROBES slots in a row taken) never loses a count silently: bit 1 of
+// last reader ended with the launch before. A full table (PAN_TABLE_PROBES slots in a row taken) never loses a count silently: bit 1 of
 // status[0] is set and the host raises RuntimeError at its next synchronisation.
 #include "common.h"
 #include "upsnet_hip.h"
@@ -31,7 +30,6 @@
 #define MOTS_IGN 2u
 #define MOTS_AREA_G 3u
 #define MOTS_KIND(k) ((unsigned)(k) << 28)
-#define MOTS_PROBES 256
 #define MOTS_T 1024
 #define MOTS_FULL_FRAME 1ull
 #define MOTS_KBITS (PQ_KEYS / 32)
@@ -56,19 +54,12 @@ struct MotsWs {
     int fbits;
 };
 
-static inline int mots_frame_bits(long npix)
-{
-    int b = 12;
-    while (b < 20 && (1L << b) < npix / 16) ++b;
-    return b;
-}
-
 static inline size_t mots_ws_ints(int bits, int max_gt) { return 16 + MOTS_KBITS + 4 * ((size_t)1 << bits) + 8 * (size_t)max_gt; }
 
 static inline MotsWs mots_ws(void *base, int max_gt, long npix)
 {
     MotsWs w;
-    w.fbits = mots_frame_bits(npix);
+    w.fbits = pan_frame_bits(npix);
     const size_t HC = (size_t)1 << w.fbits;
     int *p = (int *)base;
     w.hdr = p;
@@ -93,56 +84,12 @@ static inline MotsWs mots_ws(void *base, int max_gt, long npix)
     return w;
 }
 
-// count v > 0 of one cell into the frame table; the thread that claims a slot appends it to the frame's list
-__device__ static inline void mots_table_add(const MotsWs &ws, int *counter, unsigned long long *status, const unsigned cell, const unsigned v)
-{
-    const unsigned mask = (1u << ws.fbits) - 1, want = cell + 1;
-    unsigned slot = (cell * 2654435761u) >> (32 - ws.fbits);
-    for (int p = 0; p < MOTS_PROBES; ++p, slot = (slot + 1) & mask) {
-        unsigned k = __hip_atomic_load(&ws.ftab[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == 0) {
-            k = atomicCAS(&ws.ftab[2 * slot], 0u, want);
-            if (k == 0) {
-                const int pos = atomicAdd(counter, 1);
-                if (pos >= 0 && pos <= (int)mask) ws.fslots[pos] = (int)slot;   // one append per slot: always true for a zeroed workspace
-                k = want;
-            }
-        }
-        if (k == want) {
-            atomicAdd(&ws.ftab[2 * slot + 1], v);
-            return;
-        }
-    }
-    atomicOr(status, MOTS_FULL_FRAME);   // never silently: the host raises at its next synchronisation
-}
-
-// the count of a cell of the finished frame table (0 if it has none)
-__device__ static inline unsigned mots_lookup(const MotsWs &ws, const unsigned cell)
-{
-    const unsigned mask = (1u << ws.fbits) - 1, want = cell + 1;
-    unsigned slot = (cell * 2654435761u) >> (32 - ws.fbits);
-    for (int p = 0; p < MOTS_PROBES; ++p, slot = (slot + 1) & mask) {
-        const unsigned k = ws.ftab[2 * slot];
-        if (k == want) return ws.ftab[2 * slot + 1];
-        if (k == 0) return 0u;
-    }
-    return 0u;
-}
-
+// count v > 0 of one cell of the frame: the workgroup's LDS table, or the frame table when that is full around the cell's slot
 __device__ static inline void mots_lds_add(unsigned *s_key, int *s_val, const MotsWs &ws, int *counter, unsigned long long *status,
                                            const unsigned cell, const int v)
 {
-    const unsigned h = (cell * 2654435761u) >> (32 - PQ_HASH_BITS);
-    for (int p = 0; p < PQ_PROBES; ++p) {
-        const unsigned slot = (h + p) & (PQ_HASH - 1);
-        unsigned k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k == PQ_EMPTY) k = atomicCAS(&s_key[slot], PQ_EMPTY, cell);
-        if (k == PQ_EMPTY || k == cell) {
-            atomicAdd(&s_val[slot], v);
-            return;
-        }
-    }
-    mots_table_add(ws, counter, status, cell, (unsigned)v);   // LDS table full around this slot
+    if (!pan_lds_count<PQ_HASH_BITS>(s_key, s_val, cell, v))   // LDS table full around this slot
+        pan_table_add(ws.ftab, ws.fbits, ws.fslots, counter, status, MOTS_FULL_FRAME, cell, (unsigned)v);
 }
 
 // one run of `run` pixels with the same pred key and GT id
@@ -178,39 +125,20 @@ mots_hist_kernel(const unsigned char *__restrict__ pred, const unsigned char *__
     int *s_id = (int *)(s_hist + 2 * PQ_HASH);
     int *s_info = s_id + n;
     const int t = threadIdx.x;
-    for (int i = t; i < PQ_HASH; i += blockDim.x) { s_key[i] = PQ_EMPTY; s_val[i] = 0; }
+    pan_lds_clear<PQ_HASH_BITS>(s_key, s_val, 1);
     for (int i = t; i < n; i += blockDim.x) { s_id[i] = table[2 * i]; s_info[i] = table[2 * i + 1]; }
     s_cat[t] = cat_info[t];
     __syncthreads();
     int *counter = &ws.hdr[par];
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PQ_RUN;
-    if (p0 < npix) {
-        unsigned pw[12], gw[12];
-        pq_load48(pred, p0, npix, vec, pw);
-        pq_load48(gt, p0, npix, vec, gw);
-        unsigned pk = 0;
-        int gid = -1, run = 0;
-#pragma unroll
-        for (int i = 0; i < PQ_RUN; ++i) {
-            if (p0 + i < npix) {
-                const unsigned k = pq_byte(pw, 3 * i) << 8 | pq_byte(pw, 3 * i + 1);
-                const int g = (int)(pq_byte(gw, 3 * i) | pq_byte(gw, 3 * i + 1) << 8 | pq_byte(gw, 3 * i + 2) << 16);
-                if (k != pk || g != gid) {
-                    if (run) mots_flush(s_key, s_val, ws, counter, status, s_id, s_info, s_cat, n, pk, gid, run);
-                    pk = k;
-                    gid = g;
-                    run = 0;
-                }
-                ++run;
-            }
-        }
-        if (run) mots_flush(s_key, s_val, ws, counter, status, s_id, s_info, s_cat, n, pk, gid, run);
-    }
+    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PAN_RUN;
+    if (p0 < npix)
+        pan_pair_walk<false>(pred, gt, nullptr, p0, npix, vec, [&](const unsigned pk, const int gid, unsigned, const int run) {
+            mots_flush(s_key, s_val, ws, counter, status, s_id, s_info, s_cat, n, pk, gid, run);
+        });
     __syncthreads();
-    for (int i = t; i < PQ_HASH; i += blockDim.x) {
-        const unsigned k = s_key[i];
-        if (k != PQ_EMPTY) mots_table_add(ws, counter, status, k, (unsigned)s_val[i]);
-    }
+    pan_lds_drain<PQ_HASH_BITS>(s_key, [&](const unsigned k, const int i) {
+        pan_table_add(ws.ftab, ws.fbits, ws.fslots, counter, status, MOTS_FULL_FRAME, k, (unsigned)s_val[i]);
+    });
 }
 
 // the frame's cells: matches into the row scratch and the matched set, keys into the key list; the table is only read
@@ -236,7 +164,8 @@ mots_match_kernel(MotsWs ws, const int nrows, const int par, const unsigned char
             const int row = (cell >> 16) & 0xfff;
             const unsigned pk = cell & 0xffff;
             if (row >= nrows) continue;
-            const unsigned ap = mots_lookup(ws, MOTS_KIND(MOTS_AREA_P) | pk), ag = mots_lookup(ws, MOTS_KIND(MOTS_AREA_G) | (unsigned)row);
+            const unsigned ap = pan_table_lookup(ws.ftab, ws.fbits, MOTS_KIND(MOTS_AREA_P) | pk);
+            const unsigned ag = pan_table_lookup(ws.ftab, ws.fbits, MOTS_KIND(MOTS_AREA_G) | (unsigned)row);
             if (3ll * (long long)v > (long long)ag + (long long)ap) {   // at most one key per row and one row per key: plain stores
                 ws.r_key[row] = (int)pk + 1;
                 ws.r_i[row] = (int)v;
@@ -247,7 +176,7 @@ mots_match_kernel(MotsWs ws, const int nrows, const int par, const unsigned char
             const unsigned pk = cell & 0xffff;
             if (!(cat_info[pk >> 8] & MOTS_CAT_KNOWN))
                 atomicMin(status + 1, (unsigned long long)(where | (long long)(pk >> 8)));   // the first frame, its lowest category
-            const unsigned ign = mots_lookup(ws, MOTS_KIND(MOTS_IGN) | pk);
+            const unsigned ign = pan_table_lookup(ws.ftab, ws.fbits, MOTS_KIND(MOTS_IGN) | pk);
             const int pos = atomicAdd(&ws.hdr[2 + par], 1);
             if (pos >= 0 && pos < cap) ws.klist[pos] = (int)(pk | (2ll * (long long)ign > (long long)v ? 0x10000u : 0u) | 0x20000u);
         }
@@ -370,7 +299,7 @@ mots_end_kernel(MotsWs ws, const int *__restrict__ table, const int nrows, const
 extern "C" size_t upsnet_mots_eval_workspace_bytes(int max_gt, int height, int width)
 {
     if (max_gt < 0 || max_gt > PQ_MAX_GT || height <= 0 || width <= 0 || (long)height * width > (1L << 24)) return 0;
-    return mots_ws_ints(mots_frame_bits((long)height * width), max_gt) * sizeof(int);
+    return mots_ws_ints(pan_frame_bits((long)height * width), max_gt) * sizeof(int);
 }
 
 extern "C" int upsnet_mots_eval_frame(void *stream, const unsigned char *pred_2ch, const unsigned char *gt_rgb, int height, int width,
@@ -389,7 +318,7 @@ extern "C" int upsnet_mots_eval_frame(void *stream, const unsigned char *pred_2c
     const MotsWs ws = mots_ws(workspace, max_gt, npix);
     unsigned long long *stat = (unsigned long long *)status;
     const bool vec = (((uintptr_t)pred_2ch | (uintptr_t)gt_rgb) & 15) == 0;
-    const long threads = (npix + PQ_RUN - 1) / PQ_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const int par = frame & 1;
     hipLaunchKernelGGL(mots_hist_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), (size_t)(2 * PQ_HASH + 2 * num_rows) * sizeof(int), st,
                        pred_2ch, gt_rgb, npix, vec, table, num_rows, cat_info, ws, par, stat);

@@ -9,7 +9,7 @@
 // has parent[p] == p, VOID has -1.
 //
 // Five launches, no host read between them; the workspace may hold anything on entry:
-//   pc_tile_kernel     one workgroup per 32 x 128 tile, 16 pixels of one row per thread (three 16-byte loads). LDS holds the tile's keys
+//   pc_tile_kernel     one workgroup per 32 x 128 tile, 16 pixels of one row per thread (pan_pixels.h's loads). LDS holds the tile's keys
 //                      and labels. A pixel is seeded with the head of its run inside the thread's 16 pixels; then unions with the
 //                      neighbouring thread's last pixel and with the row above (for 8-connectivity the two upper diagonals, only where
 //                      the pixel above has another key: where it has the same one, the row above links its neighbours already) by
@@ -24,12 +24,12 @@
 //                      counts, wave-reduced.
 #include "common.h"
 #include "upsnet_hip.h"
+#include "pan_pixels.h"
 
 #define PC_KEYS 65536
 #define PC_TH 32                  // tile height
 #define PC_TW 128                 // tile width
-#define PC_RUN 16                 // pixels per thread
-#define PC_T 256                  // threads per workgroup: PC_TH rows x PC_TW / PC_RUN threads
+#define PC_T 256                  // threads per workgroup: PC_TH rows x PC_TW / PAN_RUN threads of 16 pixels
 #define PC_VOID 0xffffu
 #define PC_MAX_PIXELS (1L << 24)
 
@@ -48,46 +48,12 @@ static PcWs pc_ws(void *base, const long npix)
     return w;
 }
 
-__device__ static inline unsigned pc_byte(const unsigned *w, const int j) { return (w[j >> 2] >> (8 * (j & 3))) & 255; }
-
 __device__ static inline unsigned pc_key_of(const unsigned c, const unsigned i) { return c == 255 ? PC_VOID : (c << 8 | i); }
 
-// n (0..16) pixels x 3 bytes from src + 3 * p0: three 16-byte loads when whole and aligned, else byte loads; the rest reads as zeros
-__device__ static inline void pc_load48(const unsigned char *src, const long p0, const int n, const bool vec, unsigned w[12])
-{
-    if (vec && n == PC_RUN) {
-        const uint4 *v = (const uint4 *)(src + 3 * p0);
-        const uint4 a = v[0], b = v[1], c = v[2];
-        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-        w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-        w[8] = c.x; w[9] = c.y; w[10] = c.z; w[11] = c.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) w[j] = 0;
-#pragma unroll
-        for (int j = 0; j < 3 * PC_RUN; ++j)
-            if (j < 3 * n) w[j >> 2] |= (unsigned)src[3 * p0 + j] << (8 * (j & 3));
-    }
-}
-
-__device__ static inline void pc_store48(unsigned char *dst, const long p0, const int n, const bool vec, const unsigned w[12])
-{
-    if (vec && n == PC_RUN) {
-        uint4 *v = (uint4 *)(dst + 3 * p0);
-        v[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        v[1] = make_uint4(w[4], w[5], w[6], w[7]);
-        v[2] = make_uint4(w[8], w[9], w[10], w[11]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 3 * PC_RUN; ++j)
-            if (j < 3 * n) dst[3 * p0 + j] = (unsigned char)pc_byte(w, j);
-    }
-}
-
 // n (0..16) ints from src + p0: four 16-byte accesses when whole and p0 is a multiple of 4 (src is 16-byte aligned), else one by one
-__device__ static inline void pc_load_ints(const int *src, const long p0, const int n, int v[PC_RUN])
+__device__ static inline void pc_load_ints(const int *src, const long p0, const int n, int v[PAN_RUN])
 {
-    if (n == PC_RUN && (p0 & 3) == 0) {
+    if (n == PAN_RUN && (p0 & 3) == 0) {
         const int4 *q = (const int4 *)(src + p0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -96,19 +62,19 @@ __device__ static inline void pc_load_ints(const int *src, const long p0, const 
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < PC_RUN; ++j) v[j] = j < n ? src[p0 + j] : -1;
+        for (int j = 0; j < PAN_RUN; ++j) v[j] = j < n ? src[p0 + j] : -1;
     }
 }
 
-__device__ static inline void pc_store_ints(int *dst, const long p0, const int n, const int v[PC_RUN])
+__device__ static inline void pc_store_ints(int *dst, const long p0, const int n, const int v[PAN_RUN])
 {
-    if (n == PC_RUN && (p0 & 3) == 0) {
+    if (n == PAN_RUN && (p0 & 3) == 0) {
         int4 *q = (int4 *)(dst + p0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) q[j] = make_int4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
     } else {
 #pragma unroll
-        for (int j = 0; j < PC_RUN; ++j)
+        for (int j = 0; j < PAN_RUN; ++j)
             if (j < n) dst[p0 + j] = v[j];
     }
 }
@@ -156,33 +122,34 @@ pc_tile_kernel(const unsigned char *__restrict__ pan, const int H, const int W, 
     for (unsigned i = blockIdx.x * PC_T + t; i < PC_KEYS; i += gridDim.x * PC_T) ws.best[i] = 0ull;
     if (blockIdx.x == 0 && t < 4) stats[t] = 0;
     const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const int ly = t / (PC_TW / PC_RUN), lx0 = (t % (PC_TW / PC_RUN)) * PC_RUN;
+    const int ly = t / (PC_TW / PAN_RUN), lx0 = (t % (PC_TW / PAN_RUN)) * PAN_RUN;
     const int gy = ty * PC_TH + ly, gx0 = tx * PC_TW + lx0;
-    const int n = gy < H ? max(0, min(PC_RUN, W - gx0)) : 0;      // pixels of this thread inside the image
+    const int n = gy < H ? max(0, min(PAN_RUN, W - gx0)) : 0;      // pixels of this thread inside the image
     const long gp = (long)gy * W + gx0;
+    const long q0 = n ? gp : 0;                                   // (a thread outside the image reads and writes nothing)
     unsigned w[12];
-    pc_load48(pan, n ? gp : 0, n, vec, w);
-    unsigned k[PC_RUN];
+    pan_load48(pan, q0, q0 + n, vec, w);
+    unsigned k[PAN_RUN];
     const int base = ly * PC_TW + lx0;
     int head = base;
 #pragma unroll
-    for (int j = 0; j < PC_RUN; ++j) {
-        k[j] = j < n ? pc_key_of(pc_byte(w, 3 * j), pc_byte(w, 3 * j + 1)) : PC_VOID;
+    for (int j = 0; j < PAN_RUN; ++j) {
+        k[j] = j < n ? pc_key_of(pan_byte(w, 3 * j), pan_byte(w, 3 * j + 1)) : PC_VOID;
         if (j > 0 && k[j] != k[j - 1]) head = base + j;
         s_key[base + j] = (unsigned short)k[j];
         s_lab[base + j] = head;
     }
     {
-        int z[PC_RUN];
+        int z[PAN_RUN];
 #pragma unroll
-        for (int j = 0; j < PC_RUN; ++j) z[j] = 0;
-        pc_store_ints(ws.area, n ? gp : 0, n, z);
+        for (int j = 0; j < PAN_RUN; ++j) z[j] = 0;
+        pc_store_ints(ws.area, q0, n, z);
     }
     __syncthreads();
     if (lx0 > 0 && k[0] != PC_VOID && s_key[base - 1] == k[0]) pc_union_lds(s_lab, base, base - 1);
     if (ly > 0) {
 #pragma unroll
-        for (int j = 0; j < PC_RUN; ++j) {
+        for (int j = 0; j < PAN_RUN; ++j) {
             const unsigned kj = k[j];
             if (kj == PC_VOID) continue;
             const int q = base + j, lx = lx0 + j;
@@ -196,10 +163,10 @@ pc_tile_kernel(const unsigned char *__restrict__ pan, const int H, const int W, 
         }
     }
     __syncthreads();
-    int out[PC_RUN];
+    int out[PAN_RUN];
     int root = 0;
 #pragma unroll
-    for (int j = 0; j < PC_RUN; ++j) {
+    for (int j = 0; j < PAN_RUN; ++j) {
         if (k[j] == PC_VOID) {
             out[j] = -1;
         } else {
@@ -210,7 +177,7 @@ pc_tile_kernel(const unsigned char *__restrict__ pan, const int H, const int W, 
             out[j] = root;
         }
     }
-    pc_store_ints(ws.parent, n ? gp : 0, n, out);
+    pc_store_ints(ws.parent, q0, n, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- global union-find
@@ -282,14 +249,14 @@ pc_seam_kernel(const unsigned char *__restrict__ pan, const int H, const int W, 
 __global__ void __launch_bounds__(PC_T)
 pc_flatten_kernel(const long npix, PcWs ws)
 {
-    const long p0 = ((long)blockIdx.x * PC_T + threadIdx.x) * PC_RUN;
+    const long p0 = ((long)blockIdx.x * PC_T + threadIdx.x) * PAN_RUN;
     if (p0 >= npix) return;
-    const int n = (int)min((long)PC_RUN, npix - p0);
-    int v[PC_RUN];
+    const int n = (int)min((long)PAN_RUN, npix - p0);
+    int v[PAN_RUN];
     pc_load_ints(ws.parent, p0, n, v);
     int prev = -1, root = -1, run_root = -1, run = 0;
 #pragma unroll
-    for (int j = 0; j < PC_RUN; ++j) {
+    for (int j = 0; j < PAN_RUN; ++j) {
         if (j < n && v[j] >= 0) {
             if (v[j] != prev) {
                 prev = v[j];
@@ -311,14 +278,14 @@ pc_flatten_kernel(const long npix, PcWs ws)
 __global__ void __launch_bounds__(PC_T)
 pc_main_kernel(const unsigned char *__restrict__ pan, const long npix, PcWs ws, int *stats)
 {
-    const long p0 = ((long)blockIdx.x * PC_T + threadIdx.x) * PC_RUN;
+    const long p0 = ((long)blockIdx.x * PC_T + threadIdx.x) * PAN_RUN;
     int ncomp = 0, nkeys = 0;
     if (p0 < npix) {
-        const int n = (int)min((long)PC_RUN, npix - p0);
-        int v[PC_RUN];
+        const int n = (int)min((long)PAN_RUN, npix - p0);
+        int v[PAN_RUN];
         pc_load_ints(ws.parent, p0, n, v);
 #pragma unroll
-        for (int j = 0; j < PC_RUN; ++j) {
+        for (int j = 0; j < PAN_RUN; ++j) {
             if (j < n && v[j] == (int)(p0 + j)) {
                 const unsigned p = (unsigned)(p0 + j);
                 const unsigned long long cand = (unsigned long long)(unsigned)ws.area[p] << 32 | (0xffffffffu - p);
@@ -341,24 +308,24 @@ __global__ void __launch_bounds__(PC_T)
 pc_apply_kernel(const unsigned char *pan, unsigned char *out, int *labels, const long npix, const bool vec, const int min_area,
                 const int keep_largest, PcWs ws, int *stats)
 {
-    const long p0 = ((long)blockIdx.x * PC_T + threadIdx.x) * PC_RUN;
+    const long p0 = ((long)blockIdx.x * PC_T + threadIdx.x) * PAN_RUN;
     int ncomp = 0, npixels = 0;
     if (p0 < npix) {
-        const int n = (int)min((long)PC_RUN, npix - p0);
+        const int n = (int)min((long)PAN_RUN, npix - p0);
         unsigned w[12];
-        int v[PC_RUN];
-        pc_load48(pan, p0, n, vec, w);
+        int v[PAN_RUN];
+        pan_load48(pan, p0, p0 + n, vec, w);
         pc_load_ints(ws.parent, p0, n, v);
         int prev = -1;
         bool removed = false;
 #pragma unroll
-        for (int j = 0; j < PC_RUN; ++j) {
+        for (int j = 0; j < PAN_RUN; ++j) {
             if (j < n && v[j] >= 0) {
                 if (v[j] != prev) {
                     prev = v[j];
                     removed = ws.area[prev] < min_area;
                     if (removed && keep_largest) {
-                        const unsigned key = pc_byte(w, 3 * j) << 8 | pc_byte(w, 3 * j + 1);
+                        const unsigned key = pan_byte(w, 3 * j) << 8 | pan_byte(w, 3 * j + 1);
                         removed = (unsigned)ws.best[key] != 0xffffffffu - (unsigned)prev;
                     }
                 }
@@ -370,7 +337,7 @@ pc_apply_kernel(const unsigned char *pan, unsigned char *out, int *labels, const
                 }
             }
         }
-        pc_store48(out, p0, n, vec, w);
+        pan_store48(out, p0, p0 + n, vec, w);
         if (labels) pc_store_ints(labels, p0, n, v);
     }
     ncomp = pc_wave_sum(ncomp);
@@ -414,7 +381,7 @@ extern "C" int upsnet_pan_components(void *stream, const unsigned char *pan_2ch,
                            conn8, ws.parent);
         UPS_CHECK_LAUNCH("pc_seam_kernel");
     }
-    const long threads = (npix + PC_RUN - 1) / PC_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const unsigned grid = (unsigned)((threads + PC_T - 1) / PC_T);
     hipLaunchKernelGGL(pc_flatten_kernel, dim3(grid), dim3(PC_T), 0, st, npix, ws);
     UPS_CHECK_LAUNCH("pc_flatten_kernel");

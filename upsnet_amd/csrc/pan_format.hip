@@ -6,7 +6,7 @@
 //
 // Reference (numpy, host): np.unique over 1000 * ch0 + ch1, then per segment a full-image mask for its colour, area and bbox.
 // Here, integers only, three launches per image and a workspace that every call leaves zeroed:
-//   pan_seg_kernel     one pass over the pixels: 16 pixels per thread, run-length compressed (a run ends with its key or its row), an
+//   pan_seg_kernel     the pixel pass of pan_pixels.h with the row walk (a run ends with its key or its row) and the bbox payload: an
 //                      LDS table per workgroup, then per distinct key and workgroup one global atomic add (area) and four atomic max
 //                      (x_max, y_max, INV - x_min, INV - y_min: a zeroed cell is "nothing yet" for all five). A full LDS table
 //                      falls back to the global atomics, so a pixel-noise map with all 65280 keys is still exact.
@@ -24,15 +24,12 @@
 // taken. 100003 is coprime to 61^3, so the 226981 attempts visit every cell of the +-30 cube once.
 #include "common.h"
 #include "upsnet_hip.h"
+#include "pan_pixels.h"
 
 #define PF_KEYS 65536
 #define PF_MAX_SEGMENTS 65280     // 255 categories x 256 instances
-#define PF_RUN 16                 // pixels per thread in the pixel passes
-#define PF_HASH_BITS 10
+#define PF_HASH_BITS 10           // the segment pass's LDS table: 1024 keys per workgroup, five planes
 #define PF_HASH (1 << PF_HASH_BITS)
-#define PF_PROBES 16
-#define PF_EMPTY 0xffffffffu
-#define PF_INV 0x7fffffff         // minima are kept as the maximum of PF_INV - value (> 0 for every coordinate)
 #define PF_CUBE 226981u           // 61^3 offsets of the +-30 cube
 #define PF_STEP 100003u
 #define PF_TAKEN_WORDS (1 << 19)  // one bit per 24-bit colour
@@ -41,7 +38,8 @@
 #define PF_RELABEL_LDS 4096       // segments whose table (and counters) the relabel kernel keeps in LDS
 #define PF_INV62 (1ull << 62)
 
-// Workspace (ints): area | INV - x_min | INV - y_min | x_max | y_max | colour, each [PF_KEYS], then the taken bitmap
+// Workspace (ints): area | INV - x_min | INV - y_min | x_max | y_max (the five planes of pan_pixels.h's bbox payload, from `area`) |
+// colour, each [PF_KEYS], then the taken bitmap
 struct PfWs {
     int *area, *nxmin, *nymin, *xmax, *ymax;
     unsigned *color, *taken;
@@ -61,113 +59,20 @@ static PfWs pf_ws(void *base)
     return w;
 }
 
-__device__ static inline unsigned pf_byte(const unsigned *w, const int j) { return (w[j >> 2] >> (8 * (j & 3))) & 255; }
-
-// 16 pixels x 3 bytes = 48 bytes per thread: three 16-byte loads when the chunk is whole and the base aligned, else byte loads
-__device__ static inline void pf_load48(const unsigned char *__restrict__ src, const long p0, const long npix, const bool vec, unsigned w[12])
-{
-    if (vec && p0 + PF_RUN <= npix) {
-        const uint4 *v = (const uint4 *)(src + 3 * p0);
-        const uint4 a = v[0], b = v[1], c = v[2];
-        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-        w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-        w[8] = c.x; w[9] = c.y; w[10] = c.z; w[11] = c.w;
-    } else {
-        const long nb = 3 * (npix - p0);
-#pragma unroll
-        for (int j = 0; j < 12; ++j) w[j] = 0;
-#pragma unroll
-        for (int j = 0; j < 3 * PF_RUN; ++j)
-            if (j < nb) w[j >> 2] |= (unsigned)src[3 * p0 + j] << (8 * (j & 3));
-    }
-}
-
-__device__ static inline void pf_store48(unsigned char *__restrict__ dst, const long p0, const long npix, const bool vec, const unsigned w[12])
-{
-    if (vec && p0 + PF_RUN <= npix) {
-        uint4 *v = (uint4 *)(dst + 3 * p0);
-        v[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        v[1] = make_uint4(w[4], w[5], w[6], w[7]);
-        v[2] = make_uint4(w[8], w[9], w[10], w[11]);
-    } else {
-        const long nb = 3 * (npix - p0);
-#pragma unroll
-        for (int j = 0; j < 3 * PF_RUN; ++j)
-            if (j < nb) dst[3 * p0 + j] = (unsigned char)pf_byte(w, j);
-    }
-}
-
-__device__ static inline void pf_global_add(const PfWs &ws, const unsigned key, const int area, const int nx, const int ny, const int xm,
-                                            const int ym)
-{
-    atomicAdd(&ws.area[key], area);
-    atomicMax(&ws.nxmin[key], nx);
-    atomicMax(&ws.nymin[key], ny);
-    atomicMax(&ws.xmax[key], xm);
-    atomicMax(&ws.ymax[key], ym);
-}
-
-// one run of `run` pixels of one key on row y, columns x0 .. x0 + run - 1: its bbox share is its two end columns and its row
-__device__ static inline void pf_flush(unsigned *s_key, int *s_val, const PfWs &ws, const unsigned key, const int run, const int x0, const int y)
-{
-    if ((key >> 8) == 255) return;   // VOID, whatever its instance
-    const int x1 = x0 + run - 1;
-    const unsigned h = (key * 2654435761u) >> (32 - PF_HASH_BITS);
-    for (int p = 0; p < PF_PROBES; ++p) {
-        const unsigned slot = (h + p) & (PF_HASH - 1);
-        unsigned k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k == PF_EMPTY) k = atomicCAS(&s_key[slot], PF_EMPTY, key);
-        if (k == PF_EMPTY || k == key) {
-            atomicAdd(&s_val[slot], run);
-            atomicMax(&s_val[PF_HASH + slot], PF_INV - x0);
-            atomicMax(&s_val[2 * PF_HASH + slot], PF_INV - y);
-            atomicMax(&s_val[3 * PF_HASH + slot], x1);
-            atomicMax(&s_val[4 * PF_HASH + slot], y);
-            return;
-        }
-    }
-    pf_global_add(ws, key, run, PF_INV - x0, PF_INV - y, x1, y);   // LDS table full around this slot (noise-like maps)
-}
-
 __global__ void __launch_bounds__(256)
 pan_seg_kernel(const unsigned char *__restrict__ pred, const long npix, const int width, const bool vec, PfWs ws)
 {
     __shared__ unsigned s_key[PF_HASH];
     __shared__ int s_val[5 * PF_HASH];
-    const int t = threadIdx.x;
-    for (int i = t; i < PF_HASH; i += blockDim.x) s_key[i] = PF_EMPTY;
-    for (int i = t; i < 5 * PF_HASH; i += blockDim.x) s_val[i] = 0;
+    pan_lds_clear<PF_HASH_BITS>(s_key, s_val, 5);
     __syncthreads();
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PF_RUN;
-    if (p0 < npix) {
-        unsigned w[12];
-        pf_load48(pred, p0, npix, vec, w);
-        int x = (int)(p0 % width), y = (int)(p0 / width);
-        unsigned pk = 0;
-        int run = 0, x0 = 0, ry = 0;
-#pragma unroll
-        for (int i = 0; i < PF_RUN; ++i) {
-            if (p0 + i < npix) {
-                const unsigned k = pf_byte(w, 3 * i) << 8 | pf_byte(w, 3 * i + 1);
-                if (run == 0 || k != pk || x == 0) {   // a run shares its key and its row
-                    if (run) pf_flush(s_key, s_val, ws, pk, run, x0, ry);
-                    pk = k;
-                    run = 0;
-                    x0 = x;
-                    ry = y;
-                }
-                ++run;
-                if (++x == width) { x = 0; ++y; }
-            }
-        }
-        if (run) pf_flush(s_key, s_val, ws, pk, run, x0, ry);
-    }
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
+    if (p0 < npix)
+        pan_row_walk(pred, p0, npix, width, vec, [&](const unsigned key, const int run, const int x0, const int y) {
+            if ((key >> 8) != 255) pan_box_add<PF_HASH_BITS>(s_key, s_val, ws.area, key, run, x0, y);   // VOID, whatever its instance, is no segment
+        });
     __syncthreads();
-    for (int i = t; i < PF_HASH; i += blockDim.x) {
-        const unsigned k = s_key[i];
-        if (k != PF_EMPTY)
-            pf_global_add(ws, k, s_val[i], s_val[PF_HASH + i], s_val[2 * PF_HASH + i], s_val[3 * PF_HASH + i], s_val[4 * PF_HASH + i]);
-    }
+    pan_box_drain<PF_HASH_BITS>(s_key, s_val, ws.area);
 }
 
 __host__ __device__ static inline unsigned pf_lowbias32(unsigned x)
@@ -233,8 +138,8 @@ pan_color_kernel(const int *__restrict__ cat_table, PfWs ws, int *__restrict__ t
         int *row = table + PF_HEAD + (size_t)pos * PF_ROW;
         row[0] = key;
         row[1] = a;
-        row[2] = PF_INV - ws.nxmin[key];
-        row[3] = PF_INV - ws.nymin[key];
+        row[2] = PAN_INV - ws.nxmin[key];
+        row[3] = PAN_INV - ws.nymin[key];
         row[4] = ws.xmax[key];
         row[5] = ws.ymax[key];
         row[6] = 0;
@@ -294,16 +199,16 @@ __global__ void __launch_bounds__(256)
 pan_paint_kernel(const unsigned char *__restrict__ pred, unsigned char *__restrict__ rgb, const long npix, const bool vec,
                  const unsigned *__restrict__ color)
 {
-    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PF_RUN;
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
     if (p0 >= npix) return;
     unsigned w[12], o[12];
-    pf_load48(pred, p0, npix, vec, w);
+    pan_load48(pred, p0, npix, vec, w);
 #pragma unroll
     for (int j = 0; j < 12; ++j) o[j] = 0;
     unsigned pk = 0xffffffffu, c = 0;
 #pragma unroll
-    for (int i = 0; i < PF_RUN; ++i) {
-        const unsigned k = pf_byte(w, 3 * i) << 8 | pf_byte(w, 3 * i + 1);   // (pixels past the end read as key 0 and are not stored)
+    for (int i = 0; i < PAN_RUN; ++i) {
+        const unsigned k = pan_byte(w, 3 * i) << 8 | pan_byte(w, 3 * i + 1);   // (pixels past the end read as key 0 and are not stored)
         if (k != pk) {
             pk = k;
             c = (k >> 8) == 255 ? 0u : color[k];
@@ -311,7 +216,7 @@ pan_paint_kernel(const unsigned char *__restrict__ pred, unsigned char *__restri
 #pragma unroll
         for (int b = 0; b < 3; ++b) o[(3 * i + b) >> 2] |= (c >> (8 * b) & 255u) << (8 * ((3 * i + b) & 3));
     }
-    pf_store48(rgb, p0, npix, vec, o);
+    pan_store48(rgb, p0, npix, vec, o);
 }
 
 extern "C" size_t upsnet_pan_format_workspace_bytes(void) { return ((size_t)6 * PF_KEYS + PF_TAKEN_WORDS) * sizeof(int); }
@@ -327,7 +232,7 @@ extern "C" int upsnet_pan_format(void *stream, const unsigned char *pred_2ch, in
     hipStream_t st = (hipStream_t)stream;
     const PfWs ws = pf_ws(workspace);
     const long npix = (long)height * width;
-    const long threads = (npix + PF_RUN - 1) / PF_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const unsigned grid = (unsigned)((threads + 255) / 256);
     hipLaunchKernelGGL(pan_seg_kernel, dim3(grid), dim3(256), 0, st, pred_2ch, npix, width, ((uintptr_t)pred_2ch & 15) == 0, ws);
     UPS_CHECK_LAUNCH("pan_seg_kernel");
@@ -374,18 +279,18 @@ pan_relabel_kernel(const unsigned char *__restrict__ rgb, unsigned char *__restr
         }
         __syncthreads();
     }
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PF_RUN;
+    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PAN_RUN;
     if (p0 < npix) {
         unsigned w[12], o[12];
-        pf_load48(rgb, p0, npix, vec, w);
+        pan_load48(rgb, p0, npix, vec, w);
 #pragma unroll
         for (int j = 0; j < 12; ++j) o[j] = 0;
         int pid = -1, row = -1, run = 0;
         unsigned cs = 255u << 8;
 #pragma unroll
-        for (int i = 0; i < PF_RUN; ++i) {
+        for (int i = 0; i < PAN_RUN; ++i) {
             if (p0 + i < npix) {
-                const int id = (int)(pf_byte(w, 3 * i) | pf_byte(w, 3 * i + 1) << 8 | pf_byte(w, 3 * i + 2) << 16);
+                const int id = (int)(pan_byte(w, 3 * i) | pan_byte(w, 3 * i + 1) << 8 | pan_byte(w, 3 * i + 2) << 16);
                 if (id != pid) {
                     if (run && row >= 0) atomicAdd(use_lds ? &s_cnt[row] : &counts[row], run);
                     pid = id;
@@ -404,7 +309,7 @@ pan_relabel_kernel(const unsigned char *__restrict__ rgb, unsigned char *__restr
             }
         }
         if (run && row >= 0) atomicAdd(use_lds ? &s_cnt[row] : &counts[row], run);
-        pf_store48(out, p0, npix, vec, o);
+        pan_store48(out, p0, npix, vec, o);
     }
     if (use_lds) {
         __syncthreads();
@@ -436,7 +341,7 @@ extern "C" int upsnet_pan_relabel(void *stream, const unsigned char *rgb, int he
     hipStream_t st = (hipStream_t)stream;
     const int n = num_segments;
     const long npix = (long)height * width;
-    const long threads = (npix + PF_RUN - 1) / PF_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const bool use_lds = n <= PF_RELABEL_LDS;
     const bool vec = (((uintptr_t)rgb | (uintptr_t)out_2ch) & 15) == 0;
     hipLaunchKernelGGL(pan_relabel_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), use_lds ? (size_t)n * 3 * sizeof(int) : 0, st,

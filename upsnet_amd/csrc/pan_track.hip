@@ -9,7 +9,7 @@
 // unassigned track ages as a whole), so the frame index is kept once per track: stamp[key] = frame index + 1 (0 = never assigned).
 //
 // Three launches per frame, no host read between them:
-//   pt_count_kernel    one pass over the pixels, 16 per thread, run-length compressed over (current key, memory key); an LDS hash
+//   pt_count_kernel    the pixel pass of pan_pixels.h with its own walk: runs of equal (current key, memory key), an LDS hash
 //                      table per workgroup, one global atomic per distinct cell and workgroup (a full table falls back to the global
 //                      atomic). Cells: A_cur[key], A_mem[key], I[current key][j] for equal categories. The first arrival at an A_cur
 //                      cell counts the segment into nseg[c] (the row offsets of the table).
@@ -27,13 +27,11 @@
 // pan_stable_kernel paints the frame-stable colours of a tracked map (a pure function of (category, instance)).
 #include "common.h"
 #include "upsnet_hip.h"
+#include "pan_pixels.h"
 
 #define PT_KEYS 65536
-#define PT_RUN 16                 // pixels per thread in the pixel passes
-#define PT_HASH_BITS 11
+#define PT_HASH_BITS 11           // the count pass's LDS table: 2048 cells per workgroup
 #define PT_HASH (1 << PT_HASH_BITS)
-#define PT_PROBES 16
-#define PT_EMPTY 0xffffffffu
 #define PT_MEM_OFF PT_KEYS        // A_mem cells
 #define PT_JOINT_OFF (2 * PT_KEYS)   // I[current key][j]
 #define PT_MAX_PIXELS (1L << 24)
@@ -70,73 +68,6 @@ static PtWs pt_ws(void *base)
     return w;
 }
 
-__device__ static inline unsigned pt_byte(const unsigned *w, const int j) { return (w[j >> 2] >> (8 * (j & 3))) & 255; }
-__device__ static inline unsigned pt_half(const unsigned *w, const int j) { return (w[j >> 1] >> (16 * (j & 1))) & 65535; }
-
-// 16 pixels x 3 bytes per thread: three 16-byte loads when the chunk is whole and the base aligned, else byte loads
-__device__ static inline void pt_load48(const unsigned char *__restrict__ src, const long p0, const long npix, const bool vec, unsigned w[12])
-{
-    if (vec && p0 + PT_RUN <= npix) {
-        const uint4 *v = (const uint4 *)(src + 3 * p0);
-        const uint4 a = v[0], b = v[1], c = v[2];
-        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-        w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-        w[8] = c.x; w[9] = c.y; w[10] = c.z; w[11] = c.w;
-    } else {
-        const long nb = 3 * (npix - p0);
-#pragma unroll
-        for (int j = 0; j < 12; ++j) w[j] = 0;
-#pragma unroll
-        for (int j = 0; j < 3 * PT_RUN; ++j)
-            if (j < nb) w[j >> 2] |= (unsigned)src[3 * p0 + j] << (8 * (j & 3));
-    }
-}
-
-__device__ static inline void pt_store48(unsigned char *__restrict__ dst, const long p0, const long npix, const bool vec, const unsigned w[12])
-{
-    if (vec && p0 + PT_RUN <= npix) {
-        uint4 *v = (uint4 *)(dst + 3 * p0);
-        v[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        v[1] = make_uint4(w[4], w[5], w[6], w[7]);
-        v[2] = make_uint4(w[8], w[9], w[10], w[11]);
-    } else {
-        const long nb = 3 * (npix - p0);
-#pragma unroll
-        for (int j = 0; j < 3 * PT_RUN; ++j)
-            if (j < nb) dst[3 * p0 + j] = (unsigned char)pt_byte(w, j);
-    }
-}
-
-// 16 memory keys (uint16) per thread: two 16-byte accesses or element accesses
-__device__ static inline void pt_load_keys(const unsigned short *__restrict__ src, const long p0, const long npix, const bool vec, unsigned w[8])
-{
-    if (vec && p0 + PT_RUN <= npix) {
-        const uint4 *v = (const uint4 *)(src + p0);
-        const uint4 a = v[0], b = v[1];
-        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-        w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) w[j] = 0;
-#pragma unroll
-        for (int j = 0; j < PT_RUN; ++j)
-            if (p0 + j < npix) w[j >> 1] |= (unsigned)src[p0 + j] << (16 * (j & 1));
-    }
-}
-
-__device__ static inline void pt_store_keys(unsigned short *__restrict__ dst, const long p0, const long npix, const bool vec, const unsigned w[8])
-{
-    if (vec && p0 + PT_RUN <= npix) {
-        uint4 *v = (uint4 *)(dst + p0);
-        v[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        v[1] = make_uint4(w[4], w[5], w[6], w[7]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < PT_RUN; ++j)
-            if (p0 + j < npix) dst[p0 + j] = (unsigned short)pt_half(w, j);
-    }
-}
-
 __device__ static inline bool pt_is_thing(const unsigned key) { return (key >> 8) != 255 && (key & 255) != 0; }
 
 // global count of one cell (v > 0): the first arrival at an A_cur cell counts the segment into its category
@@ -148,17 +79,7 @@ __device__ static inline void pt_global_add(const PtWs &ws, const unsigned cell,
 
 __device__ static inline void pt_add(unsigned *s_key, int *s_val, const PtWs &ws, const unsigned cell, const int v)
 {
-    const unsigned h = (cell * 2654435761u) >> (32 - PT_HASH_BITS);
-    for (int p = 0; p < PT_PROBES; ++p) {
-        const unsigned slot = (h + p) & (PT_HASH - 1);
-        unsigned k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k == PT_EMPTY) k = atomicCAS(&s_key[slot], PT_EMPTY, cell);
-        if (k == PT_EMPTY || k == cell) {
-            atomicAdd(&s_val[slot], v);
-            return;
-        }
-    }
-    pt_global_add(ws, cell, v);   // LDS table full around this slot (noise-like maps): straight to the global count
+    if (!pan_lds_count<PT_HASH_BITS>(s_key, s_val, cell, v)) pt_global_add(ws, cell, v);   // LDS table full around this slot
 }
 
 // one run of `run` pixels with the same current key and memory key (0 = no entry)
@@ -177,21 +98,20 @@ pt_count_kernel(const unsigned char *__restrict__ cur, const unsigned short *__r
 {
     __shared__ unsigned s_key[PT_HASH];
     __shared__ int s_val[PT_HASH];
-    const int t = threadIdx.x;
-    for (int i = t; i < PT_HASH; i += blockDim.x) { s_key[i] = PT_EMPTY; s_val[i] = 0; }
+    pan_lds_clear<PT_HASH_BITS>(s_key, s_val, 1);
     __syncthreads();
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PT_RUN;
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
     if (p0 < npix) {
         unsigned cw[12], mw[8];
-        pt_load48(cur, p0, npix, vec, cw);
-        pt_load_keys(mem, p0, npix, vec, mw);
+        pan_load48(cur, p0, npix, vec, cw);
+        pan_load_halves(mem, p0, npix, vec, mw);
         unsigned pc = 0, pm = 0;
         int run = 0;
 #pragma unroll
-        for (int i = 0; i < PT_RUN; ++i) {
+        for (int i = 0; i < PAN_RUN; ++i) {
             if (p0 + i < npix) {
-                const unsigned c = pt_byte(cw, 3 * i) << 8 | pt_byte(cw, 3 * i + 1);
-                const unsigned m = pt_half(mw, i);
+                const unsigned c = pan_byte(cw, 3 * i) << 8 | pan_byte(cw, 3 * i + 1);
+                const unsigned m = pan_half(mw, i);
                 if (c != pc || m != pm) {
                     if (run) pt_flush(s_key, s_val, ws, pc, pm, run);
                     pc = c;
@@ -204,10 +124,7 @@ pt_count_kernel(const unsigned char *__restrict__ cur, const unsigned short *__r
         if (run) pt_flush(s_key, s_val, ws, pc, pm, run);
     }
     __syncthreads();
-    for (int i = t; i < PT_HASH; i += blockDim.x) {
-        const unsigned k = s_key[i];
-        if (k != PT_EMPTY) pt_global_add(ws, k, s_val[i]);
-    }
+    pan_lds_drain<PT_HASH_BITS>(s_key, [&](const unsigned k, const int i) { pt_global_add(ws, k, s_val[i]); });
 }
 
 // a strictly precedes b: IoU descending, compared exactly (I, U <= 2^25: the products fit int64), ties by ascending (i << 8 | j)
@@ -358,11 +275,11 @@ pt_relabel_kernel(const unsigned char *__restrict__ cur, unsigned char *__restri
                   const bool vec, const int frame, const int max_age, PtWs ws)
 {
     if (blockIdx.x == 0) ws.nseg[threadIdx.x] = 0;             // (256 threads; read by the match pass only, which has finished)
-    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PT_RUN;
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
     if (p0 >= npix) return;
     unsigned cw[12], mw[8], ow[12], kw[8];
-    pt_load48(cur, p0, npix, vec, cw);
-    pt_load_keys(mem, p0, npix, vec, mw);
+    pan_load48(cur, p0, npix, vec, cw);
+    pan_load_halves(mem, p0, npix, vec, mw);
 #pragma unroll
     for (int j = 0; j < 12; ++j) ow[j] = 0;
 #pragma unroll
@@ -370,9 +287,9 @@ pt_relabel_kernel(const unsigned char *__restrict__ cur, unsigned char *__restri
     unsigned pc = 0xffffffffu, pm = 0xffffffffu, id = 0;
     bool thing = false, keep = false;
 #pragma unroll
-    for (int i = 0; i < PT_RUN; ++i) {
-        const unsigned b0 = pt_byte(cw, 3 * i), b1 = pt_byte(cw, 3 * i + 1), b2 = pt_byte(cw, 3 * i + 2);
-        const unsigned c = b0 << 8 | b1, m = pt_half(mw, i);   // (pixels past the end read as zeros and are not stored)
+    for (int i = 0; i < PAN_RUN; ++i) {
+        const unsigned b0 = pan_byte(cw, 3 * i), b1 = pan_byte(cw, 3 * i + 1), b2 = pan_byte(cw, 3 * i + 2);
+        const unsigned c = b0 << 8 | b1, m = pan_half(mw, i);   // (pixels past the end read as zeros and are not stored)
         if (c != pc) {
             pc = c;
             thing = pt_is_thing(c);
@@ -393,8 +310,8 @@ pt_relabel_kernel(const unsigned char *__restrict__ cur, unsigned char *__restri
         ow[(3 * i + 2) >> 2] |= o2 << (8 * ((3 * i + 2) & 3));
         kw[i >> 1] |= k << (16 * (i & 1));
     }
-    pt_store48(out, p0, npix, vec, ow);
-    pt_store_keys(mem, p0, npix, vec, kw);
+    pan_store48(out, p0, npix, vec, ow);
+    pan_store_halves(mem, p0, npix, vec, kw);
 }
 
 extern "C" size_t upsnet_pan_track_workspace_bytes(int height, int width)
@@ -429,7 +346,7 @@ extern "C" int upsnet_pan_track_step(void *stream, const unsigned char *pan_2ch,
     PtWs ws = pt_ws(workspace);
     const long npix = (long)height * width;
     ws.table += (size_t)(frame & 1) * pt_table_ints(npix);
-    const long threads = (npix + PT_RUN - 1) / PT_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const unsigned grid = (unsigned)((threads + 255) / 256);
     const bool vec_in = (((uintptr_t)pan_2ch | (uintptr_t)memory) & 15) == 0;
     hipLaunchKernelGGL(pt_count_kernel, dim3(grid), dim3(256), 0, st, pan_2ch, memory, npix, vec_in, ws);
@@ -495,16 +412,16 @@ __global__ void __launch_bounds__(256)
 pan_stable_kernel(const unsigned char *__restrict__ pred, unsigned char *__restrict__ rgb, const long npix, const bool vec,
                   const int *__restrict__ cat_table, const int mode)
 {
-    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PT_RUN;
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
     if (p0 >= npix) return;
     unsigned w[12], o[12];
-    pt_load48(pred, p0, npix, vec, w);
+    pan_load48(pred, p0, npix, vec, w);
 #pragma unroll
     for (int j = 0; j < 12; ++j) o[j] = 0;
     unsigned pk = 0xffffffffu, c = 0;
 #pragma unroll
-    for (int i = 0; i < PT_RUN; ++i) {
-        const unsigned k = pt_byte(w, 3 * i) << 8 | pt_byte(w, 3 * i + 1);
+    for (int i = 0; i < PAN_RUN; ++i) {
+        const unsigned k = pan_byte(w, 3 * i) << 8 | pan_byte(w, 3 * i + 1);
         if (k != pk) {
             pk = k;
             c = ps_colour(cat_table, k, mode);
@@ -512,7 +429,7 @@ pan_stable_kernel(const unsigned char *__restrict__ pred, unsigned char *__restr
 #pragma unroll
         for (int b = 0; b < 3; ++b) o[(3 * i + b) >> 2] |= (c >> (8 * b) & 255u) << (8 * ((3 * i + b) & 3));
     }
-    pt_store48(rgb, p0, npix, vec, o);
+    pan_store48(rgb, p0, npix, vec, o);
 }
 
 extern "C" int upsnet_pan_stable_colors(void *stream, const unsigned char *pred_2ch, int height, int width, const int *cat_table, int mode,
@@ -522,7 +439,7 @@ extern "C" int upsnet_pan_stable_colors(void *stream, const unsigned char *pred_
     UPS_REQUIRE(height > 0 && width > 0 && (long)height * width < (1L << 31), "pan_stable_colors: bad image size %d x %d", height, width);
     UPS_REQUIRE(mode == 0 || mode == 1, "pan_stable_colors: mode %d is neither 0 (PNG) nor 1 (picture)", mode);
     const long npix = (long)height * width;
-    const long threads = (npix + PT_RUN - 1) / PT_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     hipLaunchKernelGGL(pan_stable_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pred_2ch, rgb, npix,
                        (((uintptr_t)pred_2ch | (uintptr_t)rgb) & 15) == 0, cat_table, mode);
     UPS_CHECK_LAUNCH("pan_stable_kernel");

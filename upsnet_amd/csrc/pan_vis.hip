@@ -19,8 +19,8 @@
 // No floating point anywhere; every output byte is stored exactly once; two runs give the same bytes.
 //
 // Launches per image (all on `stream`, nothing synchronised, nothing allocated); flat is the compose launch alone:
-//   pan_moment_kernel   one pass over the pixels like pan_format.hip's pan_seg_kernel: 16 pixels per thread, run-length compressed (a
-//                       run ends with its key or its row); a run of l pixels from column x0 of row y adds l x0 + l (l - 1) / 2 to its
+//   pan_moment_kernel   the pixel pass of pan_pixels.h with the row walk, like pan_format.hip's pan_seg_kernel (a run ends with its
+//                       key or its row); a run of l pixels from column x0 of row y adds l x0 + l (l - 1) / 2 to its
 //                       key's sum of x and l y to its sum of y, in an LDS table per workgroup that falls back to the global 64-bit
 //                       atomics when it is full around a slot (a pixel-noise map stays exact); then one pair of global atomics per
 //                       distinct key and workgroup.
@@ -35,6 +35,7 @@
 #include "common.h"
 #include "upsnet_hip.h"
 #include "vis_font.h"
+#include "pan_pixels.h"
 
 #define PV_FLAT 0                 // `mode` of the entry point
 #define PV_OVERLAY 1
@@ -46,11 +47,8 @@
 #define PV_MAX_NAME 32
 #define PV_MAX_SIDE 32768
 #define PV_MAX_PIXELS (1L << 28)
-#define PV_RUN 16                 // pixels per thread in the moment pass
-#define PV_HASH_BITS 10
+#define PV_HASH_BITS 10           // the moment pass's LDS table: 1024 keys per workgroup, two 64-bit planes
 #define PV_HASH (1 << PV_HASH_BITS)
-#define PV_PROBES 16
-#define PV_EMPTY 0xffffffffu
 #define PV_TW 64
 #define PV_TH 32
 #define PV_PX 4                   // pixels per thread and row
@@ -81,45 +79,19 @@ static PvWs pv_ws(void *base)
     return w;
 }
 
-__device__ static inline unsigned pv_byte(const unsigned *w, const int j) { return (w[j >> 2] >> (8 * (j & 3))) & 255; }
-
-// 16 pixels x 3 bytes per thread: three 16-byte loads when the chunk is whole and the base aligned, else byte loads
-__device__ static inline void pv_load48(const unsigned char *__restrict__ src, const long p0, const long npix, const bool vec, unsigned w[12])
-{
-    if (vec && p0 + PV_RUN <= npix) {
-        const uint4 *v = (const uint4 *)(src + 3 * p0);
-        const uint4 a = v[0], b = v[1], c = v[2];
-        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-        w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-        w[8] = c.x; w[9] = c.y; w[10] = c.z; w[11] = c.w;
-    } else {
-        const long nb = 3 * (npix - p0);
-#pragma unroll
-        for (int j = 0; j < 12; ++j) w[j] = 0;
-#pragma unroll
-        for (int j = 0; j < 3 * PV_RUN; ++j)
-            if (j < nb) w[j >> 2] |= (unsigned)src[3 * p0 + j] << (8 * (j & 3));
-    }
-}
-
 // one run of `run` pixels of one key on row y from column x0
 __device__ static inline void pv_flush(unsigned *s_key, pv_u64 *s_sum, const PvWs &ws, const unsigned key, const int run, const int x0, const int y)
 {
     if ((key >> 8) == 255) return;   // VOID, whatever its instance
     const pv_u64 mx = (pv_u64)(run * x0 + run * (run - 1) / 2), my = (pv_u64)(run * y);
-    const unsigned h = (key * 2654435761u) >> (32 - PV_HASH_BITS);
-    for (int p = 0; p < PV_PROBES; ++p) {
-        const unsigned slot = (h + p) & (PV_HASH - 1);
-        unsigned k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k == PV_EMPTY) k = atomicCAS(&s_key[slot], PV_EMPTY, key);
-        if (k == PV_EMPTY || k == key) {
-            atomicAdd(&s_sum[slot], mx);
-            atomicAdd(&s_sum[PV_HASH + slot], my);
-            return;
-        }
+    const bool held = pan_lds_claim<PV_HASH_BITS>(s_key, key, [&](const unsigned slot) {
+        atomicAdd(&s_sum[slot], mx);
+        atomicAdd(&s_sum[PV_HASH + slot], my);
+    });
+    if (!held) {
+        atomicAdd(&ws.sx[key], mx);   // LDS table full around this slot (noise-like maps)
+        atomicAdd(&ws.sy[key], my);
     }
-    atomicAdd(&ws.sx[key], mx);   // LDS table full around this slot (noise-like maps)
-    atomicAdd(&ws.sy[key], my);
 }
 
 __global__ void __launch_bounds__(256)
@@ -127,42 +99,18 @@ pan_moment_kernel(const unsigned char *__restrict__ pred, const long npix, const
 {
     __shared__ unsigned s_key[PV_HASH];
     __shared__ pv_u64 s_sum[2 * PV_HASH];
-    const int t = threadIdx.x;
-    for (int i = t; i < PV_HASH; i += blockDim.x) s_key[i] = PV_EMPTY;
-    for (int i = t; i < 2 * PV_HASH; i += blockDim.x) s_sum[i] = 0;
+    pan_lds_clear<PV_HASH_BITS>(s_key, s_sum, 2);
     __syncthreads();
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PV_RUN;
-    if (p0 < npix) {
-        unsigned w[12];
-        pv_load48(pred, p0, npix, vec, w);
-        int x = (int)(p0 % width), y = (int)(p0 / width);
-        unsigned pk = 0;
-        int run = 0, x0 = 0, ry = 0;
-#pragma unroll
-        for (int i = 0; i < PV_RUN; ++i) {
-            if (p0 + i < npix) {
-                const unsigned k = pv_byte(w, 3 * i) << 8 | pv_byte(w, 3 * i + 1);
-                if (run == 0 || k != pk || x == 0) {   // a run shares its key and its row
-                    if (run) pv_flush(s_key, s_sum, ws, pk, run, x0, ry);
-                    pk = k;
-                    run = 0;
-                    x0 = x;
-                    ry = y;
-                }
-                ++run;
-                if (++x == width) { x = 0; ++y; }
-            }
-        }
-        if (run) pv_flush(s_key, s_sum, ws, pk, run, x0, ry);
-    }
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
+    if (p0 < npix)
+        pan_row_walk(pred, p0, npix, width, vec, [&](const unsigned key, const int run, const int x0, const int y) {
+            pv_flush(s_key, s_sum, ws, key, run, x0, y);
+        });
     __syncthreads();
-    for (int i = t; i < PV_HASH; i += blockDim.x) {
-        const unsigned k = s_key[i];
-        if (k != PV_EMPTY) {
-            atomicAdd(&ws.sx[k], s_sum[i]);
-            atomicAdd(&ws.sy[k], s_sum[PV_HASH + i]);
-        }
-    }
+    pan_lds_drain<PV_HASH_BITS>(s_key, [&](const unsigned k, const int i) {
+        atomicAdd(&ws.sx[k], s_sum[i]);
+        atomicAdd(&ws.sy[k], s_sum[PV_HASH + i]);
+    });
 }
 
 // table: upsnet_pan_format's (rows in ascending key). info[0] = segments of area >= min_area, info[1] = labels recorded.
@@ -264,7 +212,7 @@ pan_compose_kernel(const bool overlay, const unsigned char *__restrict__ pred, c
             }
 #pragma unroll
             for (int i = 0; i < PV_PX; ++i)
-                if (i < npx) k[i] = pv_byte(w, 3 * i) << 8 | pv_byte(w, 3 * i + 1);
+                if (i < npx) k[i] = pan_byte(w, 3 * i) << 8 | pan_byte(w, 3 * i + 1);
         }
 #pragma unroll
         for (int i = 0; i < PV_PX; ++i) s_key[(ly + 2) * PV_LW + PV_PX * (t & 15) + i + 2] = k[i];
@@ -351,8 +299,8 @@ pan_compose_kernel(const bool overlay, const unsigned char *__restrict__ pred, c
                 const bool edge = seg && (krow[i - PV_LW] != k || krow[i + PV_LW] != k || krow[i - 1] != k || krow[i + 1] != k);
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) {
-                    unsigned v = pv_byte(w, 3 * i + ch);
-                    if (seg) v = pv_half(v, pv_byte(c, 3 * i + ch));
+                    unsigned v = pan_byte(w, 3 * i + ch);
+                    if (seg) v = pv_half(v, pan_byte(c, 3 * i + ch));
                     if (edge) v = pv_half(v, 255u);
                     px[i][ch] = v;
                 }
@@ -434,7 +382,7 @@ extern "C" int upsnet_pan_vis(void *stream, int mode, const unsigned char *pred_
     const PvWs ws = pv_ws(workspace);
     if (overlay) {
         const long npix = (long)height * width;
-        const long threads = (npix + PV_RUN - 1) / PV_RUN;
+        const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
         hipLaunchKernelGGL(pan_moment_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, pred_2ch, npix, width,
                            ((uintptr_t)pred_2ch & 15) == 0, ws);
         UPS_CHECK_LAUNCH("pan_moment_kernel");

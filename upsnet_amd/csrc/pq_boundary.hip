@@ -17,8 +17,8 @@
 // cat << 8 | inst with every cat == 255 pixel one VOID label. Bit 0 = GT boundary, bit 1 = pred boundary; a map that is not given
 // leaves its bit 0.
 //
-// Counts: pqb_hist_kernel is pq_hist_kernel reading the bit map as well (run-length over (pred key, GT id, bits), the same LDS hash and
-// one global atomic per distinct cell and workgroup) into a SECOND count area that follows the first, so a cell index addresses both:
+// Counts: pqb_hist_kernel is pq_hist_kernel reading the bit map as well (the pair walk of pan_pixels.h with its third stream: runs
+// of equal (pred key, GT id, bits), the same LDS hash) into a SECOND count area that follows the first, so a cell index addresses both:
 //   area_bp [key] | void_b [key] | inter_b [row][inst] | area_bg [row]
 // pqb_match_kernel is pq_match_kernel with iou = min(iou_m, iou_b), iou_b = inter_b / (area_bp + area_bg - inter_b - void_b) (0 when
 // that union is empty); it clears both areas. FP absorption, FN and the summation order are pq_match_kernel's.
@@ -207,28 +207,12 @@ static inline PqbOff pqb_off(int max_gt)
 
 static size_t pqb_cnt_cells(int max_gt) { return (size_t)pqb_off(max_gt).abg + (size_t)((max_gt + 1) & ~1); }   // even: seg stays 8-aligned
 
+// Workspace (bytes): pq_ws with cnt[first area | second area] | (to 16 bytes) | uint8 bits[H*W] | uint8 rows[H*W]. Only the count cells
+// and nkeys must be zero between calls.
 static size_t pqb_tables_bytes(int max_gt)
 {
     const size_t b = pqb_cnt_cells(max_gt) * sizeof(int) + (size_t)max_gt * (sizeof(PqSeg) + sizeof(double)) + (256 + 2 + PQ_KEYS) * sizeof(int);
     return (b + 15) & ~(size_t)15;
-}
-
-// Workspace (bytes): int cnt[first area | second area] | PqSeg seg[max_gt] | double row_iou[max_gt] | int crowd_row[256] | int nkeys[2]
-// | int keys[PQ_KEYS] | (to 16 bytes) | uint8 bits[H*W] | uint8 rows[H*W]. Only the count cells and nkeys must be zero between calls.
-static PqWs pqb_ws(void *base, int max_gt)
-{
-    PqWs w;
-    char *p = (char *)base;
-    w.cnt = (int *)p;
-    p += pqb_cnt_cells(max_gt) * sizeof(int);
-    w.seg = (PqSeg *)p;
-    p += (size_t)max_gt * sizeof(PqSeg);
-    w.row_iou = (double *)p;
-    p += (size_t)max_gt * sizeof(double);
-    w.crowd_row = (int *)p;
-    w.nkeys = w.crowd_row + 256;
-    w.keys = w.nkeys + 2;
-    return w;
 }
 
 // one run of `run` pixels with the same pred key, GT id and boundary bits b (bit 0 GT, bit 1 pred)
@@ -264,49 +248,16 @@ pqb_hist_kernel(const unsigned char *__restrict__ pred, const unsigned char *__r
     int *s_id = (int *)(s_hist + 2 * PQ_HASH);
     unsigned char *s_cat = (unsigned char *)(s_id + n);
     const int t = threadIdx.x;
-    for (int i = t; i < PQ_HASH; i += blockDim.x) { s_key[i] = PQ_EMPTY; s_val[i] = 0; }
+    pan_lds_clear<PQ_HASH_BITS>(s_key, s_val, 1);
     for (int i = t; i < n; i += blockDim.x) { s_id[i] = ws.seg[i].id; s_cat[i] = (unsigned char)ws.seg[i].cat; }
     __syncthreads();
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PQ_RUN;
-    if (p0 < npix) {
-        unsigned pw[12], gw[12], bw[4];
-        pq_load48(pred, p0, npix, vec, pw);
-        pq_load48(gt, p0, npix, vec, gw);
-        if (p0 + PQ_RUN <= npix) {                               // (bits starts 16-byte aligned in the workspace)
-            const uint4 v = *(const uint4 *)(bits + p0);
-            bw[0] = v.x; bw[1] = v.y; bw[2] = v.z; bw[3] = v.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bw[j] = 0;
-#pragma unroll
-            for (int j = 0; j < PQ_RUN; ++j)
-                if (p0 + j < npix) bw[j >> 2] |= (unsigned)bits[p0 + j] << (8 * (j & 3));
-        }
-        unsigned pk = 0, bb = 0;
-        int gid = -1, run = 0;
-#pragma unroll
-        for (int i = 0; i < PQ_RUN; ++i) {
-            if (p0 + i < npix) {
-                const unsigned k = pq_byte(pw, 3 * i) << 8 | pq_byte(pw, 3 * i + 1);
-                const int g = (int)(pq_byte(gw, 3 * i) | pq_byte(gw, 3 * i + 1) << 8 | pq_byte(gw, 3 * i + 2) << 16);
-                const unsigned b = pq_byte(bw, i) & 3;
-                if (k != pk || g != gid || b != bb) {
-                    if (run) pqb_flush(s_key, s_val, ws, s_id, s_cat, n, o, pk, gid, bb, run);
-                    pk = k;
-                    gid = g;
-                    bb = b;
-                    run = 0;
-                }
-                ++run;
-            }
-        }
-        if (run) pqb_flush(s_key, s_val, ws, s_id, s_cat, n, o, pk, gid, bb, run);
-    }
+    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PAN_RUN;
+    if (p0 < npix)   // (bits starts 16-byte aligned in the workspace)
+        pan_pair_walk<true>(pred, gt, bits, p0, npix, vec, [&](const unsigned pk, const int gid, const unsigned bb, const int run) {
+            pqb_flush(s_key, s_val, ws, s_id, s_cat, n, o, pk, gid, bb, run);
+        });
     __syncthreads();
-    for (int i = t; i < PQ_HASH; i += blockDim.x) {
-        const unsigned k = s_key[i];
-        if (k != PQ_EMPTY) pq_global_add(ws, k, s_val[i]);
-    }
+    pan_lds_drain<PQ_HASH_BITS>(s_key, [&](const unsigned k, const int i) { pq_global_add(ws, k, s_val[i]); });
 }
 
 // min(mask iou, boundary iou) of GT row g with pred instance inst of its category; both in float64 from integer counts
@@ -444,7 +395,7 @@ extern "C" int upsnet_pq_boundary_accumulate(void *stream, int dilation, const u
     UPS_REQUIRE(image_index >= 0 && image_index < (1 << 24), "pq_boundary_accumulate: image index %d outside 0..2^24-1", image_index);
     UPS_REQUIRE(((uintptr_t)workspace & 15) == 0, "pq_boundary_accumulate: workspace not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const PqWs ws = pqb_ws(workspace, max_gt);
+    const PqWs ws = pq_ws(workspace, pqb_cnt_cells(max_gt), max_gt);
     const PqbOff o = pqb_off(max_gt);
     const int n = num_segments;
     const long npix = (long)height * width;
@@ -454,7 +405,7 @@ extern "C" int upsnet_pq_boundary_accumulate(void *stream, int dilation, const u
     hipLaunchKernelGGL(pq_prep_kernel, dim3(1), dim3(1024), (size_t)n * 2 * sizeof(int), st, segments, n, ws);
     UPS_CHECK_LAUNCH("pq_prep_kernel");
     const bool vec = (((uintptr_t)pred_2ch | (uintptr_t)gt_rgb) & 15) == 0;
-    const long threads = (npix + PQ_RUN - 1) / PQ_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const size_t lds = (size_t)PQ_HASH * 2 * sizeof(int) + (size_t)n * (sizeof(int) + 1);
     hipLaunchKernelGGL(pqb_hist_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), lds, st, pred_2ch, gt_rgb, bits, npix, vec, n, o,
                        ws);

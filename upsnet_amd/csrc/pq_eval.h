@@ -1,24 +1,22 @@
-// pq_eval.h -- the workspace layout and the device helpers that pq_eval.hip and pq_boundary.hip share: the count cells, the LDS hash
-// of the pixel pass (one global atomic per distinct cell and workgroup), the 16-pixel loads and the mask IoU of a pair.
+// pq_eval.h -- what pq_eval.hip and pq_boundary.hip share (and video_eval.hip / mots_eval.hip borrow: the limits and pq_find): the
+// workspace layout, the count cells behind the pixel pass of pan_pixels.h, the GT preparation kernel and the mask IoU of a pair.
 #pragma once
 #include "common.h"
+#include "pan_pixels.h"
 
 #define PQ_KEYS 65536            // pred keys (cat << 8 | inst); cat 255 = VOID never counted
 #define PQ_VOID_OFF PQ_KEYS      // inter(GT VOID, pred key)
 #define PQ_JOINT_OFF (2 * PQ_KEYS)
 #define PQ_MAX_GT 4096
-#define PQ_RUN 16                // pixels per thread in the pixel passes
-#define PQ_HASH_BITS 11
+#define PQ_HASH_BITS 11          // the pixel pass's LDS table: 2048 cells per workgroup
 #define PQ_HASH (1 << PQ_HASH_BITS)
-#define PQ_PROBES 16
-#define PQ_EMPTY 0xffffffffu
 
 struct PqSeg {
     int id, cat, crowd, pad;
     long long area;              // the JSON area (not recounted, as in the reference)
 };
 
-// Workspace layout (bytes): int cnt[2 * PQ_KEYS + max_gt * 256] | PqSeg seg[max_gt] | double row_iou[max_gt] | int crowd_row[256]
+// Workspace layout (bytes): int cnt[cnt_cells] (pq_cnt_cells(max_gt) = 2 * PQ_KEYS + max_gt * 256; Boundary PQ appends a second area) | PqSeg seg[max_gt] | double row_iou[max_gt] | int crowd_row[256]
 // | int nkeys[2] | int keys[PQ_KEYS] (the image's pred keys with a non-zero area, in arrival order)
 struct PqWs {
     int *cnt;
@@ -29,14 +27,14 @@ struct PqWs {
     int *keys;
 };
 
-static inline size_t pq_cnt_bytes(int max_gt) { return ((size_t)2 * PQ_KEYS + (size_t)max_gt * 256) * sizeof(int); }
+static inline size_t pq_cnt_cells(int max_gt) { return (size_t)2 * PQ_KEYS + (size_t)max_gt * 256; }
 
-static inline PqWs pq_ws(void *base, int max_gt)
+static inline PqWs pq_ws(void *base, size_t cnt_cells, int max_gt)
 {
     PqWs w;
     char *p = (char *)base;
     w.cnt = (int *)p;
-    p += pq_cnt_bytes(max_gt);
+    p += cnt_cells * sizeof(int);
     w.seg = (PqSeg *)p;
     p += (size_t)max_gt * sizeof(PqSeg);
     w.row_iou = (double *)p;
@@ -93,17 +91,7 @@ __device__ static inline void pq_global_add(const PqWs &ws, const unsigned cell,
 
 __device__ static inline void pq_add(unsigned *s_key, int *s_val, const PqWs &ws, const unsigned cell, const int v)
 {
-    const unsigned h = (cell * 2654435761u) >> (32 - PQ_HASH_BITS);
-    for (int p = 0; p < PQ_PROBES; ++p) {
-        const unsigned slot = (h + p) & (PQ_HASH - 1);
-        unsigned k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k == PQ_EMPTY) k = atomicCAS(&s_key[slot], PQ_EMPTY, cell);
-        if (k == PQ_EMPTY || k == cell) {
-            atomicAdd(&s_val[slot], v);
-            return;
-        }
-    }
-    pq_global_add(ws, cell, v);   // LDS table full around this slot (noise-like maps): straight to the global count
+    if (!pan_lds_count<PQ_HASH_BITS>(s_key, s_val, cell, v)) pq_global_add(ws, cell, v);   // LDS table full around this slot
 }
 
 __device__ static inline int pq_find(const int *s_id, const int n, const int id)
@@ -131,27 +119,6 @@ __device__ static inline void pq_flush(unsigned *s_key, int *s_val, const PqWs &
     } else {
         const int g = pq_find(s_id, n, gid);                     // ids not in segments_info take part in nothing
         if (g >= 0 && s_cat[g] == cat) pq_add(s_key, s_val, ws, PQ_JOINT_OFF + (unsigned)g * 256 + (pk & 255), run);
-    }
-}
-
-__device__ static inline unsigned pq_byte(const unsigned *w, const int j) { return (w[j >> 2] >> (8 * (j & 3))) & 255; }
-
-// 16 pixels x 3 bytes = 48 bytes per thread: three 16-byte loads when the chunk is whole and the base aligned, else byte loads
-__device__ static inline void pq_load48(const unsigned char *__restrict__ src, const long p0, const long npix, const bool vec, unsigned w[12])
-{
-    if (vec && p0 + PQ_RUN <= npix) {
-        const uint4 *v = (const uint4 *)(src + 3 * p0);
-        const uint4 a = v[0], b = v[1], c = v[2];
-        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-        w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-        w[8] = c.x; w[9] = c.y; w[10] = c.z; w[11] = c.w;
-    } else {
-        const long nb = 3 * (npix - p0);
-#pragma unroll
-        for (int j = 0; j < 12; ++j) w[j] = 0;
-#pragma unroll
-        for (int j = 0; j < 3 * PQ_RUN; ++j)
-            if (j < nb) w[j >> 2] |= (unsigned)src[3 * p0 + j] << (8 * (j & 3));
     }
 }
 

@@ -7,8 +7,8 @@
 // over dicts. Here, integers only, three launches per image and a workspace sized once from max_gt:
 //   pq_prep_kernel   one workgroup: the image's GT segments (JSON order) sorted by id (rank counting), and per category the row
 //                    of its LAST crowd segment in JSON order (the reference's crowd_labels_dict is overwritten)
-//   pq_hist_kernel   one pass over the pixels: per-thread run-length compression of (pred key, gt id), an LDS hash table per
-//                    workgroup, one global atomic per distinct cell and workgroup (a full hash falls back to a global atomic);
+//   pq_hist_kernel   the pixel pass of pan_pixels.h over (pred key, gt id): runs counted into an LDS hash table per workgroup,
+//                    one global atomic per distinct cell and workgroup (a full hash falls back to a global atomic);
 //                    cells: pred area [key], inter(VOID, pred) [key], inter(gt row, pred) [row][inst] for equal categories only
 //                    (the first arrival at a pred area cell appends the key to a list of the image's pred segments)
 //   pq_match_kernel  one workgroup: matching (iou > 0.5 in float64), FP with VOID + crowd absorption over the listed pred segments,
@@ -31,37 +31,16 @@ pq_hist_kernel(const unsigned char *__restrict__ pred, const unsigned char *__re
     int *s_id = (int *)(s_hist + 2 * PQ_HASH);
     unsigned char *s_cat = (unsigned char *)(s_id + n);
     const int t = threadIdx.x;
-    for (int i = t; i < PQ_HASH; i += blockDim.x) { s_key[i] = PQ_EMPTY; s_val[i] = 0; }
+    pan_lds_clear<PQ_HASH_BITS>(s_key, s_val, 1);
     for (int i = t; i < n; i += blockDim.x) { s_id[i] = ws.seg[i].id; s_cat[i] = (unsigned char)ws.seg[i].cat; }
     __syncthreads();
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PQ_RUN;
-    if (p0 < npix) {
-        unsigned pw[12], gw[12];
-        pq_load48(pred, p0, npix, vec, pw);
-        pq_load48(gt, p0, npix, vec, gw);
-        unsigned pk = 0;
-        int gid = -1, run = 0;
-#pragma unroll
-        for (int i = 0; i < PQ_RUN; ++i) {
-            if (p0 + i < npix) {
-                const unsigned k = pq_byte(pw, 3 * i) << 8 | pq_byte(pw, 3 * i + 1);
-                const int g = (int)(pq_byte(gw, 3 * i) | pq_byte(gw, 3 * i + 1) << 8 | pq_byte(gw, 3 * i + 2) << 16);
-                if (k != pk || g != gid) {
-                    if (run) pq_flush(s_key, s_val, ws, s_id, s_cat, n, pk, gid, run);
-                    pk = k;
-                    gid = g;
-                    run = 0;
-                }
-                ++run;
-            }
-        }
-        if (run) pq_flush(s_key, s_val, ws, s_id, s_cat, n, pk, gid, run);
-    }
+    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PAN_RUN;
+    if (p0 < npix)
+        pan_pair_walk<false>(pred, gt, nullptr, p0, npix, vec, [&](const unsigned pk, const int gid, unsigned, const int run) {
+            pq_flush(s_key, s_val, ws, s_id, s_cat, n, pk, gid, run);
+        });
     __syncthreads();
-    for (int i = t; i < PQ_HASH; i += blockDim.x) {
-        const unsigned k = s_key[i];
-        if (k != PQ_EMPTY) pq_global_add(ws, k, s_val[i]);
-    }
+    pan_lds_drain<PQ_HASH_BITS>(s_key, [&](const unsigned k, const int i) { pq_global_add(ws, k, s_val[i]); });
 }
 
 __global__ void __launch_bounds__(PQM_T)
@@ -166,7 +145,7 @@ pq_match_kernel(const int n, const unsigned char *__restrict__ cat_known, const 
 extern "C" size_t upsnet_pq_workspace_bytes(int max_gt)
 {
     if (max_gt < 0 || max_gt > PQ_MAX_GT) return 0;
-    return pq_cnt_bytes(max_gt) + (size_t)max_gt * (sizeof(PqSeg) + sizeof(double)) + (256 + 2 + PQ_KEYS) * sizeof(int);
+    return pq_cnt_cells(max_gt) * sizeof(int) + (size_t)max_gt * (sizeof(PqSeg) + sizeof(double)) + (256 + 2 + PQ_KEYS) * sizeof(int);
 }
 
 extern "C" int upsnet_pq_accumulate(void *stream, const unsigned char *pred_2ch, const unsigned char *gt_rgb, int height, int width,
@@ -181,13 +160,13 @@ extern "C" int upsnet_pq_accumulate(void *stream, const unsigned char *pred_2ch,
     UPS_REQUIRE(image_index >= 0 && image_index < (1 << 24), "pq_accumulate: image index %d outside 0..2^24-1", image_index);
     UPS_REQUIRE(((uintptr_t)workspace & 7) == 0, "pq_accumulate: workspace not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const PqWs ws = pq_ws(workspace, max_gt);
+    const PqWs ws = pq_ws(workspace, pq_cnt_cells(max_gt), max_gt);
     const int n = num_segments;
     const long npix = (long)height * width;
     hipLaunchKernelGGL(pq_prep_kernel, dim3(1), dim3(1024), (size_t)n * 2 * sizeof(int), st, segments, n, ws);   // n == 0: crowd rows reset
     UPS_CHECK_LAUNCH("pq_prep_kernel");
     const bool vec = (((uintptr_t)pred_2ch | (uintptr_t)gt_rgb) & 15) == 0;
-    const long threads = (npix + PQ_RUN - 1) / PQ_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const size_t lds = (size_t)PQ_HASH * 2 * sizeof(int) + (size_t)n * (sizeof(int) + 1);
     hipLaunchKernelGGL(pq_hist_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), lds, st, pred_2ch, gt_rgb, npix, vec, n, ws);
     UPS_CHECK_LAUNCH("pq_hist_kernel");
@@ -215,10 +194,10 @@ confusion_kernel(const unsigned char *__restrict__ gt, const unsigned char *__re
         for (int i = t; i < cells; i += blockDim.x) s_cm[i] = 0;
         __syncthreads();
     }
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PQ_RUN;
+    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PAN_RUN;
     if (p0 < npix) {
         unsigned gw[4], pw[4];
-        if (vec && p0 + PQ_RUN <= npix) {
+        if (vec && p0 + PAN_RUN <= npix) {
             const uint4 a = *(const uint4 *)(gt + p0), b = *(const uint4 *)(pred + p0);
             gw[0] = a.x; gw[1] = a.y; gw[2] = a.z; gw[3] = a.w;
             pw[0] = b.x; pw[1] = b.y; pw[2] = b.z; pw[3] = b.w;
@@ -226,7 +205,7 @@ confusion_kernel(const unsigned char *__restrict__ gt, const unsigned char *__re
 #pragma unroll
             for (int j = 0; j < 4; ++j) gw[j] = pw[j] = 0;
 #pragma unroll
-            for (int j = 0; j < PQ_RUN; ++j)
+            for (int j = 0; j < PAN_RUN; ++j)
                 if (p0 + j < npix) {
                     gw[j >> 2] |= (unsigned)gt[p0 + j] << (8 * (j & 3));
                     pw[j >> 2] |= (unsigned)pred[p0 + j] << (8 * (j & 3));
@@ -239,9 +218,9 @@ confusion_kernel(const unsigned char *__restrict__ gt, const unsigned char *__re
         else atomicAdd(&out[key], (unsigned long long)run);                 \
     }
 #pragma unroll
-        for (int i = 0; i < PQ_RUN; ++i) {
+        for (int i = 0; i < PAN_RUN; ++i) {
             if (p0 + i < npix) {
-                const int g = (int)pq_byte(gw, i), p = (int)pq_byte(pw, i);
+                const int g = (int)pan_byte(gw, i), p = (int)pan_byte(pw, i);
                 const int k = g == ignore ? -1 : g * C + p;
                 if (k != key) { CM_FLUSH() key = k; run = 0; }
                 ++run;
@@ -270,7 +249,7 @@ extern "C" int upsnet_confusion_accumulate(void *stream, const unsigned char *gt
     const int cells = class_num * class_num;
     const bool use_lds = cells <= CM_LDS_MAX_CELLS;
     const bool vec = (((uintptr_t)gt_label | (uintptr_t)pred_label) & 15) == 0;
-    const long threads = (npix + PQ_RUN - 1) / PQ_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     hipLaunchKernelGGL(confusion_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), use_lds ? (size_t)cells * sizeof(int) : 0,
                        (hipStream_t)stream, gt_label, pred_label, npix, class_num, ignore_label, vec, use_lds,
                        (unsigned long long *)confusion);

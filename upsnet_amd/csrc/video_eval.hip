@@ -9,11 +9,11 @@
 //   AREA_G row               pixels of the GT row (under any prediction, VOID included)
 // VPQ reads the same-category JOINT cells, STQ's association the thing x thing ones, the confusion matrix is the JOINT cells summed by
 // (cat(row), cat(key)) plus AREA_G - sum for pred VOID, and the pred pixels on thing-crowd GT are the JOINT cells of those rows.
-// A dense joint table would be 4096 x 65536 ints, so all cells live in open-addressing hash tables in global memory (32-bit cell + 1
-// claimed by atomicCAS, 0 = empty; count by atomicAdd; the claimer appends the slot to a list, so nothing ever scans a table).
+// A dense joint table would be 4096 x 65536 ints, so all cells live in the global cell tables of pan_pixels.h (open addressing, the
+// claimer of a slot appends it to a list, so nothing ever scans a table).
 // Per frame, three launches:
-//   ve_hist_kernel     ONE pass over the pixels, whatever `windows` is: 16 pixels per thread (pq_eval.h's loads), run-length compressed,
-//                      pre-aggregated in an LDS hash per workgroup, one global atomic per distinct cell and workgroup
+//   ve_hist_kernel     ONE pass over the pixels, whatever `windows` is: the pixel pass of pan_pixels.h (pair walk, LDS hash per
+//                      workgroup, one global atomic per distinct cell and workgroup)
 //   ve_compact_kernel  the frame's touched slots -> the frame's (cell, count) list in a ring of the last max_window frames, and added
 //                      into the sequence-level table; the frame table is left zero; unknown pred categories are reported
 //   ve_window_kernel   one workgroup per window length n whose window ends at this frame: the n lists are sorted by cell in LDS
@@ -23,7 +23,7 @@
 // and per sequence two more (ve_seq_kernel, ve_reset_kernel): the sequence-level cells are delivered as one (cell, count) list that
 // travels to the host by one asynchronous copy -- STQ's few float64 operations run there, from integers -- and every part of the
 // workspace is zero again. Nothing between the first frame and the end of a sequence waits for the host.
-// A table that is full (VE_PROBES slots in a row taken) or a window of more than VE_SORT list entries never loses a count silently: a
+// A table that is full (PAN_TABLE_PROBES slots in a row taken) or a window of more than VE_SORT list entries never loses a count silently: a
 // bit of status[0] is set and the host raises RuntimeError at its next synchronisation.
 #include "common.h"
 #include "upsnet_hip.h"
@@ -35,7 +35,6 @@
 #define VE_VOID 2u
 #define VE_AREA_G 3u
 #define VE_KIND(k) ((unsigned)(k) << 28)
-#define VE_PROBES 256
 #define VE_SEQ_BITS 15                    // sequence-level table: 32768 slots
 #define VE_SEQ_SLOTS (1 << VE_SEQ_BITS)
 #define VE_SORT 8192                      // list entries one window pass can merge (64 KiB of LDS keys)
@@ -59,19 +58,12 @@ struct VeWs {
     int fbits;      // log2 of the frame table's slots
 };
 
-static inline int ve_frame_bits(long npix)
-{
-    int b = 12;
-    while (b < 20 && (1L << b) < npix / 16) ++b;
-    return b;
-}
-
 static inline size_t ve_ws_ints(int bits, int K) { return 32 + 3 * ((size_t)1 << bits) + 3 * (size_t)VE_SEQ_SLOTS + (size_t)K * 2 * ((size_t)1 << bits); }
 
 static inline VeWs ve_ws(void *base, int max_gt, long npix, int K)
 {
     VeWs w;
-    w.fbits = ve_frame_bits(npix);
+    w.fbits = pan_frame_bits(npix);
     const size_t HC = (size_t)1 << w.fbits;
     int *p = (int *)base;
     w.hdr = p;
@@ -90,43 +82,11 @@ static inline VeWs ve_ws(void *base, int max_gt, long npix, int K)
     return w;
 }
 
-// count v > 0 of one cell into an open-addressing table of 1 << bits slots; the thread that claims a slot appends it to `slots`
-__device__ static inline void ve_table_add(unsigned *__restrict__ tab, const int bits, int *__restrict__ slots, int *counter,
-                                           unsigned long long *status, const unsigned long long full_bit, const unsigned cell, const unsigned v)
-{
-    const unsigned mask = (1u << bits) - 1, want = cell + 1;
-    unsigned slot = (cell * 2654435761u) >> (32 - bits);
-    for (int p = 0; p < VE_PROBES; ++p, slot = (slot + 1) & mask) {
-        unsigned k = __hip_atomic_load(&tab[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == 0) {
-            k = atomicCAS(&tab[2 * slot], 0u, want);
-            if (k == 0) {
-                const int pos = atomicAdd(counter, 1);
-                if (pos >= 0 && pos <= (int)mask) slots[pos] = (int)slot;   // one append per slot: always true for a zeroed workspace
-                k = want;
-            }
-        }
-        if (k == want) {
-            atomicAdd(&tab[2 * slot + 1], v);
-            return;
-        }
-    }
-    atomicOr(status, full_bit);   // never silently: the host raises at its next synchronisation
-}
-
+// count v > 0 of one cell of the frame: the workgroup's LDS table, or the frame table when that is full around the cell's slot
 __device__ static inline void ve_lds_add(unsigned *s_key, int *s_val, const VeWs &ws, unsigned long long *status, const unsigned cell, const int v)
 {
-    const unsigned h = (cell * 2654435761u) >> (32 - PQ_HASH_BITS);
-    for (int p = 0; p < PQ_PROBES; ++p) {
-        const unsigned slot = (h + p) & (PQ_HASH - 1);
-        unsigned k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k == PQ_EMPTY) k = atomicCAS(&s_key[slot], PQ_EMPTY, cell);
-        if (k == PQ_EMPTY || k == cell) {
-            atomicAdd(&s_val[slot], v);
-            return;
-        }
-    }
-    ve_table_add(ws.ftab, ws.fbits, ws.fslots, &ws.hdr[0], status, VE_FULL_FRAME, cell, (unsigned)v);   // LDS table full around this slot
+    if (!pan_lds_count<PQ_HASH_BITS>(s_key, s_val, cell, v))
+        pan_table_add(ws.ftab, ws.fbits, ws.fslots, &ws.hdr[0], status, VE_FULL_FRAME, cell, (unsigned)v);
 }
 
 // one run of `run` pixels with the same pred key and GT id
@@ -155,37 +115,18 @@ ve_hist_kernel(const unsigned char *__restrict__ pred, const unsigned char *__re
     int *s_val = (int *)(s_hist + PQ_HASH);
     int *s_id = (int *)(s_hist + 2 * PQ_HASH);
     const int t = threadIdx.x;
-    for (int i = t; i < PQ_HASH; i += blockDim.x) { s_key[i] = PQ_EMPTY; s_val[i] = 0; }
+    pan_lds_clear<PQ_HASH_BITS>(s_key, s_val, 1);
     for (int i = t; i < n; i += blockDim.x) s_id[i] = table[2 * i];
     __syncthreads();
-    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PQ_RUN;
-    if (p0 < npix) {
-        unsigned pw[12], gw[12];
-        pq_load48(pred, p0, npix, vec, pw);
-        pq_load48(gt, p0, npix, vec, gw);
-        unsigned pk = 0;
-        int gid = -1, run = 0;
-#pragma unroll
-        for (int i = 0; i < PQ_RUN; ++i) {
-            if (p0 + i < npix) {
-                const unsigned k = pq_byte(pw, 3 * i) << 8 | pq_byte(pw, 3 * i + 1);
-                const int g = (int)(pq_byte(gw, 3 * i) | pq_byte(gw, 3 * i + 1) << 8 | pq_byte(gw, 3 * i + 2) << 16);
-                if (k != pk || g != gid) {
-                    if (run) ve_flush(s_key, s_val, ws, status, s_id, n, pk, gid, run);
-                    pk = k;
-                    gid = g;
-                    run = 0;
-                }
-                ++run;
-            }
-        }
-        if (run) ve_flush(s_key, s_val, ws, status, s_id, n, pk, gid, run);
-    }
+    const long p0 = ((long)blockIdx.x * blockDim.x + t) * PAN_RUN;
+    if (p0 < npix)
+        pan_pair_walk<false>(pred, gt, nullptr, p0, npix, vec, [&](const unsigned pk, const int gid, unsigned, const int run) {
+            ve_flush(s_key, s_val, ws, status, s_id, n, pk, gid, run);
+        });
     __syncthreads();
-    for (int i = t; i < PQ_HASH; i += blockDim.x) {
-        const unsigned k = s_key[i];
-        if (k != PQ_EMPTY) ve_table_add(ws.ftab, ws.fbits, ws.fslots, &ws.hdr[0], status, VE_FULL_FRAME, k, (unsigned)s_val[i]);
-    }
+    pan_lds_drain<PQ_HASH_BITS>(s_key, [&](const unsigned k, const int i) {
+        pan_table_add(ws.ftab, ws.fbits, ws.fslots, &ws.hdr[0], status, VE_FULL_FRAME, k, (unsigned)s_val[i]);
+    });
 }
 
 // the frame's touched slots -> ring list `slotk` and the sequence table; the frame table and its slot list are zero afterwards
@@ -209,7 +150,7 @@ ve_compact_kernel(VeWs ws, const int slotk, const unsigned char *__restrict__ ca
         const unsigned cell = k - 1;
         if (cell >> 28 == VE_AREA_P && !cat_known[(cell >> 8) & 255])
             atomicMin(status + 1, (unsigned long long)(where | (long long)((cell >> 8) & 255)));   // the first frame, its lowest category
-        ve_table_add(ws.stab, VE_SEQ_BITS, ws.sslots, &ws.hdr[1], status, VE_FULL_SEQ, cell, v);
+        pan_table_add(ws.stab, VE_SEQ_BITS, ws.sslots, &ws.hdr[1], status, VE_FULL_SEQ, cell, v);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         ws.ring_n[slotk] = n;
@@ -389,7 +330,7 @@ extern "C" size_t upsnet_video_eval_workspace_bytes(int max_gt, int height, int 
     if (max_gt < 0 || max_gt > PQ_MAX_GT || height <= 0 || width <= 0 || (long)height * width > (1L << 24) || max_window < 1 ||
         max_window > VE_MAX_WINDOW)
         return 0;
-    return ve_ws_ints(ve_frame_bits((long)height * width), max_window) * sizeof(int);
+    return ve_ws_ints(pan_frame_bits((long)height * width), max_window) * sizeof(int);
 }
 
 extern "C" size_t upsnet_video_eval_sequence_ints(void) { return 2 + 2 * (size_t)VE_SEQ_SLOTS; }
@@ -422,7 +363,7 @@ extern "C" int upsnet_video_eval_frame(void *stream, const unsigned char *pred_2
     const VeWs ws = ve_ws(workspace, max_gt, npix, max_window);
     unsigned long long *stat = (unsigned long long *)status;
     const bool vec = (((uintptr_t)pred_2ch | (uintptr_t)gt_rgb) & 15) == 0;
-    const long threads = (npix + PQ_RUN - 1) / PQ_RUN;
+    const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     hipLaunchKernelGGL(ve_hist_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), (size_t)(2 * PQ_HASH + num_rows) * sizeof(int), st,
                        pred_2ch, gt_rgb, npix, vec, table, num_rows, ws, stat);
     UPS_CHECK_LAUNCH("ve_hist_kernel");
