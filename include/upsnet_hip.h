@@ -1224,6 +1224,36 @@ size_t upsnet_pan_components_workspace_bytes(int height, int width);
 int upsnet_pan_components(void *stream, const unsigned char *pan_2ch, int height, int width, int connectivity, int min_area,
                           int keep_largest, void *workspace, unsigned char *out_2ch, int *labels, int *stats);
 
+/* The absorbing mode of the same cleaning: a removed component takes the (category, instance) of the kept segment
+ * it shares the longest border with and becomes VOID only where it has no such border. The rule is this project's own
+ * (csrc/pan_components.hip, restated twice in tests/pan_absorb_ref.py):
+ *   - keys, VOID, components, labels, areas, main components and which components are removed: exactly as upsnet_pan_components on
+ *     the same arguments. A removed component is a FRAGMENT; every other component is KEPT;
+ *   - votes: for every pixel p of a fragment r and every one of the four EDGE neighbours q of p inside the image (edge neighbours
+ *     whatever `connectivity` is: border length is an edge notion): if q is not VOID and belongs to a kept component, the key of q
+ *     gets one vote from r. One vote per pixel edge. VOID pixels, pixels outside the image and pixels of other fragments give none;
+ *   - the donor of r is the key with the most votes, ties to the smaller key; no votes, no donor;
+ *   - a fragment pixel with a donor becomes (donor category, donor instance, byte 2); one without becomes (255, 0, byte 2); every
+ *     other pixel keeps its bytes;
+ *   - a single round: a fragment that touches only other fragments, VOID or the image border, or kept pixels only across a corner,
+ *     becomes VOID. Nothing is iterated.
+ * Consequences: min_area == 0 is the identity; the result is a fixed point (an absorbed fragment is edge-adjacent to a kept pixel of
+ * its new key and joins that kept component, so a second application removes nothing); the result differs from
+ * upsnet_pan_components' exactly on the absorbed pixels.
+ * out_2ch may be pan_2ch itself; labels (may be NULL) are those of the INPUT map. stats: int32 [8] = [0..3] as upsnet_pan_components
+ * (distinct keys, components, fragments, fragment pixels), [4] fragments absorbed, [5] pixels absorbed, [6] distinct (fragment, donor
+ * key) pairs that received a vote, [7] vote table overflow (0 or 1).
+ * workspace: upsnet_pan_absorb_workspace_bytes(H, W) bytes, 16-byte aligned: that of upsnet_pan_components, one 64-bit winner cell per
+ * pixel index, and the vote table of 2 H W slots (a 64-bit key and a 32-bit count each). A (fragment, key) pair needs a grid edge
+ * between a fragment pixel and a kept pixel, and a map has 2HW - H - W edges: there are always fewer pairs than slots, so an insertion
+ * cannot fail and stats[7] is 0. Should it ever be 1, out_2ch is a copy of pan_2ch and stats[2..5] are 0: the map is never silently
+ * wrong. The workspace's contents on entry are ARBITRARY and nothing depends on an earlier call. Eight launches, nothing is
+ * synchronised or allocated. Refused before any launch, as upsnet_pan_components refuses it: a null pointer, H * W outside 1..2^24 (the
+ * workspace size is then 0), connectivity other than 4 or 8, min_area < 0, a misaligned buffer. */
+size_t upsnet_pan_absorb_workspace_bytes(int height, int width);
+int upsnet_pan_absorb(void *stream, const unsigned char *pan_2ch, int height, int width, int connectivity, int min_area, int keep_largest,
+                      void *workspace, unsigned char *out_2ch, int *labels, int *stats);
+
 /* ============================== Video metrics of tracked sequences: VPQ and STQ ============================== */
 
 /* Video Panoptic Quality (Kim et al., Video Panoptic Segmentation, CVPR 2020) and Segmentation and Tracking Quality (Weber et al.,

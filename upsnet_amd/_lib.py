@@ -192,6 +192,8 @@ _SIGNATURES = {
     "upsnet_pan_stable_colors": (c_int, [P, P, c_int, c_int, P, c_int, P]),
     "upsnet_pan_components_workspace_bytes": (c_size_t, [c_int, c_int]),
     "upsnet_pan_components": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "upsnet_pan_absorb_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "upsnet_pan_absorb": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
     "upsnet_video_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "upsnet_video_eval_sequence_ints": (c_size_t, []),
     "upsnet_video_eval_frame": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),

@@ -107,6 +107,9 @@ config.test.soft_nms_score_thresh = 0.0001
 config.test.pan_min_component = 0
 config.test.pan_component_connectivity = 8
 config.test.pan_component_keep_largest = True
+# 'void': such a component becomes VOID; 'absorb' (DESIGN 4.27): it takes the (category, instance) of the kept segment it shares the
+# longest border with, and becomes VOID only where it borders none
+config.test.pan_component_mode = 'void'
 
 
 def _merge(dst, src):

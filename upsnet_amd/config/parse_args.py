@@ -14,10 +14,14 @@ def add_pan_component_arguments(parser, before):
                         'component of a pair always stays (test.pan_component_keep_largest); 0 = off' % before)
     parser.add_argument('--pan_component_connectivity', type=int, default=None, metavar='{4,8}',
                         help='with --pan_min_component: sets config.test.pan_component_connectivity, 4 or 8 (default 8)')
+    parser.add_argument('--pan_component_mode', default=None, metavar='{void,absorb}',
+                        help='with --pan_min_component: sets config.test.pan_component_mode. void (default): such a component becomes '
+                        'VOID; absorb: it takes the (category, instance) of the segment it shares the longest border with, and becomes '
+                        'VOID only where it borders none')
 
 
 def apply_pan_component_arguments(args, fail):
-    """The two options into config.test, once the yaml is merged; then the resulting values are checked, whichever of the two set them.
+    """The three options into config.test, once the yaml is merged; then the resulting values are checked, whichever of the two set them.
     fail(message) ends the run (parser.error, or a SystemExit): every message names the option or the yaml key."""
     if args.pan_min_component is not None:
         if args.pan_min_component < 0:
@@ -29,6 +33,12 @@ def apply_pan_component_arguments(args, fail):
         if args.pan_component_connectivity not in (4, 8):
             fail('--pan_component_connectivity must be 4 or 8, got %d' % args.pan_component_connectivity)
         config.test.pan_component_connectivity = int(args.pan_component_connectivity)
+    if args.pan_component_mode is not None:
+        if not config.test.get('pan_min_component', 0):
+            fail('--pan_component_mode is a parameter of --pan_min_component, which is missing')
+        if args.pan_component_mode not in ('void', 'absorb'):
+            fail("--pan_component_mode must be void or absorb, got %r" % (args.pan_component_mode,))
+        config.test.pan_component_mode = args.pan_component_mode
     n, c = config.test.get('pan_min_component', 0), config.test.get('pan_component_connectivity', 8)
     if isinstance(n, bool) or not isinstance(n, int) or n < 0:
         fail('test.pan_min_component must be an integer >= 0, got %r' % (n,))
@@ -36,6 +46,8 @@ def apply_pan_component_arguments(args, fail):
         fail('test.pan_component_connectivity must be 4 or 8, got %r' % (c,))
     if not isinstance(config.test.get('pan_component_keep_largest', True), bool):
         fail('test.pan_component_keep_largest must be true or false, got %r' % (config.test.pan_component_keep_largest,))
+    if config.test.get('pan_component_mode', 'void') not in ('void', 'absorb'):
+        fail("test.pan_component_mode must be void or absorb, got %r" % (config.test.pan_component_mode,))
 
 
 def parse_args(description='', argv=None):

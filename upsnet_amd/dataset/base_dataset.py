@@ -127,20 +127,33 @@ class BaseDataset(object):
         return ops.combined_pan_result(segs, boxes, masks, id_last_stuff, score_threshold=score_threshold,
                                        fraction_threshold=fraction_threshold, stuff_area_limit=stuff_area_limit)
 
-    def clean_pan_result(self, pans, min_area=None, connectivity=None, keep_largest=None, what='panoptic'):
+    def clean_pan_result(self, pans, min_area=None, connectivity=None, keep_largest=None, what='panoptic', mode=None):
         """get_unified_pan_result's / get_combined_pan_result's maps with the disconnected fragments of fewer than min_area pixels
-        turned into VOID (dataset/pan_components.clean_panoptic); the parameters default to config.test.pan_min_component,
-        pan_component_connectivity and pan_component_keep_largest. Logs the components and pixels removed over all maps, once."""
+        turned into VOID (dataset/pan_components.clean_panoptic) or, with mode 'absorb', into the segment they border most
+        (DESIGN 4.27); the parameters default to config.test.pan_min_component, pan_component_connectivity,
+        pan_component_keep_largest and pan_component_mode. Logs the components and pixels removed (and absorbed) over all maps, once.
+        RuntimeError if the absorb mode's vote table overflowed on any map (it is sized so that it cannot)."""
         from .pan_components import clean_panoptic
         min_area = config.test.pan_min_component if min_area is None else min_area
         connectivity = config.test.pan_component_connectivity if connectivity is None else connectivity
         keep_largest = config.test.pan_component_keep_largest if keep_largest is None else keep_largest
-        cleaned, total = clean_panoptic(pans, min_area, connectivity, keep_largest, return_stats=True)
+        mode = config.test.get('pan_component_mode', 'void') if mode is None else mode
+        cleaned, total = clean_panoptic(pans, min_area, connectivity, keep_largest, return_stats=True, mode=mode)
         if total is not None:
-            _, comps, gone, pixels = total.cpu().tolist()
-            logger.info('%s: %d of %d connected components (%d pixels) of fewer than %d pixels removed from %d maps (%d-connectivity%s)',
-                        what, gone, comps, pixels, min_area, len(cleaned), connectivity,
-                        ', the largest of every segment kept' if keep_largest else '')
+            total = total.cpu().tolist()
+            _, comps, gone, pixels = total[:4]
+            kept = ', the largest of every segment kept' if keep_largest else ''
+            if mode == 'void':
+                logger.info('%s: %d of %d connected components (%d pixels) of fewer than %d pixels removed from %d maps (%d-connectivity%s)',
+                            what, gone, comps, pixels, min_area, len(cleaned), connectivity, kept)
+            else:
+                absorbed, absorbed_pixels, _, overflow = total[4:]
+                if overflow:
+                    raise RuntimeError("%s: the vote table of pan_absorb overflowed on %d of %d maps: those maps were not cleaned"
+                                       % (what, overflow, len(cleaned)))
+                logger.info('%s: %d of %d connected components (%d pixels) of fewer than %d pixels removed from %d maps (%d-connectivity%s), '
+                            '%d of them (%d pixels) absorbed into the segment they border most', what, gone, comps, pixels, min_area,
+                            len(cleaned), connectivity, kept, absorbed, absorbed_pixels)
         return cleaned
 
     def load_panoptic_gt(self):

@@ -67,7 +67,9 @@ base augmentation alone), comes before the voting, and the results pickle also c
 `--pan_min_component N [--pan_component_connectivity {4,8}]` (or `test.pan_min_component` / `test.pan_component_connectivity` /
 `test.pan_component_keep_largest` in the yaml) removes disconnected fragments from every panoptic result before it is scored, written
 or drawn (csrc/pan_components.hip): a connected component of a (category, instance) pair with fewer than N pixels becomes
-VOID, the largest component of the pair excepted; the results pickle is not changed, so `--eval_only` may try another N.
+VOID, the largest component of the pair excepted; the results pickle is not changed, so `--eval_only` may try another N. With
+`--pan_component_mode absorb` (or `test.pan_component_mode`) such a component takes the pair of the segment it shares the
+longest border with, and becomes VOID only where it borders none.
 One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os

@@ -1992,38 +1992,73 @@ def pan_components(pan_2ch, min_area=0, connectivity=8, keep_largest=True, *, wa
     INPUT map, -1 for VOID. All device tensors; five launches, nothing waits for the host. workspace= (pan_components_workspace; any
     contents), out= (may be pan_2ch itself) and labels= are taken instead of being allocated.
     ValueError before any launch: a wrong dtype, shape or size, connectivity other than 4 or 8, a negative or non-integer min_area."""
+    return _pan_clean("pan_components", lib().upsnet_pan_components_workspace_bytes, lib().upsnet_pan_components, 4, pan_2ch,
+                      min_area, connectivity, keep_largest, want_labels, workspace, out, labels)
+
+
+def pan_absorb_workspace(height, width, device):
+    """Workspace of pan_absorb for maps of height x width pixels: that of pan_components, one winner cell per pixel and the vote table
+    of 2 * H * W slots. The kernels initialise what they read: its contents never matter, and one workspace serves every map of that
+    size (or a smaller one)."""
+    nbytes = int(lib().upsnet_pan_absorb_workspace_bytes(int(height), int(width)))
+    if nbytes == 0:
+        raise ValueError("pan_absorb: a map of %d x %d pixels has no workspace: H * W must lie in 1..2^24" % (height, width))
+    return torch.zeros((nbytes,), dtype=torch.uint8, device=device)
+
+
+def pan_absorb(pan_2ch, min_area=0, connectivity=8, keep_largest=True, *, want_labels=False, workspace=None, out=None, labels=None):
+    """pan_components with the removed components (fragments) absorbed instead of voided (include/upsnet_hip.h states the rule;
+    csrc/pan_components.hip): a fragment takes the (category, instance) of the kept segment it shares the longest border
+    with -- one vote per pixel edge between a fragment pixel and a kept pixel, the most votes win, ties to the smaller key -- and
+    becomes VOID (255, 0, byte 2 kept) only where it has no such border. One round: a fragment that touches only other fragments, VOID,
+    the image border or kept pixels across a corner becomes VOID. Which components are fragments is pan_components' rule on the same
+    arguments; min_area = 0 only labels.
+
+    Returns (out, stats, labels): out uint8 [H,W,3]; stats int32 [8] = distinct keys, components, fragments, fragment pixels (the four
+    of pan_components), fragments absorbed, pixels absorbed, distinct (fragment, donor key) pairs voted for, vote table overflow (0: the
+    table is sized so that it cannot fill; were it ever 1, out is a copy of pan_2ch, and the caller that reads stats must raise);
+    labels as pan_components. All device tensors; eight launches, nothing waits for the host. workspace= (pan_absorb_workspace; any
+    contents), out= (may be pan_2ch itself) and labels= are taken instead of being allocated.
+    ValueError before any launch: a wrong dtype, shape or size, connectivity other than 4 or 8, a negative or non-integer min_area."""
+    return _pan_clean("pan_absorb", lib().upsnet_pan_absorb_workspace_bytes, lib().upsnet_pan_absorb, 8, pan_2ch, min_area,
+                      connectivity, keep_largest, want_labels, workspace, out, labels)
+
+
+def _pan_clean(name, workspace_bytes, entry, nstats, pan_2ch, min_area, connectivity, keep_largest, want_labels, workspace, out, labels):
+    """pan_components and pan_absorb: one set of argument checks and allocations, worded with the caller's name; `entry` (the C entry
+    point, `workspace_bytes` its workspace size) fills int32 [nstats]."""
     if pan_2ch.dtype != torch.uint8 or pan_2ch.dim() != 3 or pan_2ch.shape[2] != 3 or not pan_2ch.is_contiguous():
-        raise ValueError("pan_components: pan_2ch must be contiguous uint8 [H,W,3], got %s %s" % (tuple(pan_2ch.shape), pan_2ch.dtype))
+        raise ValueError("%s: pan_2ch must be contiguous uint8 [H,W,3], got %s %s" % (name, tuple(pan_2ch.shape), pan_2ch.dtype))
     if connectivity not in (4, 8):
-        raise ValueError("pan_components: connectivity must be 4 or 8, got %r" % (connectivity,))
+        raise ValueError("%s: connectivity must be 4 or 8, got %r" % (name, connectivity))
     if isinstance(min_area, bool) or int(min_area) != min_area or min_area < 0 or min_area > 0x7fffffff:
-        raise ValueError("pan_components: min_area must be an integer >= 0, got %r" % (min_area,))
+        raise ValueError("%s: min_area must be an integer >= 0, got %r" % (name, min_area))
     H, W = int(pan_2ch.shape[0]), int(pan_2ch.shape[1])
     if H * W == 0 or H * W > (1 << 24):
-        raise ValueError("pan_components: a map of %d x %d pixels: H * W must lie in 1..2^24" % (H, W))
+        raise ValueError("%s: a map of %d x %d pixels: H * W must lie in 1..2^24" % (name, H, W))
     if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous()):
-        raise ValueError("pan_components: out must be contiguous uint8 [%d,%d,3], got %s %s" % (H, W, tuple(out.shape), out.dtype))
+        raise ValueError("%s: out must be contiguous uint8 [%d,%d,3], got %s %s" % (name, H, W, tuple(out.shape), out.dtype))
     if labels is not None and (labels.dtype != torch.int32 or tuple(labels.shape) != (H, W) or not labels.is_contiguous()
                                or labels.data_ptr() % 16):
-        raise ValueError("pan_components: labels must be a contiguous, 16-byte aligned int32 [%d,%d] tensor, got %s %s"
-                         % (H, W, tuple(labels.shape), labels.dtype))
+        raise ValueError("%s: labels must be a contiguous, 16-byte aligned int32 [%d,%d] tensor, got %s %s"
+                         % (name, H, W, tuple(labels.shape), labels.dtype))
     require_cuda(pan_2ch, workspace, out, labels)      # (after the checks that need no device)
-    need = int(lib().upsnet_pan_components_workspace_bytes(H, W))
+    need = int(workspace_bytes(H, W))
     if workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need
                                   or workspace.data_ptr() % 16):
-        raise ValueError("pan_components: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least %d bytes for a map "
-                         "of %d x %d" % (need, H, W))
+        raise ValueError("%s: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least %d bytes for a map "
+                         "of %d x %d" % (name, need, H, W))
     dev = pan_2ch.device
     with torch.cuda.device(dev):
         if workspace is None:
-            workspace = pan_components_workspace(H, W, dev)
+            workspace = torch.zeros((need,), dtype=torch.uint8, device=dev)
         if out is None:
             out = pan_2ch.clone()
         if labels is None and want_labels:
             labels = torch.zeros((H, W), dtype=torch.int32, device=dev)
-        stats = torch.zeros((4,), dtype=torch.int32, device=dev)
-        check(lib().upsnet_pan_components(stream(), ptr(pan_2ch), H, W, int(connectivity), int(min_area), int(bool(keep_largest)),
-                                          ptr(workspace), ptr(out), ptr(labels), ptr(stats)), "pan_components")
+        stats = torch.zeros((nstats,), dtype=torch.int32, device=dev)
+        check(entry(stream(), ptr(pan_2ch), H, W, int(connectivity), int(min_area), int(bool(keep_largest)), ptr(workspace), ptr(out),
+                    ptr(labels), ptr(stats)), name)
     return out, stats, labels
 
 

@@ -3,7 +3,7 @@
     python -m upsnet_amd.sequence --cfg <yaml> (--weight_path <pth> | --synthetic_weights) --frames <folder> --out <dir>
                                   --panoptic_categories <json> [--track_iou T] [--track_max_age N] [--combined]
                                   [--vis_panoptic {flat,overlay,both}] [--in-flight N] [--video_gt <folder> [--vpq_windows N [N ...]]]
-                                  [--pan_min_component N [--pan_component_connectivity {4,8}]]
+                                  [--pan_min_component N [--pan_component_connectivity {4,8}] [--pan_component_mode {void,absorb}]]
     python -m upsnet_amd.sequence --cfg <yaml> --track_only <folder of pan_2ch PNGs> --out <dir> --panoptic_categories <json> [...]
 
 No annotation JSON is needed. The image files directly in --frames, sorted by name, are one sequence (named after the folder); every
@@ -24,7 +24,8 @@ serials (track_id) go on counting, so a track_id names one object of one sequenc
 the model; the photographs are not there, so of the pictures only 'flat' can be drawn. One rank only.
 --pan_min_component N (or test.pan_min_component in the yaml) turns the connected components of fewer than N pixels into VOID in every
 map before the tracker sees it, the largest of every segment excepted (dataset/pan_components.py), so that a
-stray fragment does not overlap another track; --track_only inputs are cleaned the same way.
+stray fragment does not overlap another track; --track_only inputs are cleaned the same way. --pan_component_mode absorb gives such a
+component to the segment it shares the longest border with instead (section 4.27), which leaves no hole in that segment's mask.
 --video_gt <folder> scores every sequence, once it is tracked and written, against <folder>/<sequence>/gt.json and
 <folder>/<sequence>/pan/<frame>.png (VPQ and STQ on the device; upsnet_amd/video_eval.py says how the frames
 pair and re-scores written runs); --vpq_windows sets the window lengths (default 1 2 3 4). Then <out>/video_scores.json is written and
