@@ -1194,6 +1194,34 @@ size_t upsnet_pan_track_table_offset(void);
 int upsnet_pan_track_step(void *stream, const unsigned char *pan_2ch, int height, int width, double iou_thresh, int max_age, int frame,
                           void *workspace, unsigned short *memory, unsigned char *out_2ch, int *host_table, int host_rows);
 
+/* The same step with constant-velocity motion prediction (restated in tests/pan_track_motion_ref.py). For objects that
+ * keep their motion from frame to frame; on erratic motion it matches fewer segments than the plain step. Integers throughout.
+ * Every track (c, j) also keeps a centroid (cx, cy) = (floor(sum x / area), floor(sum y / area)) over the pixels it was last assigned
+ * and a velocity (vx, vy) in pixels per frame. Step t:
+ *   1. predict: a memory pixel (x, y) of track k, last assigned at frame s, votes for (x + vx (t - s), y + vy (t - s)), the shift in
+ *      int64; a vote outside the image is dropped; among the votes on a pixel the smallest age t - s wins (ages compete as min(age,
+ *      65535)), then the smallest key. The result, the predicted memory, holds at most one key per pixel, so the tracks stay disjoint
+ *      and the candidate bound and iou_thresh >= 1/16 stand as they are.
+ *   2. counts, candidates and the greedy matching of upsnet_pan_track_step, with A_mem and I counted on the predicted memory.
+ *   3. "live" for the issue of new ids and the pool of tracks that may be taken over are those of the REAL memory: a track predicted
+ *      off the image, or outvoted on all its pixels, has A_mem = 0 but is still remembered, and its id is not issued again.
+ *   4. output map and memory update of upsnet_pan_track_step, on the real memory: it stays "the last seen mask, in place".
+ *   5. every segment assigned in this step gives its track a new centroid; matched to a track last assigned at frame s, v = (c_new -
+ *      c_old) / (t - s) per axis, truncated toward zero; newly issued or taken over, v = (0, 0). Any other track keeps both.
+ * With all velocities zero the predicted memory is the real one and the step equals upsnet_pan_track_step bit for bit.
+ * motion_workspace: upsnet_pan_track_motion_workspace_bytes(H, W) bytes, 16-byte aligned, ZEROED ONCE (zeroing it again, with the
+ * tracker's state, resets the tracker): int32 (cx, cy, vx, vy) per key c << 8 | j from byte 0; the cells from byte
+ * upsnet_pan_track_motion_count_offset() to upsnet_pan_track_motion_pred_offset() are zero after every step; from the latter on, one
+ * uint32 per pixel, the predicted memory of the last step: 0 = none, else the key is 65535 - (value & 65535).
+ * Seven launches (clear, predict, count, match, relabel, moments, velocities) and the copy; nothing is synchronised or allocated.
+ * Refused before any launch: what upsnet_pan_track_step refuses, and a null or not 16-byte aligned motion_workspace. */
+size_t upsnet_pan_track_motion_workspace_bytes(int height, int width);
+size_t upsnet_pan_track_motion_count_offset(void);
+size_t upsnet_pan_track_motion_pred_offset(void);
+int upsnet_pan_track_step_motion(void *stream, const unsigned char *pan_2ch, int height, int width, double iou_thresh, int max_age, int frame,
+                                 void *workspace, unsigned short *memory, unsigned char *out_2ch, int *host_table, int host_rows,
+                                 void *motion_workspace);
+
 /* Frame-stable colours of a 2-channel map, a pure function of (category, instance). mode 0: (R, G, B) = (category, instance, 1), VOID
  * (0,0,0). mode 1: stuff takes its category colour, a thing the offset rule of upsnet_pan_format with ordinal := instance and the
  * first attempt whose colour is not (0,0,0), no taken set. cat_table as in upsnet_pan_format (may be NULL in mode 0); an unknown

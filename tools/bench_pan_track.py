@@ -54,9 +54,9 @@ def sequence(H, W, things, frames, seed=0):
     return out
 
 
-def measure(frames, max_age, warmup):
+def measure(frames, max_age, warmup, motion='none'):
     from upsnet_amd.dataset.pan_track import PanopticTracker
-    trk = PanopticTracker(iou_thresh=0.3, max_age=max_age)
+    trk = PanopticTracker(iou_thresh=0.3, max_age=max_age, motion=motion)
     for f in frames[:warmup]:
         trk.update(f)
     torch.cuda.synchronize()
@@ -72,7 +72,7 @@ def measure(frames, max_age, warmup):
     matched = sum(s['matched'] for segs in held for s in segs)
     total = sum(len(segs) for segs in held)
     # the whole loop, from a fresh tracker on the same frames
-    trk = PanopticTracker(iou_thresh=0.3, max_age=max_age)
+    trk = PanopticTracker(iou_thresh=0.3, max_age=max_age, motion=motion)
     for f in frames[:warmup]:
         trk.update(f)
     torch.cuda.synchronize()

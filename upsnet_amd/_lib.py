@@ -189,6 +189,10 @@ _SIGNATURES = {
     "upsnet_pan_track_table_ints": (c_size_t, [c_int, c_int]),
     "upsnet_pan_track_table_offset": (c_size_t, []),
     "upsnet_pan_track_step": (c_int, [P, P, c_int, c_int, c_double, c_int, c_int, P, P, P, P, c_int]),
+    "upsnet_pan_track_motion_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "upsnet_pan_track_motion_count_offset": (c_size_t, []),
+    "upsnet_pan_track_motion_pred_offset": (c_size_t, []),
+    "upsnet_pan_track_step_motion": (c_int, [P, P, c_int, c_int, c_double, c_int, c_int, P, P, P, P, c_int, P]),
     "upsnet_pan_stable_colors": (c_int, [P, P, c_int, c_int, P, c_int, P]),
     "upsnet_pan_components_workspace_bytes": (c_size_t, [c_int, c_int]),
     "upsnet_pan_components": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),

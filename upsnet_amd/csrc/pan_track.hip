@@ -24,6 +24,23 @@
 //                      and its memory entry is cleared when its track was assigned in this step or is older than max_age.
 // The head and the first host_rows rows of the table are then copied to pinned host memory on the same stream.
 //
+// Constant-velocity motion prediction (opt-in: upsnet_pan_track_step_motion; tests/pan_track_motion_ref.py). Every track
+// also keeps the floor centroid of the pixels it was last assigned and a velocity in pixels per frame. Seven launches per frame:
+//   pt_clear_kernel     zeroes the predicted memory: one 32-bit priority per pixel, 0 = none.
+//   pt_predict_kernel   every real-memory pixel of track k, last assigned at frame s, votes for (x + vx (t - s), y + vy (t - s)) (the
+//                       shift in int64; a vote outside the image is dropped) by atomicMax of (65535 - min(t - s, 65535)) << 16 |
+//                       (65535 - k): the youngest track wins a pixel, then the smallest key, so the predicted tracks stay disjoint
+//                       and the candidate bound holds. Also sets live[k]: the real memory holds k, wherever it is predicted.
+//   pt_count_kernel<1>  the count pass on the predicted memory (A_mem and I are counted there).
+//   pt_match_kernel<1>  "live" for id issue and the take-over pool come from live[], not from A_mem > 0: a track shifted off the image
+//                       or outvoted everywhere is still remembered, and its id must not be issued twice. Leaves the old stamp of every
+//                       matched track in prev[] and zeroes its category's live[].
+//   pt_relabel_kernel   unchanged, on the real memory.
+//   pt_moment_kernel    area, sum x and sum y (64-bit) of every track assigned in this step, from the new real memory (whose pixels
+//                       of such a track are exactly the step's), pre-aggregated per workgroup in an LDS hash table.
+//   pt_velocity_kernel  one thread per key: centroid = floor(sum / area); matched: v = (c_new - c_old) / (t - s) truncated toward zero,
+//                       else 0. Zeroes the moment cells and prev[].
+//
 // pan_stable_kernel paints the frame-stable colours of a tracked map (a pure function of (category, instance)).
 #include "common.h"
 #include "upsnet_hip.h"
@@ -68,6 +85,34 @@ static PtWs pt_ws(void *base)
     return w;
 }
 
+// Motion workspace (ints): state[PT_KEYS] as int4 (cx, cy, vx, vy) | prev[PT_KEYS] | live[PT_KEYS] | area[PT_KEYS] | sum x, sum y
+// [PT_KEYS] of 64 bits each (prev .. sum y: zero between steps) | prio[H * W rounded up to 4] (the predicted memory of the last step)
+#define PT_MO_COUNT_OFF (4 * PT_KEYS)
+#define PT_MO_PRED_OFF (11 * PT_KEYS)
+#define PT_MO_BITS 10             // the moment pass's LDS table: 1024 cells per workgroup
+struct PtMo {
+    int4 *state;
+    int *prev, *live, *area;
+    unsigned long long *sx, *sy;
+    unsigned *prio;
+};
+
+static PtMo pt_mo(void *base)
+{
+    PtMo m;
+    int *p = (int *)base;
+    m.state = (int4 *)p;
+    m.prev = p + PT_MO_COUNT_OFF;
+    m.live = m.prev + PT_KEYS;
+    m.area = m.live + PT_KEYS;
+    m.sx = (unsigned long long *)(m.area + PT_KEYS);
+    m.sy = m.sx + PT_KEYS;
+    m.prio = (unsigned *)(p + PT_MO_PRED_OFF);
+    return m;
+}
+
+static inline size_t pt_mo_ints(long npix) { return (size_t)PT_MO_PRED_OFF + (size_t)((npix + 3) & ~3L); }
+
 __device__ static inline bool pt_is_thing(const unsigned key) { return (key >> 8) != 255 && (key & 255) != 0; }
 
 // global count of one cell (v > 0): the first arrival at an A_cur cell counts the segment into its category
@@ -93,8 +138,32 @@ __device__ static inline void pt_flush(unsigned *s_key, int *s_val, const PtWs &
     }
 }
 
+// the predicted memory's keys of 16 pixels in the layout of pan_load_halves (prio is 16-byte aligned, p0 a multiple of 16)
+__device__ static inline unsigned pt_pred_key(const unsigned p) { return p ? 0xffffu - (p & 0xffffu) : 0u; }
+
+__device__ static inline void pt_load_pred(const unsigned *prio, const long p0, const long npix, unsigned w[8])
+{
+    if (p0 + PAN_RUN <= npix) {
+        const uint4 *v = (const uint4 *)(prio + p0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint4 a = v[q];
+            w[2 * q] = pt_pred_key(a.x) | pt_pred_key(a.y) << 16;
+            w[2 * q + 1] = pt_pred_key(a.z) | pt_pred_key(a.w) << 16;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[j] = 0;
+#pragma unroll
+        for (int j = 0; j < PAN_RUN; ++j)
+            if (p0 + j < npix) w[j >> 1] |= pt_pred_key(prio[p0 + j]) << (16 * (j & 1));
+    }
+}
+
+// MOTION: `mem` is the predicted memory (32-bit priorities), else the real one (uint16 keys)
+template <bool MOTION>
 __global__ void __launch_bounds__(256)
-pt_count_kernel(const unsigned char *__restrict__ cur, const unsigned short *__restrict__ mem, const long npix, const bool vec, PtWs ws)
+pt_count_kernel(const unsigned char *__restrict__ cur, const void *__restrict__ mem, const long npix, const bool vec, PtWs ws)
 {
     __shared__ unsigned s_key[PT_HASH];
     __shared__ int s_val[PT_HASH];
@@ -104,7 +173,8 @@ pt_count_kernel(const unsigned char *__restrict__ cur, const unsigned short *__r
     if (p0 < npix) {
         unsigned cw[12], mw[8];
         pan_load48(cur, p0, npix, vec, cw);
-        pan_load_halves(mem, p0, npix, vec, mw);
+        if (MOTION) pt_load_pred((const unsigned *)mem, p0, npix, mw);
+        else pan_load_halves((const unsigned short *)mem, p0, npix, vec, mw);
         unsigned pc = 0, pm = 0;
         int run = 0;
 #pragma unroll
@@ -134,10 +204,13 @@ __device__ static inline bool pt_before(const int ia, const int ua, const int ka
     return l != r ? l > r : ka < kb;
 }
 
+// MOTION: A_mem and I were counted on the predicted memory; what is live comes from mo.live (set by the predict pass from the real memory)
+template <bool MOTION>
 __global__ void __launch_bounds__(PTM_T)
-pt_match_kernel(const double thr, const int frame, PtWs ws)
+pt_match_kernel(const double thr, const int frame, PtWs ws, PtMo mo)
 {
     __shared__ int s_acur[256], s_amem[256];
+    __shared__ unsigned char s_live[MOTION ? 256 : 1];         // per track j: in the real memory at the start of the step
     __shared__ int s_ci[PT_MAX_CAND], s_cu[PT_MAX_CAND];      // candidates: I, U
     __shared__ unsigned short s_ck[PT_MAX_CAND];               // i << 8 | j
     __shared__ int s_id[256], s_flag[256], s_mi[256], s_mu[256], s_row[256];   // per segment i: id, matched | over << 1, I, U, row
@@ -159,6 +232,11 @@ pt_match_kernel(const double thr, const int frame, PtWs ws)
         s_trk[t] = 0;
         if (a) { cnt[c << 8 | t] = 0; s_any = 1; }
         if (m) cnt[PT_MEM_OFF + (c << 8 | t)] = 0;
+        if (MOTION) {
+            const int l = mo.live[c << 8 | t];
+            s_live[t] = l != 0;
+            if (l) mo.live[c << 8 | t] = 0;
+        }
     }
     if (c == 0 && t < PT_HEAD) {                               // the table's head: number of rows, frame index
         int total = 0;
@@ -231,7 +309,7 @@ pt_match_kernel(const double thr, const int frame, PtWs ws)
             int got = 0;
             for (int k = 0; k < 255; ++k) {
                 const int id = (cursor + k) % 255 + 1;
-                if (!s_amem[id] && !s_trk[id]) {
+                if (!(MOTION ? (int)s_live[id] : s_amem[id]) && !s_trk[id]) {
                     got = id;
                     cursor = (cursor + k + 1) % 255;
                     break;
@@ -241,14 +319,14 @@ pt_match_kernel(const double thr, const int frame, PtWs ws)
                 // all 255 ids live: take over the unassigned memory track with the oldest frame, ties to the smallest id
                 int best = 0x7fffffff;
                 for (int id = 1; id < 256; ++id) {
-                    if (s_trk[id] || !s_amem[id]) continue;
+                    if (s_trk[id] || !(MOTION ? (int)s_live[id] : s_amem[id])) continue;
                     const int s = ws.stamp[c << 8 | id];
                     if (s < best) { best = s; got = id; }
                 }
                 s_flag[i] = 2;
             }
             s_id[i] = got;
-            s_trk[got] = 1;
+            s_trk[got] = MOTION ? 2 : 1;                       // (2: issued or taken over, no velocity to take)
         }
         ws.cursor[c] = cursor;
     }
@@ -266,6 +344,7 @@ pt_match_kernel(const double thr, const int frame, PtWs ws)
             row[6] = s_acur[t];
             row[7] = s_flag[t] >> 1;
         }
+        if (MOTION && s_trk[t] == 1) mo.prev[c << 8 | t] = ws.stamp[c << 8 | t];   // matched: the frame + 1 of its last assignment
         if (s_trk[t]) ws.stamp[c << 8 | t] = frame + 1;
     }
 }
@@ -314,6 +393,129 @@ pt_relabel_kernel(const unsigned char *__restrict__ cur, unsigned char *__restri
     pan_store_halves(mem, p0, npix, vec, kw);
 }
 
+// ------------------------------------------------------------------------------------------------- motion prediction
+__global__ void __launch_bounds__(256)
+pt_clear_kernel(uint4 *__restrict__ prio, const long n16)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n16) prio[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ void __launch_bounds__(256)
+pt_predict_kernel(const unsigned short *__restrict__ mem, const long npix, const int width, const int height, const bool vec, const int frame,
+                  const int *__restrict__ stamp, PtMo mo)
+{
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
+    if (p0 >= npix) return;
+    unsigned mw[8];
+    pan_load_halves(mem, p0, npix, vec, mw);
+    int x = (int)(p0 % width), y = (int)(p0 / width);
+    unsigned pm = 0, pri = 0;
+    long long dx = 0, dy = 0;
+#pragma unroll
+    for (int i = 0; i < PAN_RUN; ++i) {
+        const unsigned m = pan_half(mw, i);                    // (pixels past the end read as zeros: no vote)
+        if (m != pm) {
+            pm = m;
+            if (m) {
+                const long long age = (long long)frame - ((long long)stamp[m] - 1);
+                const int4 st = mo.state[m];
+                dx = (long long)st.z * age;
+                dy = (long long)st.w * age;
+                pri = (0xffffu - (unsigned)(age < 0 ? 0 : (age > 0xffff ? 0xffff : age))) << 16 | (0xffffu - m);
+                mo.live[m] = 1;
+            }
+        }
+        if (m) {
+            const long long nx = x + dx, ny = y + dy;
+            if (nx >= 0 && nx < width && ny >= 0 && ny < height) atomicMax(&mo.prio[ny * width + nx], pri);
+        }
+        if (++x == width) { x = 0; ++y; }
+    }
+}
+
+// global moments of one key: area, sum x, sum y
+__device__ static inline void pt_moment_global(const PtMo &mo, const unsigned key, const int area, const unsigned long long sx,
+                                               const unsigned long long sy)
+{
+    atomicAdd(&mo.area[key], area);
+    atomicAdd(&mo.sx[key], sx);
+    atomicAdd(&mo.sy[key], sy);
+}
+
+// `mem` is the real memory after the relabel pass: the pixels of a track with stamp frame + 1 are exactly those assigned in this step
+__global__ void __launch_bounds__(256)
+pt_moment_kernel(const unsigned short *__restrict__ mem, const long npix, const int width, const bool vec, const int frame,
+                 const int *__restrict__ stamp, PtMo mo)
+{
+    __shared__ unsigned s_key[1 << PT_MO_BITS];
+    __shared__ int s_area[1 << PT_MO_BITS];
+    __shared__ unsigned long long s_sx[1 << PT_MO_BITS], s_sy[1 << PT_MO_BITS];
+    pan_lds_clear<PT_MO_BITS>(s_key, s_area, 1);
+    for (int i = threadIdx.x; i < (1 << PT_MO_BITS); i += blockDim.x) { s_sx[i] = 0; s_sy[i] = 0; }
+    __syncthreads();
+    const long p0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * PAN_RUN;
+    if (p0 < npix) {
+        unsigned mw[8];
+        pan_load_halves(mem, p0, npix, vec, mw);
+        // one run of `run` pixels of track k on row ry from column x0: sum x = run x0 + run (run - 1) / 2, sum y = run ry
+        auto flush = [&](const unsigned k, const int run, const int x0, const int ry) {
+            const unsigned long long sx = (unsigned long long)run * x0 + (unsigned long long)(run * (run - 1) / 2);
+            const unsigned long long sy = (unsigned long long)run * ry;
+            const bool held = pan_lds_claim<PT_MO_BITS>(s_key, k, [&](const unsigned slot) {
+                atomicAdd(&s_area[slot], run);
+                atomicAdd(&s_sx[slot], sx);
+                atomicAdd(&s_sy[slot], sy);
+            });
+            if (!held) pt_moment_global(mo, k, run, sx, sy);
+        };
+        int x = (int)(p0 % width), y = (int)(p0 / width);
+        unsigned pm = 0, pk = 0;                               // pk: pm if its track was assigned in this step, else 0
+        int run = 0, x0 = 0, ry = 0;
+#pragma unroll
+        for (int i = 0; i < PAN_RUN; ++i) {
+            const unsigned m = pan_half(mw, i);                // (pixels past the end read as zeros: no run)
+            if (m != pm || x == 0) {                           // a run shares its key and its row
+                if (run) flush(pk, run, x0, ry);
+                if (m != pm) {
+                    pm = m;
+                    pk = m && stamp[m] == frame + 1 ? m : 0u;
+                }
+                run = 0;
+                x0 = x;
+                ry = y;
+            }
+            if (pk) ++run;
+            if (++x == width) { x = 0; ++y; }
+        }
+        if (run) flush(pk, run, x0, ry);
+    }
+    __syncthreads();
+    pan_lds_drain<PT_MO_BITS>(s_key, [&](const unsigned k, const int i) { pt_moment_global(mo, k, s_area[i], s_sx[i], s_sy[i]); });
+}
+
+// one thread per key; a key with area > 0 was assigned in this step, prev > 0 says it was matched (frame + 1 of its last assignment)
+__global__ void __launch_bounds__(256)
+pt_velocity_kernel(const int frame, PtMo mo)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;       // the grid has exactly PT_KEYS threads
+    const int a = mo.area[k], prev = mo.prev[k];
+    if (prev) mo.prev[k] = 0;
+    if (!a) return;
+    const int cx = (int)(mo.sx[k] / (unsigned long long)a), cy = (int)(mo.sy[k] / (unsigned long long)a);
+    int vx = 0, vy = 0;
+    if (prev) {
+        const int4 old = mo.state[k];
+        const int gap = max(frame - (prev - 1), 1);
+        vx = (cx - old.x) / gap;                               // (C division truncates toward zero)
+        vy = (cy - old.y) / gap;
+    }
+    mo.state[k] = make_int4(cx, cy, vx, vy);
+    mo.area[k] = 0;
+    mo.sx[k] = 0;
+    mo.sy[k] = 0;
+}
+
 extern "C" size_t upsnet_pan_track_workspace_bytes(int height, int width)
 {
     if (height < 1 || width < 1 || (long)height * width > PT_MAX_PIXELS) return 0;
@@ -330,9 +532,19 @@ extern "C" size_t upsnet_pan_track_table_ints(int height, int width)
     return pt_table_ints((long)height * width);
 }
 
-extern "C" int upsnet_pan_track_step(void *stream, const unsigned char *pan_2ch, int height, int width, double iou_thresh, int max_age,
-                                     int frame, void *workspace, unsigned short *memory, unsigned char *out_2ch, int *host_table,
-                                     int host_rows)
+extern "C" size_t upsnet_pan_track_motion_workspace_bytes(int height, int width)
+{
+    if (height < 1 || width < 1 || (long)height * width > PT_MAX_PIXELS) return 0;
+    return pt_mo_ints((long)height * width) * sizeof(int);
+}
+
+extern "C" size_t upsnet_pan_track_motion_count_offset(void) { return (size_t)PT_MO_COUNT_OFF * sizeof(int); }
+
+extern "C" size_t upsnet_pan_track_motion_pred_offset(void) { return (size_t)PT_MO_PRED_OFF * sizeof(int); }
+
+// one step; motion_workspace = nullptr: the plain rule (three launches), else with motion prediction (seven)
+static int pt_step(void *stream, const unsigned char *pan_2ch, int height, int width, double iou_thresh, int max_age, int frame,
+                   void *workspace, unsigned short *memory, unsigned char *out_2ch, int *host_table, int host_rows, void *motion_workspace)
 {
     UPS_REQUIRE(pan_2ch && workspace && memory && out_2ch, "pan_track_step: null pointer");
     UPS_REQUIRE(height > 0 && width > 0 && (long)height * width <= PT_MAX_PIXELS, "pan_track_step: image of %d x %d pixels outside 1..2^24",
@@ -344,23 +556,59 @@ extern "C" int upsnet_pan_track_step(void *stream, const unsigned char *pan_2ch,
                 "pan_track_step: workspace / memory / table not aligned");
     hipStream_t st = (hipStream_t)stream;
     PtWs ws = pt_ws(workspace);
+    const PtMo mo = motion_workspace ? pt_mo(motion_workspace) : PtMo{};
     const long npix = (long)height * width;
     ws.table += (size_t)(frame & 1) * pt_table_ints(npix);
     const long threads = (npix + PAN_RUN - 1) / PAN_RUN;
     const unsigned grid = (unsigned)((threads + 255) / 256);
-    const bool vec_in = (((uintptr_t)pan_2ch | (uintptr_t)memory) & 15) == 0;
-    hipLaunchKernelGGL(pt_count_kernel, dim3(grid), dim3(256), 0, st, pan_2ch, memory, npix, vec_in, ws);
-    UPS_CHECK_LAUNCH("pt_count_kernel");
-    hipLaunchKernelGGL(pt_match_kernel, dim3(255), dim3(PTM_T), 0, st, iou_thresh, frame, ws);
-    UPS_CHECK_LAUNCH("pt_match_kernel");
+    const bool vec_in = (((uintptr_t)pan_2ch | (uintptr_t)memory) & 15) == 0, vec_mem = ((uintptr_t)memory & 15) == 0;
+    if (motion_workspace) {
+        const long n16 = (npix + 3) / 4;
+        hipLaunchKernelGGL(pt_clear_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, (uint4 *)mo.prio, n16);
+        UPS_CHECK_LAUNCH("pt_clear_kernel");
+        hipLaunchKernelGGL(pt_predict_kernel, dim3(grid), dim3(256), 0, st, memory, npix, width, height, vec_mem, frame, ws.stamp, mo);
+        UPS_CHECK_LAUNCH("pt_predict_kernel");
+        hipLaunchKernelGGL(pt_count_kernel<true>, dim3(grid), dim3(256), 0, st, pan_2ch, (const void *)mo.prio, npix,
+                           ((uintptr_t)pan_2ch & 15) == 0, ws);
+        UPS_CHECK_LAUNCH("pt_count_kernel<motion>");
+        hipLaunchKernelGGL(pt_match_kernel<true>, dim3(255), dim3(PTM_T), 0, st, iou_thresh, frame, ws, mo);
+        UPS_CHECK_LAUNCH("pt_match_kernel<motion>");
+    } else {
+        hipLaunchKernelGGL(pt_count_kernel<false>, dim3(grid), dim3(256), 0, st, pan_2ch, (const void *)memory, npix, vec_in, ws);
+        UPS_CHECK_LAUNCH("pt_count_kernel");
+        hipLaunchKernelGGL(pt_match_kernel<false>, dim3(255), dim3(PTM_T), 0, st, iou_thresh, frame, ws, mo);
+        UPS_CHECK_LAUNCH("pt_match_kernel");
+    }
     hipLaunchKernelGGL(pt_relabel_kernel, dim3(grid), dim3(256), 0, st, pan_2ch, out_2ch, memory, npix,
                        vec_in && ((uintptr_t)out_2ch & 15) == 0, frame, max_age, ws);
     UPS_CHECK_LAUNCH("pt_relabel_kernel");
+    if (motion_workspace) {
+        hipLaunchKernelGGL(pt_moment_kernel, dim3(grid), dim3(256), 0, st, memory, npix, width, vec_mem, frame, ws.stamp, mo);
+        UPS_CHECK_LAUNCH("pt_moment_kernel");
+        hipLaunchKernelGGL(pt_velocity_kernel, dim3(PT_KEYS / 256), dim3(256), 0, st, frame, mo);
+        UPS_CHECK_LAUNCH("pt_velocity_kernel");
+    }
     if (host_table) {
         const size_t rows = (size_t)host_rows < pt_rows(npix) ? (size_t)host_rows : pt_rows(npix);
         UPS_CHECK_HIP(hipMemcpyAsync(host_table, ws.table, (PT_HEAD + rows * PT_ROW) * sizeof(int), hipMemcpyDeviceToHost, st));
     }
     return 0;
+}
+
+extern "C" int upsnet_pan_track_step(void *stream, const unsigned char *pan_2ch, int height, int width, double iou_thresh, int max_age,
+                                     int frame, void *workspace, unsigned short *memory, unsigned char *out_2ch, int *host_table,
+                                     int host_rows)
+{
+    return pt_step(stream, pan_2ch, height, width, iou_thresh, max_age, frame, workspace, memory, out_2ch, host_table, host_rows, nullptr);
+}
+
+extern "C" int upsnet_pan_track_step_motion(void *stream, const unsigned char *pan_2ch, int height, int width, double iou_thresh, int max_age,
+                                            int frame, void *workspace, unsigned short *memory, unsigned char *out_2ch, int *host_table,
+                                            int host_rows, void *motion_workspace)
+{
+    UPS_REQUIRE(motion_workspace && ((uintptr_t)motion_workspace & 15) == 0, "pan_track_step_motion: motion workspace null or not 16-byte aligned");
+    return pt_step(stream, pan_2ch, height, width, iou_thresh, max_age, frame, workspace, memory, out_2ch, host_table, host_rows,
+                   motion_workspace);
 }
 
 

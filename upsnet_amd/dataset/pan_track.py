@@ -15,6 +15,12 @@ serial), matched, iou (I / U as a float, for people only), area. It is read from
 memory by an asynchronous copy: the sequence resolves when it is first looked at, or at the end of the next update, whichever comes
 first, so a loop that never looks at it never waits for more than the frame before.
 
+Motion prediction (opt-in): PanopticTracker(..., motion='constant_velocity') keeps a centroid and a velocity per
+track and associates each frame with the memory shifted by velocity x age instead of the memory in place, so that an object that
+accelerates, reappears after an occlusion or passes another one keeps its identity. It is for persistent motion (sparsely sampled
+video of moving objects); on erratic motion, a random walk for instance, it matches fewer segments than the default. The rule is
+restated in tests/pan_track_motion_ref.py. predicted() and motion_state() show what the last step predicted and what it keeps.
+
 The 8-bit id is what fits channel 1 and the existing writers; it is recycled after 255 issues per category. The serial counts from 1
 over the tracker's life and is never reused: it is the identity consumers should use.
 """
@@ -30,15 +36,18 @@ from .pq import _check_image
 MAX_PIXELS = 1 << 24
 HEAD, ROW = 8, 8              # ints before the first row / per row of the step's table (include/upsnet_hip.h)
 FAST_ROWS = 1024              # rows that travel with the step's one device-to-host copy; a frame of more costs a second copy
+MOTIONS = ('none', 'constant_velocity')
 
 
-def check_params(iou_thresh, max_age):
-    """ValueError unless 1/16 <= iou_thresh <= 1 and max_age is an integer >= 0. The lower bound: memory tracks are disjoint, so a
+def check_params(iou_thresh, max_age, motion='none'):
+    """ValueError unless 1/16 <= iou_thresh <= 1, max_age is an integer >= 0 and motion is one of MOTIONS. The lower bound: memory tracks are disjoint, so a
     segment has at most 1 / iou_thresh candidates, which bounds the kernel's LDS candidate list at 16 per segment, 4080 per category."""
     if not (1.0 / 16.0 <= float(iou_thresh) <= 1.0):      # (NaN fails too)
         raise ValueError("iou_thresh must lie in [1/16, 1], got %r" % (iou_thresh,))
     if int(max_age) != max_age or max_age < 0:
         raise ValueError("max_age must be an integer >= 0, got %r" % (max_age,))
+    if motion not in MOTIONS:
+        raise ValueError("motion must be one of %s, got %r" % (', '.join(MOTIONS), motion))
 
 
 class TrackSegments(Sequence):
@@ -79,16 +88,22 @@ class PanopticTracker(object):
     """One sequence's tracker on one device. The frame size is fixed by the first update() (or after reset()).
 
     update(pan_2ch) -> (tracked uint8 [H,W,3] device tensor, TrackSegments); three launches and one asynchronous copy, nothing waits.
+    motion='constant_velocity' (default 'none': the same launches as ever) predicts where every track is before it associates, for
+    objects in persistent motion (seven launches and the copy). Then predicted() -> int32 [H,W] numpy array, the key of the track the
+    last step predicted at a pixel and -1 for none, and motion_state() -> {(category, instance): (cx, cy, vx, vy)} for the tracks state()
+    shows: the floor centroid of the pixels last assigned and the velocity in pixels per frame.
     reset() forgets every track, the frame size and the frame counter; the serials go on counting unless reset(serials=True).
     state() -> (key int32 [H,W], frame int32 [H,W]) numpy arrays: key = category << 8 | instance of the track a pixel remembers and -1
     for none; frame = the index of the frame that last wrote the pixel and -1 for none.
     ValueError, raised before any launch and leaving the state untouched: a frame that is not uint8 [H,W,3], of another size than the
     tracker's, or of more than 2^24 pixels."""
 
-    def __init__(self, iou_thresh=0.3, max_age=0, device=None):
-        check_params(iou_thresh, max_age)
+    def __init__(self, iou_thresh=0.3, max_age=0, device=None, motion='none'):
+        check_params(iou_thresh, max_age, motion)
         self.iou_thresh = float(iou_thresh)
         self.max_age = int(max_age)
+        self.motion = motion
+        self._mws = None
         self.device = torch.device(device) if device is not None else None
         self.next_serial = 1
         self._ws = None
@@ -119,9 +134,14 @@ class PanopticTracker(object):
             n = min(self._table_ints, HEAD + ROW * FAST_ROWS)
             self._tables = [torch.empty((n,), dtype=torch.int32, pin_memory=True) for _ in range(2)]
             self._mem = torch.empty((H, W), dtype=torch.int16, device=dev).zero_()
+            if self.motion != 'none':
+                self._mws = torch.empty((int(lib().upsnet_pan_track_motion_workspace_bytes(H, W)),), dtype=torch.uint8, device=dev).zero_()
+                self._pred_off = int(lib().upsnet_pan_track_motion_pred_offset())
         else:
             self._ws[self._stamp_off:].zero_()       # stamps, cursors, scratch (the count cells are zero after every step)
             self._mem.zero_()
+            if self._mws is not None:
+                self._mws.zero_()                    # centroids, velocities, the predicted memory
         self.device = dev
         self.shape = (H, W)
 
@@ -146,7 +166,11 @@ class PanopticTracker(object):
         step.host = self._tables[step.frame & 1]
         with torch.cuda.device(self.device):
             out = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
-            ops.pan_track_step(pan_2ch.contiguous(), self.iou_thresh, self.max_age, step.frame, self._ws, self._mem, out, step.host)
+            if self._mws is None:
+                ops.pan_track_step(pan_2ch.contiguous(), self.iou_thresh, self.max_age, step.frame, self._ws, self._mem, out, step.host)
+            else:
+                ops.pan_track_step_motion(pan_2ch.contiguous(), self.iou_thresh, self.max_age, step.frame, self._ws, self._mem, out,
+                                          self._mws, step.host)
             step.event = torch.cuda.Event()
             step.event.record()
         step.segments = TrackSegments(self, step)
@@ -191,6 +215,26 @@ class PanopticTracker(object):
         frame = stamp[key.reshape(-1).long()].reshape(key.shape) - 1      # (all memory pixels of a track share its last frame)
         none = key == 0
         return key.masked_fill(none, -1).cpu().numpy(), frame.masked_fill(none, -1).cpu().numpy()
+
+
+    def _motion_on(self, what):
+        if self.motion == 'none':
+            raise RuntimeError("PanopticTracker.%s(): the tracker was built with motion='none'" % what)
+        if self.shape is None or self.frame_index == 0:
+            raise RuntimeError("PanopticTracker.%s(): no frame yet" % what)
+
+    def predicted(self):
+        self._motion_on('predicted')
+        H, W = self.shape
+        prio = self._mws[self._pred_off:self._pred_off + 4 * H * W].view(torch.int32).reshape(H, W)
+        return (0xffff - (prio & 0xffff)).masked_fill(prio == 0, -1).cpu().numpy()
+
+    def motion_state(self):
+        self._motion_on('motion_state')
+        keys = torch.unique(self._mem.to(torch.int32) & 0xffff)
+        keys = keys[keys != 0]
+        rows = self._mws[:16 * 65536].view(torch.int32).reshape(65536, 4)[keys.long()].cpu().tolist()
+        return {(k >> 8, k & 255): tuple(r) for k, r in zip(keys.cpu().tolist(), rows)}
 
 
 def track_sequence(pans, **kw):

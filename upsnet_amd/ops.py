@@ -1935,6 +1935,20 @@ def pan_track_step(pan_2ch, iou_thresh, max_age, frame, workspace, memory, out, 
     once; out: uint8 [H,W,3], the tracked map; host_table: pinned int32 host memory that takes the table's head (8 ints) and its first
     rows (8 ints each), as many as fit, by an asynchronous copy (None: no copy). Three launches, no host synchronisation, no allocation
     (dataset/pan_track.PanopticTracker owns the buffers)."""
+    return _pan_track_step("pan_track_step", pan_2ch, iou_thresh, max_age, frame, workspace, memory, out, host_table, None)
+
+
+def pan_track_step_motion(pan_2ch, iou_thresh, max_age, frame, workspace, memory, out, motion_workspace, host_table=None):
+    """pan_track_step with constant-velocity motion prediction: motion_workspace is a contiguous uint8 device tensor of
+    upsnet_pan_track_motion_workspace_bytes(H, W) bytes, 16-byte aligned and zeroed once; it holds the tracks' centroids and velocities
+    and the step's predicted memory. Seven launches, no host synchronisation, no allocation."""
+    require_cuda(motion_workspace)
+    if motion_workspace.dtype != torch.uint8 or not motion_workspace.is_contiguous() or motion_workspace.data_ptr() % 16:
+        raise ValueError("pan_track_step_motion: motion_workspace must be a contiguous, 16-byte aligned uint8 tensor")
+    return _pan_track_step("pan_track_step_motion", pan_2ch, iou_thresh, max_age, frame, workspace, memory, out, host_table, motion_workspace)
+
+
+def _pan_track_step(what, pan_2ch, iou_thresh, max_age, frame, workspace, memory, out, host_table, motion_workspace):
     require_cuda(pan_2ch, workspace, memory, out)
     if pan_2ch.dtype != torch.uint8 or pan_2ch.dim() != 3 or pan_2ch.shape[2] != 3 or not pan_2ch.is_contiguous():
         raise ValueError("pan_track_step: pan_2ch must be contiguous uint8 [H,W,3], got %s %s" % (tuple(pan_2ch.shape), pan_2ch.dtype))
@@ -1952,8 +1966,14 @@ def pan_track_step(pan_2ch, iou_thresh, max_age, frame, workspace, memory, out, 
                 or not host_table.is_contiguous():
             raise ValueError("pan_track_step: host_table must be contiguous pinned int32 host memory of at least 8 ints")
         host_rows = (host_table.numel() - 8) // 8
-    check(lib().upsnet_pan_track_step(stream(), ptr(pan_2ch), H, W, float(iou_thresh), int(max_age), int(frame), ptr(workspace),
-                                      ptr(memory), ptr(out), ptr(host_table), host_rows), "pan_track_step")
+    args = (stream(), ptr(pan_2ch), H, W, float(iou_thresh), int(max_age), int(frame), ptr(workspace), ptr(memory), ptr(out),
+            ptr(host_table), host_rows)
+    if motion_workspace is None:
+        check(lib().upsnet_pan_track_step(*args), what)
+    else:
+        if motion_workspace.numel() < int(lib().upsnet_pan_track_motion_workspace_bytes(H, W)):
+            raise ValueError("pan_track_step_motion: motion_workspace too small for a frame of %d x %d" % (H, W))
+        check(lib().upsnet_pan_track_step_motion(*(args + (ptr(motion_workspace),))), what)
     return out
 
 

@@ -2,6 +2,7 @@
 
     python -m upsnet_amd.sequence --cfg <yaml> (--weight_path <pth> | --synthetic_weights) --frames <folder> --out <dir>
                                   --panoptic_categories <json> [--track_iou T] [--track_max_age N] [--combined]
+                                  [--track_motion {none,constant_velocity}]
                                   [--vis_panoptic {flat,overlay,both}] [--in-flight N] [--video_gt <folder> [--vpq_windows N [N ...]]]
                                   [--pan_min_component N [--pan_component_connectivity {4,8}] [--pan_component_mode {void,absorb}]]
     python -m upsnet_amd.sequence --cfg <yaml> --track_only <folder of pan_2ch PNGs> --out <dir> --panoptic_categories <json> [...]
@@ -20,6 +21,9 @@ serials (track_id) go on counting, so a track_id names one object of one sequenc
   pred.json             COCO panoptic annotations; every segment also carries 'track_id' (0 for stuff)
   tracks.json           {'tracks': [{'track_id', 'category_id', 'instance', 'first_frame', 'last_frame', 'frames'}]}, frames by name
   vis/, vis_flat/       with --vis_panoptic: the pictures, every track in one colour throughout
+--track_motion constant_velocity (default none) lets the tracker predict every track's place from its velocity
+before it associates: for objects in persistent motion in sparsely sampled sequences, where it keeps identities through occlusions,
+accelerations and crossings; on erratic motion it matches fewer segments than the default. It applies to --track_only too.
 --track_only tracks an already written prediction (for instance results/pans_unified/pan_2ch of an evaluation run) without building
 the model; the photographs are not there, so of the pictures only 'flat' can be drawn. One rank only.
 --pan_min_component N (or test.pan_min_component in the yaml) turns the connected components of fewer than N pixels into VOID in every
@@ -164,6 +168,8 @@ def parse_args(argv=None):
     p.add_argument('--panoptic_categories', type=str, default='', metavar='JSON', help="a panoptic JSON whose 'categories' to use")
     p.add_argument('--track_iou', type=float, default=0.3, metavar='T', help='mask IoU from which a segment may continue a track, in [1/16, 1]')
     p.add_argument('--track_max_age', type=int, default=0, metavar='N', help='frames a track may be missing and still be re-acquired')
+    p.add_argument('--track_motion', choices=('none', 'constant_velocity'), default='none',
+                   help='constant_velocity: predict every track from its velocity before associating (for persistent motion)')
     p.add_argument('--combined', action='store_true', help='track get_combined_pan_result (detections + semantic map) instead of the panoptic head')
     p.add_argument('--vis_panoptic', choices=('flat', 'overlay', 'both'), default=None, help='also draw the tracked maps')
     p.add_argument('--in-flight', type=int, default=1, help='images in flight (1 = the reference loop)')
@@ -192,9 +198,9 @@ def main(argv=None):
         raise SystemExit("--panoptic_categories: no panoptic JSON at %r (its 'categories' name and colour the segments)" % args.panoptic_categories)
     from .dataset.pan_track import PanopticTracker, check_params
     try:
-        check_params(args.track_iou, args.track_max_age)
+        check_params(args.track_iou, args.track_max_age, args.track_motion)
     except ValueError as e:
-        raise SystemExit('--track_iou / --track_max_age: %s' % e)
+        raise SystemExit('--track_iou / --track_max_age / --track_motion: %s' % e)
     update_config(args.cfg)
     from .config.parse_args import apply_pan_component_arguments
     apply_pan_component_arguments(args, _exit)
@@ -217,7 +223,7 @@ def main(argv=None):
     sequences = discover_sequences(args.frames or args.track_only, '--frames' if args.frames else '--track_only')
     with open(args.panoptic_categories, 'r') as f:
         categories = json.load(f)['categories']
-    tracker = PanopticTracker(iou_thresh=args.track_iou, max_age=args.track_max_age)
+    tracker = PanopticTracker(iou_thresh=args.track_iou, max_age=args.track_max_age, motion=args.track_motion)
     done = []
     score, finish = None, lambda res: res
     if args.video_gt or args.mots_gt or args.write_mots:
