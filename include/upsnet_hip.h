@@ -669,6 +669,23 @@ int upsnet_panoptic_fuse_up(void *stream, const float *fcn_score, int score_nhwc
                             const int64_t *cls_idx, const int64_t *keep_inds, const int *num_keep, const int *real_keep,
                             int kmax, int mask_size, const int64_t *class_map, int64_t *pan_out, int64_t *sem_out);
 
+/* upsnet_panoptic_fuse_up with the confidence of every pixel (the reference keeps the arg-max only). The rule:
+ *   - z, the panoptic logits of a pixel of the [Hs*scale, Ws*scale] map, are exactly those upsnet_panoptic_fuse_up compares: the
+ *     num_stuff stuff logits (the x4 bilinear upsampling of the score, fp32 without FMA); for each of the k = *num_keep kept instances in
+ *     index order seg_inst + mask_energy, which is exactly 0 where the instance touches neither its box nor its mask (with
+ *     *real_keep == 0 the one dummy channel has no mask energy, as in the reference); the void logit max(thing channels) - max_j seg_inst_j;
+ *   - P = softmax(z) (the reference's training loss is over exactly these channels, resnet_upsnet.py:234-243);
+ *   - conf = P[winner], the winner being the label pan_out gets (255: the void channel). The winner is a maximum of z, so
+ *     conf = 1 / sum_c exp(z_c - z_max), in fp32, every one of the k instance channels included;
+ *   - conf_out = (unsigned)(conf * 255.0f + 0.5f), one byte per pixel.
+ * conf_out uint8 [Hs*scale, Ws*scale], 4-byte aligned. pan_out and sem_out are bit-equal to upsnet_panoptic_fuse_up's; one launch of
+ * a kernel of its own, so the label-only kernel is what it was. Everything else as upsnet_panoptic_fuse_up. */
+int upsnet_panoptic_fuse_up_conf(void *stream, const float *fcn_score, int score_nhwc, int num_seg, int score_h, int score_w,
+                                 int scale, int num_stuff, const float *mask_rois, const float *mask_logit,
+                                 const int64_t *cls_idx, const int64_t *keep_inds, const int *num_keep, const int *real_keep,
+                                 int kmax, int mask_size, const int64_t *class_map, int64_t *pan_out, int64_t *sem_out,
+                                 unsigned char *conf_out);
+
 /* Reference-shaped fusion on materialised planes (resnet_upsnet.py:234-243):
  * seg_inst, mask_energy [k,H,W]. */
 int upsnet_panoptic_argmax(void *stream, const float *fcn_output, int num_seg, int height, int width, int num_stuff,
@@ -728,6 +745,12 @@ int upsnet_im_post_rle(void *stream, const float *pred_boxes, const float *mask_
 int upsnet_restore_label_maps(void *stream, const int64_t *sseg, const int64_t *pano, long src_stride, int src_height, int src_width,
                               const int *y_ofs, int out_height, const int *x_ofs, int out_width, unsigned char *out_sseg,
                               unsigned char *out_pano);
+
+/* The same gather for one uint8 plane (the panoptic confidence of upsnet_panoptic_fuse_up_conf, which thereby reaches the original
+ * image size by the rule of the label maps): out[y][x] = src[y_ofs[y]][x_ofs[x]]; src uint8 [src_height][src_stride], out uint8
+ * [out_height][out_width]. One launch, no host synchronisation. */
+int upsnet_restore_plane_u8(void *stream, const unsigned char *src, long src_stride, int src_height, int src_width, const int *y_ofs,
+                            int out_height, const int *x_ofs, int out_width, unsigned char *out);
 
 /* ============================== Evaluation: panoptic quality and semantic confusion matrix ============================== */
 
@@ -1281,6 +1304,30 @@ int upsnet_pan_components(void *stream, const unsigned char *pan_2ch, int height
 size_t upsnet_pan_absorb_workspace_bytes(int height, int width);
 int upsnet_pan_absorb(void *stream, const unsigned char *pan_2ch, int height, int width, int connectivity, int min_area, int keep_largest,
                       void *workspace, unsigned char *out_2ch, int *labels, int *stats);
+
+/* ============================== Panoptic confidence: segment scores and the score filter ============================== */
+
+/* Scores of the segments of a 2-channel map from a confidence plane (csrc/pan_confidence.hip; restated in
+ * tests/pan_confidence_ref.py). pan_2ch uint8 [H,W,3] (key = byte 0 << 8 | byte 1; byte 0 == 255 is VOID, which is no segment and has
+ * no row), conf uint8 [H,W] (upsnet_panoptic_fuse_up_conf's bytes, restored to the map's size). Per key: area = its pixels, sum_q = the
+ * sum of their confidence bytes, both uint32 (H * W <= 2^24, so 255 * 2^24 < 2^32); the score of a segment is sum_q / (255 area),
+ * which the host forms in double.
+ *   table uint32 [upsnet_pan_segment_scores_table_ints()] (out): [0] = number of rows n, [1..3] = 0, then n rows (key, area, sum_q) in
+ *   ascending key; rows past n are not written.
+ * workspace: upsnet_pan_segment_scores_workspace_bytes() bytes, 4-byte aligned; its contents on entry are ARBITRARY. Three launches
+ * (clear, count, compact), integer atomics only, nothing is synchronised or allocated. Refused before any launch: a null pointer, H * W
+ * outside 1..2^24, a misaligned workspace or table. */
+size_t upsnet_pan_segment_scores_workspace_bytes(void);
+size_t upsnet_pan_segment_scores_table_ints(void);
+int upsnet_pan_segment_scores(void *stream, const unsigned char *pan_2ch, const unsigned char *conf, int height, int width,
+                              void *workspace, unsigned *table);
+
+/* The score filter: every pixel of a non-VOID key whose row of `table` (upsnet_pan_segment_scores of the same map) has
+ * (double)sum_q < min_score * (double)(255 * area) becomes (255, 0, 0); every other pixel keeps its three bytes (so does a key without a
+ * row). One IEEE double product and no addition: numpy decides the same. 0 <= min_score <= 1 (0 removes nothing). out_2ch may be
+ * pan_2ch itself. One launch, nothing is synchronised or allocated. */
+int upsnet_pan_score_filter(void *stream, const unsigned char *pan_2ch, int height, int width, const unsigned *table, double min_score,
+                            unsigned char *out_2ch);
 
 /* ============================== Video metrics of tracked sequences: VPQ and STQ ============================== */
 

@@ -92,6 +92,7 @@ _SIGNATURES = {
     "upsnet_seg_term": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_int, P]),
     "upsnet_panoptic_fuse": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, P, c_int, P, P]),
     "upsnet_panoptic_fuse_up": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, P, P, P]),
+    "upsnet_panoptic_fuse_up_conf": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_int, P, P, P, P]),
     "upsnet_conv2d_stem_nhwc4_f32": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "upsnet_conv_pack_weight_stem": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "upsnet_deconv2x2_nhwc_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, c_int, P]),
@@ -135,6 +136,7 @@ _SIGNATURES = {
     "upsnet_pq_boundary_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "upsnet_pq_boundary_accumulate": (c_int, [P, c_int, P, P, c_int, c_int, P, c_int, P, c_int, c_int, P, P, P, P, P, P]),
     "upsnet_restore_label_maps": (c_int, [P, P, P, c_long, c_int, c_int, P, c_int, P, c_int, P, P]),
+    "upsnet_restore_plane_u8": (c_int, [P, P, c_long, c_int, c_int, P, c_int, P, c_int, P]),
     "upsnet_confusion_accumulate": (c_int, [P, P, P, c_long, c_int, c_int, P]),
     "upsnet_det_eval_image_workspace_bytes": (c_size_t, [c_int] * 6),
     "upsnet_det_eval_image": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, c_int, c_int, P, P, c_int, P, P, P, P,
@@ -198,6 +200,10 @@ _SIGNATURES = {
     "upsnet_pan_components": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
     "upsnet_pan_absorb_workspace_bytes": (c_size_t, [c_int, c_int]),
     "upsnet_pan_absorb": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "upsnet_pan_segment_scores_workspace_bytes": (c_size_t, []),
+    "upsnet_pan_segment_scores_table_ints": (c_size_t, []),
+    "upsnet_pan_segment_scores": (c_int, [P, P, P, c_int, c_int, P, P]),
+    "upsnet_pan_score_filter": (c_int, [P, P, c_int, c_int, P, c_double, P]),
     "upsnet_video_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "upsnet_video_eval_sequence_ints": (c_size_t, []),
     "upsnet_video_eval_frame": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),

@@ -110,6 +110,17 @@ config.test.pan_component_keep_largest = True
 # 'void': such a component becomes VOID; 'absorb' (DESIGN 4.27): it takes the (category, instance) of the kept segment it shares the
 # longest border with, and becomes VOID only where it borders none
 config.test.pan_component_mode = 'void'
+# panoptic confidence (csrc/panoptic.hip: panoptic_fuse_up_conf_kernel, csrc/pan_confidence.hip; the reference keeps the
+# arg-max only): with pan_confidence the model also returns 'panoptic_conf', one byte per pixel = 255 x the softmax over the panoptic
+# logits at the winning label; the evaluation then writes a "score" per segment. pan_min_score > 0 (implies pan_confidence) turns every
+# unified segment whose mean confidence is below it into VOID before the maps are cleaned, scored, written or drawn.
+config.test.pan_confidence = False
+config.test.pan_min_score = 0.0
+
+
+def pan_confidence_wanted():
+    """config.test.pan_confidence, or a pan_min_score that needs it"""
+    return bool(config.test.get('pan_confidence', False)) or config.test.get('pan_min_score', 0.0) > 0
 
 
 def _merge(dst, src):

@@ -139,6 +139,16 @@ def parse_args(description='', argv=None):
     parser.add_argument('--soft_nms_sigma', type=float, default=None, metavar='S',
                         help='with --soft_nms: sets config.test.soft_nms_sigma, the width of the gaussian decay (default 0.5)')
     add_pan_component_arguments(parser, 'scored, written or drawn')
+    parser.add_argument('--pan_confidence', action='store_true',
+                        help='sets config.test.pan_confidence: the panoptic head also returns its confidence, one byte per pixel (255 x '
+                        'the softmax over the panoptic logits at the winning label); --write_panoptic then writes a "score" per segment '
+                        'of the unified result, its mean confidence')
+    parser.add_argument('--pan_min_score', type=float, default=None, metavar='T',
+                        help='sets config.test.pan_min_score (implies --pan_confidence): every segment of the unified panoptic result whose '
+                        'mean confidence is below T (0..1) becomes VOID before the maps are cleaned, scored, written or drawn; 0 = off')
+    parser.add_argument('--write_pan_confidence', action='store_true',
+                        help='with --write_panoptic and --pan_confidence (or --pan_min_score): also write the confidence planes as 8-bit '
+                        'grey PNGs to results/pans_unified/conf')
     args, rest = parser.parse_known_args(argv)
     if args.cfg:
         update_config(args.cfg)
@@ -162,6 +172,15 @@ def parse_args(description='', argv=None):
                 parser.error('--%s is a parameter of --soft_nms, which is missing' % name)
             config.test[name] = getattr(args, name)
     apply_pan_component_arguments(args, parser.error)
+    if args.pan_confidence:
+        config.test.pan_confidence = True
+    if args.pan_min_score is not None:
+        config.test.pan_min_score = float(args.pan_min_score)
+    t = config.test.get('pan_min_score', 0.0)
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not (0.0 <= t <= 1.0):
+        parser.error('--pan_min_score (test.pan_min_score) must be a number in 0..1, got %r' % (t,))
+    if not isinstance(config.test.get('pan_confidence', False), bool):
+        parser.error('test.pan_confidence must be true or false, got %r' % (config.test.pan_confidence,))
     if rest:    # (the reference re-parses strictly, parse_args.py:32; an option neither parser knows is reported, not swallowed)
         parser.error('unrecognized arguments: %s' % ' '.join(rest))
     return args

@@ -695,14 +695,16 @@ __device__ static inline UpCoef fup_coef(int dst, float r, int src_size)
     return c;
 }
 
-template <int SCALE>
-__global__ void __launch_bounds__(256)
-panoptic_fuse_up_kernel(const float *__restrict__ score, const long pix_stride, const long ch_stride, const int S,
-                        const int Hs, const int Ws, const int s_stuff, const float *__restrict__ mask_rois,
-                        const float *__restrict__ logits, const int64_t *__restrict__ cls_idx,
-                        const int64_t *__restrict__ keep_inds, const int *__restrict__ num_keep,
-                        const int *__restrict__ real_keep, const int ms, const int64_t *__restrict__ class_map,
-                        const int enable_void, int64_t *__restrict__ pan, int64_t *__restrict__ sem)
+// The body of both kernels below. CONF: also the confidence of the winner (include/upsnet_hip.h: upsnet_panoptic_fuse_up_conf), one
+// byte per pixel into `conf`; without it `conf` is never touched and every CONF statement folds away (profiles/pan_confidence.txt: the
+// label-only kernel's registers, LDS and occupancy are what they were before the body was shared).
+template <int SCALE, bool CONF>
+__device__ __forceinline__ void
+fup_tile(const float *__restrict__ score, const long pix_stride, const long ch_stride, const int S, const int Hs, const int Ws,
+         const int s_stuff, const float *__restrict__ mask_rois, const float *__restrict__ logits, const int64_t *__restrict__ cls_idx,
+         const int64_t *__restrict__ keep_inds, const int *__restrict__ num_keep, const int *__restrict__ real_keep, const int ms,
+         const int64_t *__restrict__ class_map, const int enable_void, int64_t *__restrict__ pan, int64_t *__restrict__ sem,
+         unsigned char *__restrict__ conf)
 {
     constexpr int SW = FUP_TW / SCALE + 2, SH = FUP_TH / SCALE + 2;  // source patch incl. halo
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -821,36 +823,117 @@ panoptic_fuse_up_kernel(const float *__restrict__ score, const long pix_stride, 
             if (inseg) { if (si > mi_listed[q]) mi_listed[q] = si; ++n_in[q]; }
         }
     }
+    float zmax[4], zvoid[4];   // CONF: the winner's logit and the void logit
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int x = x0 + q;
+        if (CONF) { zmax[q] = best[q]; zvoid[q] = best[q]; }
         if (x >= W) continue;
         float m = mi_listed[q];
         if (n_in[q] < k) m = fmaxf(m, 0.f);
         int64_t lab = bi[q];
-        if (enable_void) { const float vd = tmax[q] - m; if (vd > best[q]) lab = 255; }
+        if (enable_void) {
+            const float vd = tmax[q] - m;
+            if (vd > best[q]) lab = 255;
+            if (CONF) { zvoid[q] = vd; zmax[q] = fmaxf(best[q], vd); }
+        }
         pan[(long)y * W + x] = lab;
         if (sem) sem[(long)y * W + x] = sbi[q];
+    }
+    if (CONF) {
+        // conf = P[winner] = 1 / sum_c exp(z_c - z_max) over the stuff channels, ALL k instance channels and the void channel: a second
+        // walk over the same logits now that z_max is known (every term <= 1, the winner's is exactly 1). The first-zero shortcut of
+        // the arg-max does not carry over: each of the k - nlist instances that touch the tile nowhere has the logit 0 and adds
+        // exp(0 - z_max), the same term, added once with its count.
+        float sum[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < s_stuff; ++c) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sum[q] += __expf(FUP_AT(c, q) - zmax[q]);
+        }
+        for (int li = 0; li < nlist; ++li) {
+            const FuseInst &fi = s_inst[s_list[li]];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int x = x0 + q;
+                float si = 0.f, mk = 0.f;
+                if (x < W) {
+                    if (fi.sem_ch >= 0 && y >= fi.sb.y0 && y < fi.sb.y1 && x >= fi.sb.x0 && x < fi.sb.x1) si = FUP_AT(fi.sem_ch, q);
+                    if (real && y >= fi.mb.y_0 && y < fi.mb.y_1 && x >= fi.mb.x_0 && x < fi.mb.x_1)
+                        mk = pan_resize_at(logits + fi.logit_off, ms, fi.mb.w, fi.mb.h, x - fi.mb.bx0, y - fi.mb.by0);
+                }
+                sum[q] += __expf((si + mk) - zmax[q]);
+            }
+        }
+        const float untouched = (float)(k - nlist);
+        unsigned packed = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (k > nlist) sum[q] += untouched * __expf(0.f - zmax[q]);
+            if (enable_void) sum[q] += __expf(zvoid[q] - zmax[q]);
+            const float c = 1.0f / sum[q];
+            packed |= ((unsigned)(c * 255.0f + 0.5f) & 255u) << (8 * q);
+        }
+        // W = 4 Ws and x0 are multiples of 4 (and `conf` 4-byte aligned): the thread's four bytes are one aligned word, all inside the row
+        *reinterpret_cast<unsigned *>(conf + (long)y * W + x0) = packed;
     }
 #undef FUP_AT
 }
 
-extern "C" int upsnet_panoptic_fuse_up(void *stream, const float *fcn_score, int score_nhwc, int num_seg, int score_h, int score_w,
-                                       int scale, int num_stuff, const float *mask_rois, const float *mask_logit,
-                                       const int64_t *cls_idx, const int64_t *keep_inds, const int *num_keep, const int *real_keep,
-                                       int kmax, int mask_size, const int64_t *class_map, int64_t *pan_out, int64_t *sem_out)
+template <int SCALE>
+__global__ void __launch_bounds__(256)
+panoptic_fuse_up_kernel(const float *__restrict__ score, const long pix_stride, const long ch_stride, const int S,
+                        const int Hs, const int Ws, const int s_stuff, const float *__restrict__ mask_rois,
+                        const float *__restrict__ logits, const int64_t *__restrict__ cls_idx,
+                        const int64_t *__restrict__ keep_inds, const int *__restrict__ num_keep,
+                        const int *__restrict__ real_keep, const int ms, const int64_t *__restrict__ class_map,
+                        const int enable_void, int64_t *__restrict__ pan, int64_t *__restrict__ sem)
+{
+    fup_tile<SCALE, false>(score, pix_stride, ch_stride, S, Hs, Ws, s_stuff, mask_rois, logits, cls_idx, keep_inds, num_keep, real_keep, ms,
+                           class_map, enable_void, pan, sem, nullptr);
+}
+
+// The sibling with the confidence plane: a separate kernel, so that the label-only one keeps its registers and its occupancy.
+template <int SCALE>
+__global__ void __launch_bounds__(256)
+panoptic_fuse_up_conf_kernel(const float *__restrict__ score, const long pix_stride, const long ch_stride, const int S,
+                             const int Hs, const int Ws, const int s_stuff, const float *__restrict__ mask_rois,
+                             const float *__restrict__ logits, const int64_t *__restrict__ cls_idx,
+                             const int64_t *__restrict__ keep_inds, const int *__restrict__ num_keep,
+                             const int *__restrict__ real_keep, const int ms, const int64_t *__restrict__ class_map,
+                             const int enable_void, int64_t *__restrict__ pan, int64_t *__restrict__ sem,
+                             unsigned char *__restrict__ conf)
+{
+    fup_tile<SCALE, true>(score, pix_stride, ch_stride, S, Hs, Ws, s_stuff, mask_rois, logits, cls_idx, keep_inds, num_keep, real_keep, ms,
+                          class_map, enable_void, pan, sem, conf);
+}
+
+// both entry points: `name` words the errors; conf_out == nullptr launches the label-only kernel
+static int fup_launch(const char *name, void *stream, const float *fcn_score, int score_nhwc, int num_seg, int score_h, int score_w,
+                      int scale, int num_stuff, const float *mask_rois, const float *mask_logit, const int64_t *cls_idx,
+                      const int64_t *keep_inds, const int *num_keep, const int *real_keep, int kmax, int mask_size,
+                      const int64_t *class_map, int64_t *pan_out, int64_t *sem_out, unsigned char *conf_out)
 {
     UPS_REQUIRE(fcn_score && mask_rois && mask_logit && cls_idx && keep_inds && num_keep && real_keep && class_map && pan_out,
-                "panoptic_fuse_up: null pointer");
-    UPS_REQUIRE(scale == 4, "panoptic_fuse_up: only the x4 upsampling of FCNHead (upsample_rate=4) is built (got %d)", scale);
-    UPS_REQUIRE(num_stuff >= 1 && num_stuff < num_seg && num_seg <= FUP_MAXS, "panoptic_fuse_up: bad channel split %d/%d", num_stuff, num_seg);
-    UPS_REQUIRE(kmax >= 1 && kmax <= FUSE_MAXK, "panoptic_fuse_up: at most %d instances supported (got %d)", FUSE_MAXK, kmax);
-    UPS_REQUIRE(mask_size >= 2 && mask_size <= PAN_MAXMS, "panoptic_fuse_up: bad mask size");
+                "%s: null pointer", name);
+    UPS_REQUIRE(scale == 4, "%s: only the x4 upsampling of FCNHead (upsample_rate=4) is built (got %d)", name, scale);
+    UPS_REQUIRE(num_stuff >= 1 && num_stuff < num_seg && num_seg <= FUP_MAXS, "%s: bad channel split %d/%d", name, num_stuff, num_seg);
+    UPS_REQUIRE(kmax >= 1 && kmax <= FUSE_MAXK, "%s: at most %d instances supported (got %d)", name, FUSE_MAXK, kmax);
+    UPS_REQUIRE(mask_size >= 2 && mask_size <= PAN_MAXMS, "%s: bad mask size", name);
     const int H = score_h * scale, W = score_w * scale;
     const int tiles = ((W + FUP_TW - 1) / FUP_TW) * ((H + FUP_TH - 1) / FUP_TH);
     const size_t smem = (size_t)num_seg * (FUP_TH / 4 + 2) * (FUP_TW / 4 + 2) * sizeof(float) + FUSE_MAXK * (sizeof(FuseInst) + sizeof(int) + 1) + 16;
     const long pix_stride = score_nhwc ? num_seg : 1, ch_stride = score_nhwc ? 1 : (long)score_h * score_w;
-    static std::atomic<unsigned long long> attr_dev{0};
+    static std::atomic<unsigned long long> attr_dev{0}, attr_dev_conf{0};
+    if (conf_out) {
+        if (smem > 64 * 1024)
+            UPS_ONCE_PER_DEVICE(attr_dev_conf, UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&panoptic_fuse_up_conf_kernel<4>),
+                                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)));
+        hipLaunchKernelGGL(panoptic_fuse_up_conf_kernel<4>, dim3(tiles), dim3(256), smem, (hipStream_t)stream, fcn_score, pix_stride,
+                           ch_stride, num_seg, score_h, score_w, num_stuff, mask_rois, mask_logit, cls_idx, keep_inds, num_keep, real_keep,
+                           mask_size, class_map, 1, pan_out, sem_out, conf_out);
+        UPS_CHECK_LAUNCH("panoptic_fuse_up_conf_kernel");
+        return 0;
+    }
     if (smem > 64 * 1024)
         UPS_ONCE_PER_DEVICE(attr_dev, UPS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&panoptic_fuse_up_kernel<4>),
                                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)));
@@ -860,3 +943,24 @@ extern "C" int upsnet_panoptic_fuse_up(void *stream, const float *fcn_score, int
     UPS_CHECK_LAUNCH("panoptic_fuse_up_kernel");
     return 0;
 }
+
+extern "C" int upsnet_panoptic_fuse_up(void *stream, const float *fcn_score, int score_nhwc, int num_seg, int score_h, int score_w,
+                                       int scale, int num_stuff, const float *mask_rois, const float *mask_logit,
+                                       const int64_t *cls_idx, const int64_t *keep_inds, const int *num_keep, const int *real_keep,
+                                       int kmax, int mask_size, const int64_t *class_map, int64_t *pan_out, int64_t *sem_out)
+{
+    return fup_launch("panoptic_fuse_up", stream, fcn_score, score_nhwc, num_seg, score_h, score_w, scale, num_stuff, mask_rois, mask_logit,
+                      cls_idx, keep_inds, num_keep, real_keep, kmax, mask_size, class_map, pan_out, sem_out, nullptr);
+}
+
+extern "C" int upsnet_panoptic_fuse_up_conf(void *stream, const float *fcn_score, int score_nhwc, int num_seg, int score_h, int score_w,
+                                            int scale, int num_stuff, const float *mask_rois, const float *mask_logit,
+                                            const int64_t *cls_idx, const int64_t *keep_inds, const int *num_keep, const int *real_keep,
+                                            int kmax, int mask_size, const int64_t *class_map, int64_t *pan_out, int64_t *sem_out,
+                                            unsigned char *conf_out)
+{
+    UPS_REQUIRE(conf_out && ((uintptr_t)conf_out & 3) == 0, "panoptic_fuse_up_conf: conf_out null or not 4-byte aligned");
+    return fup_launch("panoptic_fuse_up_conf", stream, fcn_score, score_nhwc, num_seg, score_h, score_w, scale, num_stuff, mask_rois,
+                      mask_logit, cls_idx, keep_inds, num_keep, real_keep, kmax, mask_size, class_map, pan_out, sem_out, conf_out);
+}
+

@@ -13,19 +13,17 @@
 #define RS_CHUNK 16
 #define RS_BLOCK 256
 
-__global__ void __launch_bounds__(RS_BLOCK)
-restore_label_maps_kernel(const int64_t *__restrict__ src0, const int64_t *__restrict__ src1, const long stride, const int src_h,
-                          const int src_w, const int *__restrict__ y_ofs, const int *__restrict__ x_ofs, const int out_h, const int out_w,
-                          unsigned char *__restrict__ dst0, unsigned char *__restrict__ dst1)
+// one thread's chunk of the gather from a plane of T (the low byte of an element is kept)
+template <class T>
+__device__ static inline void rs_gather_chunk(const T *__restrict__ src, const long stride, const int src_h, const int src_w,
+                                              const int *__restrict__ y_ofs, const int *__restrict__ x_ofs, const int out_h, const int out_w,
+                                              unsigned char *__restrict__ dst)
 {
-    // blockIdx.y selects the map: 0 = semantic, 1 = panoptic (grid.y is 1 when there is no panoptic map)
-    const int64_t *__restrict__ src = blockIdx.y ? src1 : src0;
-    unsigned char *__restrict__ dst = blockIdx.y ? dst1 : dst0;
     const long npix = (long)out_h * out_w;
     const long p0 = ((long)blockIdx.x * RS_BLOCK + threadIdx.x) * RS_CHUNK;
     if (p0 >= npix) return;
     int y = (int)(p0 / out_w), x = (int)(p0 - (long)y * out_w);
-    const int64_t *row = src + (long)min(max(y_ofs[y], 0), src_h - 1) * stride;
+    const T *row = src + (long)min(max(y_ofs[y], 0), src_h - 1) * stride;
     unsigned w[RS_CHUNK / 4] = {0u, 0u, 0u, 0u};
     const int n = (int)min((long)RS_CHUNK, npix - p0);
 #pragma unroll
@@ -51,6 +49,24 @@ restore_label_maps_kernel(const int64_t *__restrict__ src0, const int64_t *__res
     }
 }
 
+__global__ void __launch_bounds__(RS_BLOCK)
+restore_label_maps_kernel(const int64_t *__restrict__ src0, const int64_t *__restrict__ src1, const long stride, const int src_h,
+                          const int src_w, const int *__restrict__ y_ofs, const int *__restrict__ x_ofs, const int out_h, const int out_w,
+                          unsigned char *__restrict__ dst0, unsigned char *__restrict__ dst1)
+{
+    // blockIdx.y selects the map: 0 = semantic, 1 = panoptic (grid.y is 1 when there is no panoptic map)
+    rs_gather_chunk(blockIdx.y ? src1 : src0, stride, src_h, src_w, y_ofs, x_ofs, out_h, out_w, blockIdx.y ? dst1 : dst0);
+}
+
+// the same gather for a uint8 plane (the panoptic confidence)
+__global__ void __launch_bounds__(RS_BLOCK)
+restore_plane_u8_kernel(const unsigned char *__restrict__ src, const long stride, const int src_h, const int src_w,
+                        const int *__restrict__ y_ofs, const int *__restrict__ x_ofs, const int out_h, const int out_w,
+                        unsigned char *__restrict__ dst)
+{
+    rs_gather_chunk(src, stride, src_h, src_w, y_ofs, x_ofs, out_h, out_w, dst);
+}
+
 extern "C" int upsnet_restore_label_maps(void *stream, const int64_t *sseg, const int64_t *pano, long src_stride, int src_height,
                                          int src_width, const int *y_ofs, int out_height, const int *x_ofs, int out_width,
                                          unsigned char *out_sseg, unsigned char *out_pano)
@@ -69,5 +85,24 @@ extern "C" int upsnet_restore_label_maps(void *stream, const int64_t *sseg, cons
     hipLaunchKernelGGL(restore_label_maps_kernel, dim3((unsigned)blocks, pano ? 2 : 1), dim3(RS_BLOCK), 0, (hipStream_t)stream, sseg,
                        pano, src_stride, src_height, src_width, y_ofs, x_ofs, out_height, out_width, out_sseg, out_pano);
     UPS_CHECK_LAUNCH("restore_label_maps_kernel");
+    return 0;
+}
+
+extern "C" int upsnet_restore_plane_u8(void *stream, const unsigned char *src, long src_stride, int src_height, int src_width,
+                                       const int *y_ofs, int out_height, const int *x_ofs, int out_width, unsigned char *out)
+{
+    UPS_REQUIRE(src && y_ofs && x_ofs && out, "restore_plane_u8: null pointer");
+    UPS_REQUIRE(src_height >= 1 && src_width >= 1 && src_stride >= src_width, "restore_plane_u8: bad source %d x %d, stride %ld", src_height,
+                src_width, src_stride);
+    UPS_REQUIRE(out_height >= 0 && out_width >= 0 && (long)out_height * out_width < (1L << 40), "restore_plane_u8: bad output %d x %d",
+                out_height, out_width);
+    const long npix = (long)out_height * out_width;
+    if (npix == 0) return 0;
+    const long threads = (npix + RS_CHUNK - 1) / RS_CHUNK;
+    const long blocks = (threads + RS_BLOCK - 1) / RS_BLOCK;
+    UPS_REQUIRE(blocks < (1L << 31), "restore_plane_u8: output of %ld pixels too large", npix);
+    hipLaunchKernelGGL(restore_plane_u8_kernel, dim3((unsigned)blocks), dim3(RS_BLOCK), 0, (hipStream_t)stream, src, src_stride, src_height,
+                       src_width, y_ofs, x_ofs, out_height, out_width, out);
+    UPS_CHECK_LAUNCH("restore_plane_u8_kernel");
     return 0;
 }

@@ -156,6 +156,26 @@ class BaseDataset(object):
                             len(cleaned), connectivity, kept, absorbed, absorbed_pixels)
         return cleaned
 
+    def score_pan_segments(self, pans, confs):
+        """One dictionary per map, {(category, instance): (area, sum_q, score)}: the mean panoptic confidence of every segment of
+        get_unified_pan_result's maps (dataset/pan_confidence.segment_scores); confs: the confidence planes of the same
+        images at the maps' size (results['all_pano_confs'])."""
+        from .pan_confidence import segment_scores
+        pans, confs = list(pans), list(confs)
+        if len(pans) != len(confs):
+            raise ValueError("%d maps and %d confidence planes" % (len(pans), len(confs)))
+        return [segment_scores(p, c) for p, c in zip(pans, confs)]
+
+    def filter_pan_result(self, pans, confs, min_score=None, what='unified pano result'):
+        """get_unified_pan_result's maps with every segment whose mean confidence is below min_score (default:
+        config.test.pan_min_score) turned into VOID (dataset/pan_confidence.filter_by_score). Logs the segments removed
+        over all maps, once."""
+        from .pan_confidence import filter_by_score
+        min_score = config.test.pan_min_score if min_score is None else min_score
+        kept, (before, after) = filter_by_score(pans, confs, min_score, return_stats=True)
+        logger.info('%s: %d of %d segments of mean confidence below %g removed from %d maps', what, before - after, before, min_score, len(kept))
+        return kept
+
     def load_panoptic_gt(self):
         """(images, annotations, categories) of self.panoptic_json_file; images yields the uint8 [H,W,3] GT PNGs of
         self.panoptic_gt_folder in the JSON's 'images' order (as the reference loads them), lazily."""
@@ -191,13 +211,16 @@ class BaseDataset(object):
             ev.add(pred, gt, ann['segments_info'])
         return ev.summary()
 
-    def write_panoptic(self, pred_pans_2ch, output_dir, categories=None, categories_json=None):
+    def write_panoptic(self, pred_pans_2ch, output_dir, categories=None, categories_json=None, confs=None, write_conf=False):
         """The files of the reference's evaluate_panoptic (:321-327): output_dir/pan_2ch/*.png, pan/*.png, pred.json and -- with ground
         truth -- gt.json (dataset/pan_format.write_panoptic: colours, naming, deviations). With ground truth the predictions are
         those of evaluate_panoptic (one per annotation of self.panoptic_json_file, in its order); names come from the JSON's
         'images', image ids from its annotations, categories from its 'categories'. A set without ground truth (has_gt false) takes
         names and ids from the image list, and its categories from `categories` (a table as PanopticEvaluator takes it) or from the
-        'categories' of the panoptic JSON `categories_json`; ValueError if neither is given. Returns the annotations written."""
+        'categories' of the panoptic JSON `categories_json`; ValueError if neither is given. Returns the annotations written.
+        confs (the confidence planes of the same images): every segments_info entry gains "score", the mean confidence of
+        the segment on the map as written; write_conf: the planes also go to output_dir/conf/*.png as 8-bit grey. Without confs the
+        files are what they always were."""
         from .pan_format import write_panoptic
         if getattr(self, 'has_gt', True):
             with open(self.panoptic_json_file, 'r') as f:
@@ -219,7 +242,7 @@ class BaseDataset(object):
             with open(categories_json, 'r') as f:
                 categories = json.load(f)['categories']
         os.makedirs(output_dir, exist_ok=True)
-        annotations = write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=image_ids)
+        annotations = write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=image_ids, confs=confs, write_conf=write_conf)
         if gt_json is not None:
             with open(os.path.join(output_dir, 'gt.json'), 'w') as f:
                 json.dump(gt_json, f)

@@ -253,15 +253,23 @@ def _save_png(array, path):
     Image.fromarray(array).save(path)
 
 
-def write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=None, stable_ids=False):
+def write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=None, stable_ids=False, confs=None, write_conf=False):
     """Write output_dir/pan_2ch/<name>.png (the 2-channel maps), output_dir/pan/<name>.png (the panoptic PNGs) and
     output_dir/pred.json ({'annotations': [{'image_id', 'file_name', 'segments_info'}]}); name = png_name(images[i]['file_name']),
     image_id = image_ids[i] if given, else images[i]['id']. Returns the annotations. ValueError before any launch: counts that do
     not match, an image without file_name (or id), two images of one output name, a map that is not uint8 [H,W,3]. stable_ids: the
-    frame-stable ids and colours of the module's docstring (for tracked maps)."""
+    frame-stable ids and colours of the module's docstring (for tracked maps). confs (one uint8 [H,W] confidence plane per map, device
+    tensors or numpy arrays): every segments_info entry gains "score" = the mean confidence of the segment over 255
+    (dataset/pan_confidence.segment_scores, on the map as given); write_conf: the planes are also written to
+    output_dir/conf/<name>.png, 8-bit grey. Without confs every file is byte for byte what it is without the argument."""
     preds, images = list(pred_pans_2ch), list(images)
     if len(preds) != len(images):
         raise ValueError("%d predictions for %d images" % (len(preds), len(images)))
+    confs = None if confs is None else list(confs)
+    if confs is not None and len(confs) != len(preds):
+        raise ValueError("%d confidence planes for %d predictions" % (len(confs), len(preds)))
+    if write_conf and confs is None:
+        raise ValueError("write_conf needs the confidence planes (confs=)")
     if image_ids is not None and len(image_ids) != len(images):
         raise ValueError("%d image ids for %d images" % (len(image_ids), len(images)))
     names = []
@@ -275,7 +283,7 @@ def write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=None
     for pred in preds:
         _check_image('pred_2ch', pred)
     fmt = PanopticFormatter(categories, stable_ids=stable_ids)
-    for sub in ('pan_2ch', 'pan'):
+    for sub in ('pan_2ch', 'pan') + (('conf',) if write_conf else ()):
         for name in names:
             os.makedirs(os.path.dirname(os.path.join(output_dir, sub, name)), exist_ok=True)
     annotations = [None] * len(preds)
@@ -285,6 +293,18 @@ def write_panoptic(pred_pans_2ch, images, categories, output_dir, image_ids=None
 
         def retire(p, k):
             _, rgb_host, segments_info = fmt.finish(p)
+            if confs is not None:     # (both tables list the non-VOID keys of one map in ascending key)
+                from .pan_confidence import segment_scores
+                scores = segment_scores(preds[k], confs[k])
+                if len(scores) != len(segments_info):
+                    raise RuntimeError("image %d: %d scored segments for %d written ones" % (k, len(scores), len(segments_info)))
+                for seg, ((cat, _), (_, _, score)) in zip(segments_info, scores.items()):
+                    if seg['category_id'] != cat:
+                        raise RuntimeError("image %d: score of category %d for a segment of category %d" % (k, cat, seg['category_id']))
+                    seg['score'] = score
+                if write_conf:
+                    plane = confs[k].cpu().numpy() if isinstance(confs[k], torch.Tensor) else np.asarray(confs[k])
+                    jobs.append(pool.submit(_save_png, np.ascontiguousarray(plane), os.path.join(output_dir, 'conf', names[k])))
             annotations[k] = {'image_id': ids[k], 'file_name': names[k], 'segments_info': segments_info}
             jobs.append(pool.submit(_save_png, p.pred_host, os.path.join(output_dir, 'pan_2ch', names[k])))
             jobs.append(pool.submit(_save_png, rgb_host, os.path.join(output_dir, 'pan', names[k])))

@@ -56,3 +56,10 @@ def restore_to_image(sseg, pano, im_info):
     resolution; pano may be None) -> uint8 device maps at the original image resolution, one launch for both."""
     y_ofs, x_ofs = cv2_nearest_tables(im_info)
     return ops.restore_label_maps(sseg, pano, y_ofs, x_ofs)
+
+
+def restore_plane_to_image(plane, im_info):
+    """restore_to_image's gather for a uint8 plane at network resolution (the panoptic confidence): the same tables, so a
+    pixel of the restored plane belongs to the pixel of the restored label maps."""
+    y_ofs, x_ofs = cv2_nearest_tables(im_info)
+    return ops.restore_plane_u8(plane, y_ofs, x_ofs)

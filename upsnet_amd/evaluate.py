@@ -9,6 +9,7 @@
                                   [--eval_boundary_pq [--boundary_pq_dilation_ratio R]] [--aug_scales S [S ...]] [--aug_flip]
                                   [--bbox_vote [--bbox_vote_thresh T]] [--soft_nms [--soft_nms_method M] [--soft_nms_sigma S]]
                                   [--pan_min_component N [--pan_component_connectivity {4,8}]]
+                                  [--pan_confidence] [--pan_min_score T] [--write_pan_confidence]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_panoptic <pred.json> [--score_panoptic_folder <dir>] [--eval_boundary_pq ...]
     python -m upsnet_amd.evaluate --cfg <yaml> --score_ssegs <folder>
     python -m upsnet_amd.evaluate --cfg <yaml> --score_instances <folder>
@@ -70,6 +71,14 @@ or drawn (csrc/pan_components.hip): a connected component of a (cat
 VOID, the largest component of the pair excepted; the results pickle is not changed, so `--eval_only` may try another N. With
 `--pan_component_mode absorb` (or `test.pan_component_mode`) such a component takes the pair of the segment it shares the
 longest border with, and becomes VOID only where it borders none.
+`--pan_confidence` (or `test.pan_confidence`) makes the panoptic head also return its confidence, one byte per pixel: 255 x
+the softmax over the panoptic logits at the winning label (csrc/panoptic.hip). The planes are restored beside the label maps and
+pickled as 'all_pano_confs', so `--eval_only` can score again; `--write_panoptic` then writes a "score" per segment of the unified
+result, its mean confidence on the map as written, and `--write_pan_confidence` the planes as grey PNGs to results/pans_unified/conf.
+`--pan_min_score T` (or `test.pan_min_score`; implies the above) turns every unified segment of a mean confidence below T into VOID
+(csrc/pan_confidence.hip) after get_unified_pan_result and before the fragment cleaning; a results pickle written without the option
+holds no planes, and using it with the option raises a ValueError that says so. The combined merge has no panoptic logits: with
+`--pan_combined` only the unified result is scored or filtered (logged once).
 One rank only (WORLD_SIZE > 1 is refused)."""
 import logging
 import os
@@ -80,7 +89,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .config.config import config
+from .config.config import config, pan_confidence_wanted
 
 logger = logging.getLogger(__name__)
 
@@ -115,12 +124,14 @@ def scale_boxes(pred_boxes, im_info):
     return pred_boxes[:, 1:].float().cpu().numpy() / np.float32(im_info[2])
 
 
-def post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds, all_proposals=None):
+def post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds, all_proposals=None,
+               all_pano_confs=None):
     """One image's share of the reference's loop after the network (upsnet_end2end_test.py:254-272): appends to the result lists;
-    with all_proposals (a list), also the box head's proposals at the original image scale (scale_boxes' rule), float32 [n, 4]."""
+    with all_proposals (a list), also the box head's proposals at the original image scale (scale_boxes' rule), float32 [n, 4]; with
+    all_pano_confs (a list), also the panoptic confidence plane restored beside the label maps (config.test.pan_confidence)."""
     if all_proposals is not None:
         all_proposals.append(scale_boxes(out['proposals'], im_info))
-    from .dataset.restore import restore_to_image
+    from .dataset.restore import restore_plane_to_image, restore_to_image
     from .dataset.rle import im_post
     net = config.network
     if net.has_rcnn:
@@ -142,6 +153,8 @@ def post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_p
         if net.has_panoptic_head:
             all_panos.append(pano.cpu().numpy())
             all_pano_cls_inds.append(out['panoptic_cls_inds'].cpu().numpy())
+            if all_pano_confs is not None:
+                all_pano_confs.append(restore_plane_to_image(out['panoptic_conf'], im_info).cpu().numpy())
 
 
 def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False):
@@ -155,6 +168,7 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
     all_ssegs = [] if net.has_fcn_head else None
     all_panos, all_pano_cls_inds = ([], []) if net.has_panoptic_head else (None, None)
     all_proposals = [] if keep_proposals else None
+    all_pano_confs = [] if net.has_panoptic_head and pan_confidence_wanted() else None
     from .tta import augmentation_list, bbox_vote_params, eager_path_enabled, soft_nms_params
     test_aug = augmentation_list() if eager_path_enabled() else None     # (box voting / soft-NMS alone: the base augmentation, eagerly)
     bbox_vote = bbox_vote_params()
@@ -180,7 +194,7 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
         t1 = time.perf_counter()
         # (with keep_proposals, out['proposals'] may be a view of a graph slot's buffer: it is read here, after the synchronise
         # above and before that slot's next replay -- the next image of the slot is launched only after this finish())
-        post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds, all_proposals)
+        post_image(out, im_info, num_classes, all_boxes, all_masks, all_ssegs, all_panos, all_pano_cls_inds, all_proposals, all_pano_confs)
         post_time = time.perf_counter() - t1
         # net_time: host time blocked on the network for this image (launch + wait); with one image in flight that is the
         # reference's forward + synchronize
@@ -215,6 +229,8 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
                'all_pano_cls_inds': all_pano_cls_inds}
     if keep_proposals:
         results['all_proposals'] = all_proposals
+    if all_pano_confs is not None:
+        results['all_pano_confs'] = all_pano_confs
     if test_aug is not None:
         results['test_aug'] = [list(a) for a in test_aug]
     if bbox_vote is not None:
@@ -224,15 +240,38 @@ def run_inference(model, dataset, in_flight=1, device=None, keep_proposals=False
     return results, times
 
 
+_COMBINED_NOTE = []     # (the note about the combined merge is logged once per process)
+
+
+def panoptic_confs(results, combined, order):
+    """The confidence planes that go with panoptic_predictions' maps, or None: the option is off, or the maps are the combined merge's,
+    which has no panoptic logits (logged once). ValueError: the option needs planes that an older result file does not hold."""
+    if not pan_confidence_wanted():
+        return None
+    if combined:
+        if not _COMBINED_NOTE:
+            _COMBINED_NOTE.append(True)
+            logger.info('panoptic confidence: the combined merge has no panoptic logits; only the unified result is scored or filtered')
+        return None
+    if results.get('all_pano_confs') is None:
+        raise ValueError("test.pan_confidence / test.pan_min_score need the confidence planes, and these results hold none "
+                         "('all_pano_confs' is missing: the result file was written without the option; run the inference again)")
+    return [results['all_pano_confs'][k] for k in order]
+
+
 def panoptic_predictions(dataset, results, combined, order=None):
     """The 2-channel maps of the results, unified (the panoptic head's) or combined (the heuristic merge), one per entry of `order`
-    (positions in the image list; default: the image list's own order). With config.test.pan_min_component > 0 the maps pass through
-    dataset.clean_pan_result first (disconnected fragments become VOID): scoring, writing and drawing see the same maps."""
+    (positions in the image list; default: the image list's own order). With config.test.pan_min_score > 0 the unified maps first lose
+    the segments of a lower mean confidence (dataset.filter_pan_result). With config.test.pan_min_component > 0 the maps
+    then pass through dataset.clean_pan_result (disconnected fragments become VOID): scoring, writing and drawing see the
+    same maps."""
     order = list(range(len(dataset))) if order is None else order
     if not combined:
         pans = dataset.get_unified_pan_result([results['all_ssegs'][k] for k in order], [results['all_panos'][k] for k in order],
                                               [results['all_pano_cls_inds'][k] for k in order],
                                               stuff_area_limit=config.test.panoptic_stuff_area_limit)
+        if config.test.get('pan_min_score', 0.0) > 0:
+            pans = dataset.filter_pan_result(pans, panoptic_confs(results, False, order))
     else:
         def ordered(per_class):
             return [[v[k] for k in order] if c else v for c, v in enumerate(per_class)]
@@ -250,7 +289,7 @@ def ssegs_folder(results_dir, label_ids):
 def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_proposals=False, eval_instances=False, write_panoptic=False,
                      panoptic_categories=None, eval_pixels=False, write_ssegs=False, ssegs_label_ids=False, write_instances=False,
                      instances_1bit=False, eval_boundary=False, boundary_dilation_ratio=0.02, boundary_pq_ratio=None, vis_panoptic=None,
-                     vis_panoptic_min_area=1024, vis_panoptic_files=None):
+                     vis_panoptic_min_area=1024, vis_panoptic_files=None, write_pan_confidence=False):
     """The reference's evaluation calls (upsnet_end2end_test.py:300-314), each only when its head is configured. Returns
     {'box_ap': stats, 'mask_ap': stats, 'panoptic': PQ dict, 'sseg': mIoU dict} (the keys of the heads that ran), plus
     'panoptic_combined' (PQ dict of get_combined_pan_result) with pan_combined and 'proposal_ar' (AR@100 ... ARl@1000 of
@@ -265,7 +304,9 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
     after 'panoptic' and 'panoptic_combined_boundary' after 'panoptic_combined': Boundary PQ of the same predictions at that ratio
     (BaseDataset.evaluate_panoptic_boundary). vis_panoptic ('flat', 'overlay' or 'both'): every panoptic result that is scored (or,
     without ground truth, would be) is also drawn into the folder write_panoptic uses, <folder>/vis_flat and / or <folder>/vis
-    (BaseDataset.vis_panoptic, labels from vis_panoptic_min_area pixels); the written paths are appended to vis_panoptic_files."""
+    (BaseDataset.vis_panoptic, labels from vis_panoptic_min_area pixels); the written paths are appended to vis_panoptic_files.
+    With config.test.pan_confidence (or pan_min_score > 0) and results['all_pano_confs'], write_panoptic's pred.json of the unified
+    result carries a "score" per segment; write_pan_confidence also writes the planes to pans_unified/conf/*.png."""
     net = config.network
     metrics = {}
     if write_ssegs:
@@ -279,7 +320,9 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
                 pans = panoptic_predictions(dataset, results, combined)
                 folder = os.path.join(results_dir, 'pans_combined' if combined else 'pans_unified')
                 if write_panoptic:
-                    dataset.write_panoptic(pans, folder, categories_json=panoptic_categories)
+                    dataset.write_panoptic(pans, folder, categories_json=panoptic_categories,
+                                           confs=panoptic_confs(results, combined, list(range(len(dataset)))),
+                                           write_conf=write_pan_confidence and not combined)
                 draw_panoptic(dataset, pans, folder, vis_panoptic, vis_panoptic_min_area, panoptic_categories, vis_panoptic_files)
         return metrics
     os.makedirs(results_dir, exist_ok=True)
@@ -300,7 +343,8 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
             metrics['panoptic_boundary'] = dataset.evaluate_panoptic_boundary(pans, os.path.join(results_dir, 'pans_unified'),
                                                                               dilation_ratio=boundary_pq_ratio)
         if write_panoptic:
-            dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_unified'))
+            dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_unified'), confs=panoptic_confs(results, False, dataset.panoptic_order()),
+                                   write_conf=write_pan_confidence)
         draw_panoptic(dataset, pans, os.path.join(results_dir, 'pans_unified'), vis_panoptic, vis_panoptic_min_area, None, vis_panoptic_files)
     if pan_combined:
         logger.info('combined pano result:')
@@ -311,7 +355,7 @@ def evaluate_results(dataset, results, results_dir, pan_combined=False, eval_pro
             metrics['panoptic_combined_boundary'] = dataset.evaluate_panoptic_boundary(pans, os.path.join(results_dir, 'pans_combined'),
                                                                                        dilation_ratio=boundary_pq_ratio)
         if write_panoptic:
-            dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_combined'))
+            dataset.write_panoptic(pans, os.path.join(results_dir, 'pans_combined'), confs=panoptic_confs(results, True, None))
         draw_panoptic(dataset, pans, os.path.join(results_dir, 'pans_combined'), vis_panoptic, vis_panoptic_min_area, None, vis_panoptic_files)
     if net.has_fcn_head:
         metrics['sseg'] = dataset.evaluate_ssegs(results['all_ssegs'], os.path.join(results_dir, 'ssegs'))
@@ -454,8 +498,14 @@ def main(argv=None):
         raise SystemExit('--vis_panoptic_min_area sets the smallest labelled segment of --vis_panoptic overlay / both, which is missing')
     if args.vis_panoptic_min_area is not None and args.vis_panoptic_min_area < 0:
         raise SystemExit('--vis_panoptic_min_area: %d is negative' % args.vis_panoptic_min_area)
+    if pan_confidence_wanted() and not net.has_panoptic_head:
+        raise SystemExit('--pan_confidence / --pan_min_score read the panoptic head\'s logits: they need network.has_panoptic_head '
+                         '(has_panoptic_head=%s)' % net.has_panoptic_head)
+    if args.write_pan_confidence and not (args.write_panoptic and pan_confidence_wanted()):
+        raise SystemExit('--write_pan_confidence writes the confidence planes beside the files of --write_panoptic: it needs '
+                         '--write_panoptic and --pan_confidence (or --pan_min_score)')
     pv_files = []
-    pv_kw = dict(vis_panoptic=args.vis_panoptic, vis_panoptic_files=pv_files,
+    pv_kw = dict(vis_panoptic=args.vis_panoptic, vis_panoptic_files=pv_files, write_pan_confidence=args.write_pan_confidence,
                  vis_panoptic_min_area=1024 if args.vis_panoptic_min_area is None else args.vis_panoptic_min_area)
     pv_out = {'vis_panoptic_files': pv_files} if args.vis_panoptic else {}
     if args.score_panoptic_folder and not args.score_panoptic:

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from .._lib import check, lib
-from ..config.config import config
+from ..config.config import config, pan_confidence_wanted
 from ..operators.modules.mask_removal import MaskRemoval
 from ..operators.modules.mask_roi import MaskROI, check_count
 from ..operators.modules.pyramid_proposal import PyramidProposal
@@ -290,10 +290,14 @@ class resnet_upsnet(resnet_rcnn):
             H, W = fcn.shape[2] * 4, fcn.shape[3] * 4
             keep, num_keep, real_keep = self.mask_removal.select(pb[:, 1:], ps, pan_logit, pc, (H, W), num_dev=pan_num)
             num_stuff = self.num_seg_classes - (self.num_classes - 1)
-            panoptic, sem = ops.panoptic_fuse_up(fcn, 4, num_stuff, pb, pan_logit, pc, keep, num_keep, real_keep, self._class_map_dev(pb.device))
+            # (with the confidence plane: the sibling kernel, and one more static output of the captured graph)
+            panoptic, sem, *conf = ops.panoptic_fuse_up(fcn, 4, num_stuff, pb, pan_logit, pc, keep, num_keep, real_keep,
+                                                        self._class_map_dev(pb.device), want_conf=pan_confidence_wanted())
             kept_cls, kept_scores, counters = ops.panoptic_tail_pack(keep, num_keep, pc, ps, det_num, pan_num, extra_num)
             tail_out = dict(keep=keep, panoptic=panoptic, sem=sem, counters=counters, mask_prob=torch.sigmoid(mask_det),
                             kept_cls=kept_cls, kept_scores=kept_scores)
+            if conf:
+                tail_out['conf'] = conf[0]
         if tail_out is None:
             nums = torch.cat([det_num, pan_num, extra_num])
         return dict(feats=feats, fcn=fcn, fuse_up=fuse_up, tail=tail_out, det_boxes=det_boxes, det_scores=det_scores, det_cls=det_cls,
@@ -306,6 +310,8 @@ class resnet_upsnet(resnet_rcnn):
         in turn; for each, the first two images run eagerly (weight packing, function attributes, library handles), the third is
         captured."""
         key = (tuple(x.shape), x.dtype, x.is_contiguous(), tuple(float(v) for v in np.asarray(im_info_host).reshape(-1)))
+        if pan_confidence_wanted():   # (a graph captured without the confidence plane has no such output, and the other way round)
+            key += ('conf',)
         slots = self._graphs.get(key)
         if slots is None:
             slots = self._graphs[key] = {'next': 0, 'slots': [{'seen': 0, 'idx': i} for i in range(self.graph_slots)]}
@@ -396,6 +402,8 @@ class resnet_upsnet(resnet_rcnn):
                     'fcn_outputs': t['sem'], 'cls_inds': st['det_cls'][:n_det], 'panoptic_cls_inds': t['kept_cls'][:k],
                     'panoptic_cls_probs': t['kept_scores'][:k], 'panoptic_outputs': t['panoptic'],
                 }
+                if 'conf' in t:
+                    out['panoptic_conf'] = t['conf']
                 self._keep_proposals(out, st['rois'], st['n_rois'])
                 return out if self.graph_outputs_alias else {key: v.clone() for key, v in out.items()}
         else:
@@ -421,21 +429,11 @@ class resnet_upsnet(resnet_rcnn):
         self._tap(det_boxes=det_boxes, det_scores=det_scores, det_cls=det_cls, pan_boxes=pan_boxes, pan_scores=pan_scores,
                   pan_cls=pan_cls, pan_logit=pan_logit)
         keep, num_keep, real_keep = self.mask_removal.select(pan_boxes[:, 1:], pan_scores, pan_logit, pan_cls, (H, W))
-        num_stuff = self.num_seg_classes - (self.num_classes - 1)
-        cmap = self._class_map_dev(pan_boxes.device)
         if fuse_up:
             self._tap(fcn_score=fcn_score)
         else:
             self._tap(fcn_output=fcn_output)
-        if n_pan > 256:  # beyond the fused kernels' instance table: reference-shaped materialising path
-            if fcn_output is None:
-                fcn_output = F.interpolate(fcn_score, None, 4, mode='bilinear', align_corners=False)
-            panoptic, sem = self._materialised_head(fcn_output, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep)
-        elif fuse_up:
-            panoptic, sem = ops.panoptic_fuse_up(fcn_score, 4, num_stuff, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, cmap)
-        else:
-            panoptic, sem = ops.panoptic_fuse(fcn_output, num_stuff, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, cmap,
-                                              self.enable_void)
+        panoptic, sem, conf = self._panoptic_fusion(fcn_score, fcn_output, n_pan, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep)
         k = int(num_keep.item())
         keep = keep[:k]
         self._tap(keep=keep, panoptic=panoptic, sem=sem)
@@ -444,6 +442,8 @@ class resnet_upsnet(resnet_rcnn):
             'cls_inds': det_cls, 'panoptic_cls_inds': pan_cls[keep], 'panoptic_cls_probs': pan_scores[keep],
             'panoptic_outputs': panoptic,
         }
+        if conf is not None:
+            out['panoptic_conf'] = conf
         if graphed:   # (the graph's buffers are overwritten by its next replay)
             self._keep_proposals(out, st['rois'].clone(), st['n_rois'].clone())
         else:
@@ -461,7 +461,28 @@ class resnet_upsnet(resnet_rcnn):
             out.update(rois=rois, n_rois=n_rois, proposals=rois[:n])
         return out
 
-    def _materialised_head(self, fcn_output, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep):
+    def _panoptic_fusion(self, fcn_score, fcn_output, n_pan, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep):
+        """The panoptic fusion of the eager continuation (and of tta._tail) from the low-resolution score (fcn_output None: the x4
+        upsampling is fused) or the full-resolution logits: (panoptic, semantic, confidence or None). The confidence comes out of
+        the fused-upsample kernel's sibling; on the two rare paths without it, from the materialised planes in plain torch."""
+        num_stuff = self.num_seg_classes - (self.num_classes - 1)
+        cmap = self._class_map_dev(pan_boxes.device)
+        want_conf = pan_confidence_wanted()
+        if n_pan > 256:  # beyond the fused kernels' instance table: reference-shaped materialising path
+            if fcn_output is None:
+                fcn_output = F.interpolate(fcn_score, None, 4, mode='bilinear', align_corners=False)
+            return self._materialised_head(fcn_output, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, want_conf)
+        if fcn_output is None:
+            panoptic, sem, *conf = ops.panoptic_fuse_up(fcn_score, 4, num_stuff, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, cmap,
+                                                        want_conf=want_conf)
+            return panoptic, sem, (conf[0] if conf else None)
+        panoptic, sem = ops.panoptic_fuse(fcn_output, num_stuff, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, cmap,
+                                          self.enable_void)
+        conf = self._materialised_head(fcn_output, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, True)[2] if want_conf else None
+        return panoptic, sem, conf
+
+    def _materialised_head(self, fcn_output, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, want_conf=False):
+        """(panoptic, semantic, confidence or None) on materialised planes; the confidence in plain torch (ops.panoptic_conf_planes)"""
         H, W = fcn_output.shape[2:]
         k = int(num_keep.item())
         energy = ops.mask_paste(pan_boxes[:, 1:], pan_logit, keep, num_keep, real_keep, k, (H, W))
@@ -469,7 +490,8 @@ class resnet_upsnet(resnet_rcnn):
         _, seg_inst = self.seg_term(pan_cls[kk], fcn_output, pan_boxes[kk] * 4.0)
         num_stuff = self.num_seg_classes - (self.num_classes - 1)
         pan = ops.panoptic_argmax(fcn_output, num_stuff, seg_inst, energy, self.enable_void)
-        return pan, torch.max(fcn_output, dim=1)[1]
+        conf = ops.panoptic_conf_planes(fcn_output, num_stuff, seg_inst, energy, self.enable_void) if want_conf else None
+        return pan, torch.max(fcn_output, dim=1)[1], conf
 
     # ------------------------------------------------------------------ reference-shaped dataflow
     def _forward_modules(self, data):
@@ -509,6 +531,9 @@ class resnet_upsnet(resnet_rcnn):
         num_stuff = self.num_seg_classes - (self.num_classes - 1)
         results['panoptic_outputs'] = ops.panoptic_argmax(fcn_output['fcn_output'], num_stuff, seg_inst_logits,
                                                           mask_logits, self.enable_void)
+        if pan_confidence_wanted():
+            results['panoptic_conf'] = ops.panoptic_conf_planes(fcn_output['fcn_output'], num_stuff, seg_inst_logits, mask_logits,
+                                                                self.enable_void)
         self._tap(keep=keep_inds, panoptic=results['panoptic_outputs'], sem=results['fcn_outputs'])
         if self.keep_proposals:   # (rois is already the ranked list)
             results.update(rois=rois, n_rois=torch.full((1,), rois.shape[0], dtype=torch.int32, device=rois.device), proposals=rois)

@@ -926,9 +926,10 @@ def fcn_score_combine(parts, bias=None):
     return out
 
 
-def panoptic_fuse_up(fcn_score, scale, num_stuff, mask_rois5, mask_logit, cls_idx, keep, num, real, class_map, want_sem=True):
+def panoptic_fuse_up(fcn_score, scale, num_stuff, mask_rois5, mask_logit, cls_idx, keep, num, real, class_map, want_sem=True, want_conf=False):
     """Fused head INCLUDING FCNHead's x4 bilinear upsampling: takes the low-resolution fcn_score [1,S,Hs,Ws]
-    (logical NCHW; channels_last memory is consumed as is) and returns (panoptic, semantic) [1,Hs*scale,Ws*scale] int64."""
+    (logical NCHW; channels_last memory is consumed as is) and returns (panoptic, semantic) [1,Hs*scale,Ws*scale] int64.
+    want_conf: the sibling kernel with the confidence plane (panoptic_fuse_up_conf); returns (panoptic, semantic, conf)."""
     require_cuda(fcn_score, mask_rois5, mask_logit, cls_idx)
     sc = fcn_score.float()
     _, S, Hs, Ws = sc.shape
@@ -943,10 +944,35 @@ def panoptic_fuse_up(fcn_score, scale, num_stuff, mask_rois5, mask_logit, cls_id
     H, W = Hs * scale, Ws * scale
     pan = torch.empty((1, H, W), dtype=torch.int64, device=sc.device)
     sem = torch.empty((1, H, W), dtype=torch.int64, device=sc.device) if want_sem else None
-    check(lib().upsnet_panoptic_fuse_up(stream(), ptr(sc), int(is_nhwc), S, Hs, Ws, int(scale), int(num_stuff), ptr(mask_rois5),
-                                        ptr(mask_logit), ptr(cls_idx.to(torch.int64).contiguous()), ptr(keep), ptr(num), ptr(real),
-                                        int(min(m, 256)), ms, ptr(class_map), ptr(pan), ptr(sem)), "panoptic_fuse_up")
-    return pan, sem
+    args = (stream(), ptr(sc), int(is_nhwc), S, Hs, Ws, int(scale), int(num_stuff), ptr(mask_rois5), ptr(mask_logit),
+            ptr(cls_idx.to(torch.int64).contiguous()), ptr(keep), ptr(num), ptr(real), int(min(m, 256)), ms, ptr(class_map), ptr(pan), ptr(sem))
+    if not want_conf:
+        check(lib().upsnet_panoptic_fuse_up(*args), "panoptic_fuse_up")
+        return pan, sem
+    conf = torch.empty((1, H, W), dtype=torch.uint8, device=sc.device)
+    check(lib().upsnet_panoptic_fuse_up_conf(*args, ptr(conf)), "panoptic_fuse_up_conf")
+    return pan, sem, conf
+
+
+def panoptic_fuse_up_conf(fcn_score, scale, num_stuff, mask_rois5, mask_logit, cls_idx, keep, num, real, class_map, want_sem=True):
+    """panoptic_fuse_up with the confidence plane (include/upsnet_hip.h: upsnet_panoptic_fuse_up_conf): returns
+    (panoptic, semantic, conf); conf uint8 [1,Hs*scale,Ws*scale] = (uint8)(255 * P[winner] + 0.5), P the softmax over the panoptic
+    logits of the pixel. The two label maps are bit-equal to panoptic_fuse_up's; all three come out of one launch."""
+    return panoptic_fuse_up(fcn_score, scale, num_stuff, mask_rois5, mask_logit, cls_idx, keep, num, real, class_map, want_sem, True)
+
+
+def panoptic_conf_planes(fcn_output, num_stuff, seg_inst, mask_energy, enable_void=True):
+    """The confidence plane from materialised planes, in plain torch: for the paths the fused-upsample kernel does not serve (more than
+    256 panoptic instances, fuse_up off, the module-level forward). fcn_output [1,S,H,W], seg_inst / mask_energy [1,k,H,W] fp32 ->
+    uint8 [1,H,W] by the rule of upsnet_panoptic_fuse_up_conf: the softmax over stuff | instance | void logits (no void channel without
+    enable_void) at its maximum, which is the label panoptic_argmax emits. torch's exp and summation order are not the kernel's: the two
+    agree within one step of the byte."""
+    f = fcn_output.float()
+    z = [f[:, :num_stuff], seg_inst + mask_energy]
+    if enable_void:
+        z.append(f[:, num_stuff:].max(1, keepdim=True)[0] - seg_inst.max(1, keepdim=True)[0])
+    conf = torch.softmax(torch.cat(z, 1), 1).max(1)[0]
+    return (conf * 255.0 + 0.5).to(torch.uint8)
 
 
 # ----------------------------------------------------------------------------- stem / deconvolution / input blob
@@ -1174,6 +1200,33 @@ def restore_label_maps(sseg, pano, y_ofs, x_ofs):
     check(lib().upsnet_restore_label_maps(stream(), ptr(s), ptr(p), int(s.stride(0)), H, W, ptr(ys), H0, ptr(xs), W0, ptr(out_s),
                                           ptr(out_p)), "restore_label_maps")
     return out_s, out_p
+
+
+def restore_plane_u8(plane, y_ofs, x_ofs, *, out=None):
+    """restore_label_maps' gather for one uint8 plane (include/upsnet_hip.h: upsnet_restore_plane_u8): plane uint8 [H,W] or [1,H,W]
+    device tensor (rows may be strided, columns contiguous), the same index tables. Returns uint8 [len(y_ofs), len(x_ofs)] =
+    plane[y_ofs[y], x_ofs[x]]: the panoptic confidence at the original image size, by the rule of the label maps. out= is taken
+    instead of being allocated."""
+    require_cuda(plane)
+    s = plane.reshape(plane.shape[-2], plane.shape[-1])
+    if s.dtype != torch.uint8 or s.stride(1) != 1:
+        raise ValueError("restore_plane_u8: a uint8 plane with contiguous rows required, got %s stride %s" % (s.dtype, s.stride()))
+    H, W = s.shape
+    ys = torch.as_tensor(y_ofs, dtype=torch.int32).reshape(-1)
+    xs = torch.as_tensor(x_ofs, dtype=torch.int32).reshape(-1)
+    for name, t, n in (("y_ofs", ys, H), ("x_ofs", xs, W)):
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise ValueError("restore_plane_u8: %s outside 0..%d" % (name, n - 1))
+    ys, xs = ys.to(s.device).contiguous(), xs.to(s.device).contiguous()
+    H0, W0 = ys.numel(), xs.numel()
+    if out is None:
+        out = torch.zeros((H0, W0), dtype=torch.uint8, device=s.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (H0, W0) or not out.is_contiguous() or out.device != s.device:
+        raise ValueError("restore_plane_u8: out must be a contiguous uint8 [%d,%d] tensor on the plane's device" % (H0, W0))
+    if H0 == 0 or W0 == 0:
+        return out
+    check(lib().upsnet_restore_plane_u8(stream(), ptr(s), int(s.stride(0)), H, W, ptr(ys), H0, ptr(xs), W0, ptr(out)), "restore_plane_u8")
+    return out
 
 
 def unified_pan_result(pan, seg, cls_inds, id_last_stuff, num_seg_classes, stuff_area_limit=4 * 64 * 64):
@@ -2080,6 +2133,65 @@ def _pan_clean(name, workspace_bytes, entry, nstats, pan_2ch, min_area, connecti
         check(entry(stream(), ptr(pan_2ch), H, W, int(connectivity), int(min_area), int(bool(keep_largest)), ptr(workspace), ptr(out),
                     ptr(labels), ptr(stats)), name)
     return out, stats, labels
+
+
+def _pan_conf_check(name, pan_2ch, conf=None):
+    if pan_2ch.dtype != torch.uint8 or pan_2ch.dim() != 3 or pan_2ch.shape[2] != 3 or not pan_2ch.is_contiguous():
+        raise ValueError("%s: pan_2ch must be contiguous uint8 [H,W,3], got %s %s" % (name, tuple(pan_2ch.shape), pan_2ch.dtype))
+    H, W = int(pan_2ch.shape[0]), int(pan_2ch.shape[1])
+    if H * W == 0 or H * W > (1 << 24):
+        raise ValueError("%s: a map of %d x %d pixels: H * W must lie in 1..2^24" % (name, H, W))
+    if conf is not None and (conf.dtype != torch.uint8 or tuple(conf.shape) != (H, W) or not conf.is_contiguous()):
+        raise ValueError("%s: conf must be contiguous uint8 [%d,%d], got %s %s" % (name, H, W, tuple(conf.shape), conf.dtype))
+    return H, W
+
+
+def pan_segment_scores(pan_2ch, conf, *, workspace=None, table=None):
+    """Area and confidence sum of every segment of a 2-channel map (include/upsnet_hip.h: upsnet_pan_segment_scores).
+    pan_2ch contiguous uint8 [H,W,3], conf contiguous uint8 [H,W] (the panoptic confidence at the map's size). Returns the device
+    table, an int32 tensor [4 + 3 * 65280] whose words are unsigned (sum_q can pass 2^31: read it through numpy's .view(np.uint32)):
+    [0] = number of rows n, then n rows (key = category << 8 | instance, area, sum_q) from word 4 on, in ascending key; VOID (category
+    255) has no row. The score of a row is sum_q / (255 * area)
+    (dataset/pan_confidence.py forms it in double on the host). Three launches, nothing waits for the host. workspace= (uint8, at
+    least upsnet_pan_segment_scores_workspace_bytes() bytes, any contents) and table= (any contents) are taken instead of being
+    allocated."""
+    H, W = _pan_conf_check("pan_segment_scores", pan_2ch, conf)
+    require_cuda(pan_2ch, conf, workspace)
+    need = int(lib().upsnet_pan_segment_scores_workspace_bytes())
+    if workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need
+                                  or workspace.data_ptr() % 4):
+        raise ValueError("pan_segment_scores: workspace must be a contiguous, 4-byte aligned uint8 tensor of at least %d bytes" % need)
+    nints = int(lib().upsnet_pan_segment_scores_table_ints())
+    if table is not None and (table.dtype != torch.int32 or not table.is_contiguous() or table.numel() < nints):
+        raise ValueError("pan_segment_scores: table must be a contiguous int32 tensor of at least %d words" % nints)
+    require_cuda(table)
+    dev = pan_2ch.device
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = torch.zeros((need,), dtype=torch.uint8, device=dev)
+        if table is None:
+            table = torch.zeros((nints,), dtype=torch.int32, device=dev)
+        check(lib().upsnet_pan_segment_scores(stream(), ptr(pan_2ch), ptr(conf), H, W, ptr(workspace), ptr(table)), "pan_segment_scores")
+    return table
+
+
+def pan_score_filter(pan_2ch, table, min_score, *, out=None):
+    """Removes the doubtful segments of a 2-channel map (include/upsnet_hip.h: upsnet_pan_score_filter): every pixel of a non-VOID key
+    whose row of `table` (pan_segment_scores of the same map) has sum_q < min_score * 255 * area, compared in double, becomes
+    (255, 0, 0). 0 <= min_score <= 1; 0 removes nothing. Returns the filtered map; out= may be pan_2ch itself. One launch."""
+    H, W = _pan_conf_check("pan_score_filter", pan_2ch)
+    if not (0.0 <= float(min_score) <= 1.0):
+        raise ValueError("pan_score_filter: min_score must lie in 0..1, got %r" % (min_score,))
+    if table.dtype != torch.int32 or not table.is_contiguous() or table.numel() < int(lib().upsnet_pan_segment_scores_table_ints()):
+        raise ValueError("pan_score_filter: table must be the int32 table of pan_segment_scores")
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous()):
+        raise ValueError("pan_score_filter: out must be contiguous uint8 [%d,%d,3], got %s %s" % (H, W, tuple(out.shape), out.dtype))
+    require_cuda(pan_2ch, table, out)
+    with torch.cuda.device(pan_2ch.device):
+        if out is None:
+            out = pan_2ch.clone()
+        check(lib().upsnet_pan_score_filter(stream(), ptr(pan_2ch), H, W, ptr(table), float(min_score), ptr(out)), "pan_score_filter")
+    return out
 
 
 def video_eval_workspace(max_gt, height, width, max_window, device):

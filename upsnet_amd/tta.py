@@ -347,20 +347,13 @@ def _tail(model, score, fuse_up, mask_score, n_det, n_pan, det_boxes, det_scores
     mask_prob = torch.sigmoid(mask_score[:n_det])
     pan_logit = mask_score.index_select(0, pan_row[:n_pan].long()).gather(1, pan_cls.view(-1, 1, 1, 1).expand(-1, -1, ms, ms))
     keep, num_keep, real_keep = model.mask_removal.select(pan_boxes[:, 1:], pan_scores, pan_logit, pan_cls, (H, W))
-    num_stuff = model.num_seg_classes - (model.num_classes - 1)
-    cmap = model._class_map_dev(pan_boxes.device)
-    if n_pan > 256:  # beyond the fused kernels' instance table: reference-shaped materialising path
-        if fcn_output is None:
-            fcn_output = F.interpolate(fcn_score, None, 4, mode='bilinear', align_corners=False)
-        panoptic, sem = model._materialised_head(fcn_output, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep)
-    elif fuse_up:
-        panoptic, sem = ops.panoptic_fuse_up(fcn_score, 4, num_stuff, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, cmap)
-    else:
-        panoptic, sem = ops.panoptic_fuse(fcn_output, num_stuff, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep, cmap,
-                                          model.enable_void)
+    panoptic, sem, conf = model._panoptic_fusion(fcn_score, fcn_output, n_pan, pan_boxes, pan_logit, pan_cls, keep, num_keep, real_keep)
     keep = keep[:int(num_keep.item())]
-    return {
+    out = {
         'cls_probs': det_scores, 'pred_boxes': det_boxes, 'mask_probs': mask_prob, 'fcn_outputs': sem,
         'cls_inds': det_cls, 'panoptic_cls_inds': pan_cls[keep], 'panoptic_cls_probs': pan_scores[keep],
         'panoptic_outputs': panoptic,
     }
+    if conf is not None:
+        out['panoptic_conf'] = conf
+    return out
