@@ -285,8 +285,9 @@ int upsnet_conv2d_winograd_nhwc_f32_tail(void *stream, const float *x, float *ou
  *                      relative per product, fp32 accumulation): inside the 1e-4 fp32-logit tolerance
  * wpack_hi / wpack_lo: bf16 [KH*KW*Cin/32][ldw][32] from upsnet_conv_pack_weight_bf16, ldw = Cout rounded up to 64.
  * Same calling convention as upsnet_conv2d_nhwc_f32 (without residual_up). relu: bit 0 = ReLU; bit 1 = `residual` is at half
- * resolution and is added through a nearest x2 upsampling (1x1 kernels only: the FPN top-down add). */
-int upsnet_conv2d_nhwc_bf16(void *stream, int nseg, const float *const x[], const float *const residual[], float *const out[],
+ * resolution and is added through a nearest x2 upsampling (1x1 kernels only: the FPN top-down add); bits 2 / 3 / 4 = the input / the
+ * output / the residual tensors are bf16 (NHWC, same shapes) instead of fp32 (bf16 mode only, wpack_lo == NULL): hence void. */
+int upsnet_conv2d_nhwc_bf16(void *stream, int nseg, const void *const x[], const void *const residual[], void *const out[],
                             const int batch[], const int height[], const int width[], int Cin, const void *wpack_hi,
                             const void *wpack_lo, int ldw, const float *bias, int Cout, int KH, int KW, int stride, int pad,
                             int relu);

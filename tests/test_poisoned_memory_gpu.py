@@ -562,36 +562,43 @@ def _model_setup():
     return _MODEL['setup']
 
 
-def run_case(case, pattern):
-    """The case's test body under `pattern`: returns [(entry point, returned tensor)] and [entry point] in call order, and the number
-    of allocations."""
+def case_call(case, stack, mp):
+    """(the case's test function, stand-ins for the fixtures it asks for): `stack` is an ExitStack that the stand-ins live on, `mp`
+    a MonkeyPatch on it. Shared with tests/test_abi_contract_gpu.py, which runs the same bodies under another instrument."""
     import pathlib
     from upsnet_amd import ops
     tmod = importlib.import_module(case.module)
     fn = getattr(tmod, case.test)
+    args = {}
+    for p in inspect.signature(fn).parameters:
+        if p in case.kwargs:
+            continue
+        if p == 'U':
+            args[p] = ops
+        elif p == 'monkeypatch':
+            args[p] = mp
+        elif p == 'tmp_path':
+            args[p] = pathlib.Path(stack.enter_context(tempfile.TemporaryDirectory()))
+        elif p == 'saved_config':
+            args[p] = stack.enter_context(_saved_config())
+        elif p == 'cityscapes_config':
+            args[p] = stack.enter_context(_cityscapes_config(tmod))
+        elif p == 'setup':        # (eager: the graph path on poisoned memory is test_fused_forward_on_poisoned_memory_...)
+            args[p] = _model_setup()
+            args[p][0]._graphs.clear()
+            mp.setattr(args[p][0], 'use_graph', False)
+        else:
+            raise RuntimeError("%s: no stand-in for the fixture %r" % (case.id, p))
+    return fn, args
+
+
+def run_case(case, pattern):
+    """The case's test body under `pattern`: returns [(entry point, returned tensor)] and [entry point] in call order, and the number
+    of allocations."""
     log, calls = [], []
     with contextlib.ExitStack() as stack:
         mp = stack.enter_context(pytest.MonkeyPatch.context())
-        args = {}
-        for p in inspect.signature(fn).parameters:
-            if p in case.kwargs:
-                continue
-            if p == 'U':
-                args[p] = ops
-            elif p == 'monkeypatch':
-                args[p] = mp
-            elif p == 'tmp_path':
-                args[p] = pathlib.Path(stack.enter_context(tempfile.TemporaryDirectory()))
-            elif p == 'saved_config':
-                args[p] = stack.enter_context(_saved_config())
-            elif p == 'cityscapes_config':
-                args[p] = stack.enter_context(_cityscapes_config(tmod))
-            elif p == 'setup':        # (eager: the graph path on poisoned memory is test_fused_forward_on_poisoned_memory_...)
-                args[p] = _model_setup()
-                args[p][0]._graphs.clear()
-                mp.setattr(args[p][0], 'use_graph', False)
-            else:
-                raise RuntimeError("%s: no stand-in for the fixture %r" % (case.id, p))
+        fn, args = case_call(case, stack, mp)
         for e in case.entries:
             owner, name = _owner(e)
             mp.setattr(owner, name, _recorder(e, getattr(owner, name), pattern, log, calls))

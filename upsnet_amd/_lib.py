@@ -259,10 +259,40 @@ def require_cuda(*tensors):
 
 
 def f32c(t):
-    """fp32 + contiguous (plumbing)."""
+    """fp32 + contiguous (plumbing); None passes through."""
+    if t is None:
+        return None
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def i32c(t):
+    """int32 + contiguous: a read-only index / count input (a tensor the kernel writes is never converted: a copy would swallow the writes)."""
+    if t is None:
+        return None
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    return t.contiguous()
+
+
+def i64c(t):
+    """int64 + contiguous: a read-only index input (see i32c)."""
+    if t is None:
+        return None
+    if t.dtype != torch.int64:
+        t = t.to(torch.int64)
+    return t.contiguous()
+
+
+def written(t, dtype, what):
+    """A tensor the kernel writes (an output, a workspace, a device counter) is taken as it is or refused: `dtype` (None: any, a
+    workspace of bytes) and contiguous."""
+    if t is not None and ((dtype is not None and t.dtype != dtype) or not t.is_contiguous()):
+        raise ValueError("%s must be a contiguous %s tensor (got %s, strides %s): the kernel writes it, a converted copy would swallow the writes"
+                         % (what, 'any-type' if dtype is None else str(dtype).replace('torch.', ''), str(t.dtype).replace('torch.', ''),
+                            tuple(t.stride())))
+    return t
 
 
 def nhwc(t):
@@ -280,3 +310,8 @@ def float_array(vals):
 
 def ptr_array(tensors):
     return (c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def addr(t):
+    """Device address of a tensor as a plain int, for a table of addresses that a kernel reads (the caller keeps `t` alive)."""
+    return t.data_ptr()

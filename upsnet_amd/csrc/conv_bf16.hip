@@ -566,7 +566,7 @@ int conv1x1_wreg_bf16_launch(hipStream_t st, ConvParams &p, const void *wpack_hi
 bool conv3x3_wreg_bf16_supported(const ConvParams &p);
 int conv3x3_wreg_bf16_launch(hipStream_t st, ConvParams &p, const void *wpack_hi);
 
-extern "C" int upsnet_conv2d_nhwc_bf16(void *stream, int nseg, const float *const x[], const float *const residual[], float *const out[],
+extern "C" int upsnet_conv2d_nhwc_bf16(void *stream, int nseg, const void *const x_[], const void *const residual_[], void *const out_[],
                                        const int batch[], const int height[], const int width[], int Cin, const void *wpack_hi,
                                        const void *wpack_lo, int ldw, const float *bias, int Cout, int KH, int KW, int stride, int pad,
                                        int relu)
@@ -576,6 +576,9 @@ extern "C" int upsnet_conv2d_nhwc_bf16(void *stream, int nseg, const float *cons
     // output / the residual tensors are bf16 (NHWC, same shapes) instead of fp32 -- bf16 mode only (wpack_lo == NULL)
     const int res_up = (relu >> 1) & 1, io = (relu >> 2) & 7;
     relu &= 1;
+    const float *const *x = reinterpret_cast<const float *const *>(x_);          // (fp32 or bf16 by the io bits: the header says void)
+    const float *const *residual = reinterpret_cast<const float *const *>(residual_);
+    float *const *out = reinterpret_cast<float *const *>(out_);
     int rc = conv_fill(p, "conv2d_nhwc_bf16", nseg, x, residual, nullptr, nullptr, out, batch, height, width, Cin, Cout,
                        reinterpret_cast<const float *>(wpack_hi), ldw, bias, KH, KW, stride, pad, 1, relu);
     if (rc) return rc;

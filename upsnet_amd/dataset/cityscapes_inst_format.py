@@ -37,7 +37,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import check, i32c, lib, ptr, stream, written
 from .cityscapes_eval import CLASS_LABEL_IDS, CLASS_NAMES, MAX_PREDS, NUM_CLASSES, _transitions
 from .pan_format import MAX_ENCODE_THREADS
 
@@ -86,7 +86,8 @@ def _expand_into(d_trans, d_off, n, H, W, one_bit, out, max_bytes):
     """The launches of n checked masks: chunks of whole masks whose output stays within max_bytes (one mask at least)."""
     per = plane_bytes(H, W, one_bit)
     step = max(1, int(max_bytes) // per)
-    flat = out.view(-1)
+    d_trans, d_off = i32c(d_trans), i32c(d_off)
+    flat = written(out, torch.uint8, "expand_masks: out").view(-1)
     for m0 in range(0, n, step):
         nm = min(step, n - m0)
         check(lib().upsnet_cs_inst_expand(stream(), ptr(d_trans), ptr(d_off[m0:]), nm, H, W, 1 if one_bit else 8, ptr(flat[m0 * per:])),

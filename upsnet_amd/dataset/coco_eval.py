@@ -25,7 +25,7 @@ import logging
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import check, lib, ptr, ptr_array, stream
 from .boundary import check_dilation_ratio, checked_dilation
 from .polygon import PolygonView
 
@@ -410,13 +410,13 @@ class DetectionEvaluator(object):
             u8 = [torch.as_tensor(m).to(self.device).contiguous() for m in g['u8']]
             n_u8 = len(u8)
             if n_u8:
-                u8_ptrs = (ctypes.c_void_p * n_u8)(*[m.data_ptr() for m in u8])
+                u8_ptrs = ptr_array(u8)
                 u8_dst = (ctypes.c_int * n_u8)(*g['u8_dst'])
             keep += [det_trans, det_off, gt_trans, gt_off, gt_dst] + u8
         rec = st['rec']
         o = self._n_rec
-        u8_p = ctypes.cast(u8_ptrs, ctypes.c_void_p) if n_u8 else None
-        u8_d = ctypes.cast(u8_dst, ctypes.c_void_p) if n_u8 else None
+        u8_p = u8_ptrs if n_u8 else None          # (host arrays: of the planes' device addresses, of their rows)
+        u8_d = u8_dst if n_u8 else None
         recs = (ptr(rec['score'][o:]), ptr(rec['img'][o:]), ptr(rec['rk'][o:]), ptr(rec['match'][o:]), ptr(rec['ign'][o:]), ptr(st['npig']))
         if self.boundary:
             check(lib().upsnet_det_eval_boundary_image(

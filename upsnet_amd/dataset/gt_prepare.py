@@ -4,7 +4,7 @@ re-exports these functions."""
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, require_cuda, stream
+from .._lib import check, lib, ptr, require_cuda, stream, written
 
 GT_PREPARE_SEGMENTS = 4096      # default segment capacity of gt_prepare (a Cityscapes image holds a few hundred)
 GT_ROW = 9                      # ints per segment row: v, label, train id, iscrowd, area, x_min, y_min, x_max, y_max
@@ -53,7 +53,7 @@ def gt_prepare_launch(ids, tables, label_ids=None, seg_capacity=GT_PREPARE_SEGME
     dev = ids.device
     if workspace is None:
         workspace = gt_prepare_workspace(dev, seg_capacity)
-    elif workspace.numel() * workspace.element_size() < int(lib().upsnet_gt_prepare_workspace_bytes(seg_capacity)):
+    elif written(workspace, None, "gt_prepare: workspace").numel() * workspace.element_size() < int(lib().upsnet_gt_prepare_workspace_bytes(seg_capacity)):
         raise ValueError("gt_prepare: workspace too small for %d segments" % seg_capacity)
     train_map = torch.empty((H, W), dtype=torch.uint8, device=dev)
     rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)

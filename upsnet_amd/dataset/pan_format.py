@@ -38,7 +38,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, require_cuda, stream
+from .._lib import check, lib, ptr, require_cuda, stream, written
 from .pq import MAX_CATEGORY, _check_image
 
 logger = logging.getLogger(__name__)
@@ -368,6 +368,7 @@ def relabel(rgb, table, image_index, status):
     require_cuda(rgb, status)
     if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
         raise ValueError("relabel: rgb must be uint8 [H,W,3], got %s %s" % (tuple(rgb.shape), rgb.dtype))
+    written(status, torch.int64, "relabel: status")
     table = np.ascontiguousarray(table, np.int32).reshape(-1, 3)
     n = int(table.shape[0])
     rgb = rgb.contiguous()

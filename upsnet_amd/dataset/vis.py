@@ -154,7 +154,8 @@ def render_detections(image_rgb, boxes, labels, colours, trans, trans_off):
                 spans.append((o, max(p.size, 4)))
                 o += p.size
             d = host.to(dev, non_blocking=True)
-            views = [d[a:a + b] for a, b in spans]
+            kinds = (torch.float32, torch.int32, torch.int32, torch.int32, torch.uint8, torch.uint8)       # (the 4-byte items start at multiples of 4)
+            views = [d[a:a + b].view(k) for (a, b), k in zip(spans, kinds)]
         d_boxes, d_len, d_off, d_trans, d_labels, d_colours = views
         check(lib().upsnet_vis_render(stream(), ptr(image_rgb), H, W, n, ptr(d_boxes), ptr(d_colours), ptr(d_labels), ptr(d_len),
                                       ptr(d_trans) if trans.size else None, ptr(d_off), int(trans.size), ptr(ws), ptr(out)), "vis_render")

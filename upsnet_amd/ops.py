@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, f32c, float_array, int_array, lib, nhwc, ptr, ptr_array, require_cuda, stream
+from ._lib import addr, check, f32c, float_array, i32c, i64c, int_array, lib, nhwc, ptr, ptr_array, require_cuda, stream, written
 
 
 # bench.py sets PROFILE['enabled'] to bracket the dominant kernel with events on the launch stream
@@ -106,7 +106,7 @@ def fpn_roi_order(rois, image_hw, num_rois_dev=None):
     """int32 [N]: the workgroup -> ROI table of fpn_roi_align(order=...) that gives every XCD one contiguous range of the ROIs sorted by
     (pyramid level, image stripe, column cell). image_hw: extent of the image the ROIs live in. N <= 2048."""
     require_cuda(rois)
-    rois = f32c(rois)
+    rois, num_rois_dev = f32c(rois), i32c(num_rois_dev)
     order = torch.empty((max(rois.shape[0], 1),), dtype=torch.int32, device=rois.device)
     check(lib().upsnet_fpn_roi_order(stream(), ptr(rois), int(rois.shape[0]), ptr(num_rois_dev), int(image_hw[0]), int(image_hw[1]), ptr(order)),
           "fpn_roi_order")
@@ -123,7 +123,7 @@ def fpn_roi_align(feats, rois, pooled_h, pooled_w, spatial_scale, sampling_ratio
     require_cuda(rois, *feats)
     assert len(feats) == 4 and len(spatial_scale) == 4
     feats = [nhwc(f.float()) for f in feats]
-    rois = f32c(rois)
+    rois, num_rois_dev = f32c(rois), i32c(num_rois_dev)
     C = feats[0].shape[1]
     for f in feats:
         if f.shape[0] != 1 or f.shape[1] != C:
@@ -166,7 +166,8 @@ def deform_im2col(data_im, data_offset, im_shape, col_shape, kernel_shape, pad, 
                   deformable_group, data_col):
     """Drop-in for deform_conv_cuda.deform_im2col (deform_conv_cuda.cpp:49-68); fills data_col in place."""
     require_cuda(data_im, data_offset, data_col)
-    assert data_im.is_contiguous() and data_offset.is_contiguous() and data_col.is_contiguous()
+    data_im, data_offset = f32c(data_im), f32c(data_offset)
+    written(data_col, torch.float32, "deform_im2col: data_col")
     check(lib().upsnet_deform_im2col(stream(), ptr(data_im), ptr(data_offset), int(im_shape[1]), int(im_shape[2]),
                                      int(im_shape[3]), int(kernel_shape[0]), int(kernel_shape[1]), int(pad[0]), int(pad[1]),
                                      int(stride[0]), int(stride[1]), int(dilation[0]), int(dilation[1]), int(parallel_imgs),
@@ -178,7 +179,8 @@ def mod_deform_im2col(data_im, data_offset, data_mask, im_shape, col_shape, kern
                       deformable_group, data_col):
     """Drop-in for mod_deform_conv_cuda.mod_deform_im2col (mod_deform_conv_cuda.cpp:51-74), batch 1."""
     require_cuda(data_im, data_offset, data_mask, data_col)
-    assert data_im.is_contiguous() and data_offset.is_contiguous() and data_mask.is_contiguous()
+    data_im, data_offset, data_mask = f32c(data_im), f32c(data_offset), f32c(data_mask)
+    written(data_col, torch.float32, "mod_deform_im2col: data_col")
     check(lib().upsnet_mod_deform_im2col(stream(), ptr(data_im), ptr(data_offset), ptr(data_mask), 1, int(im_shape[1]),
                                          int(im_shape[2]), int(im_shape[3]), int(col_shape[1]), int(col_shape[2]),
                                          int(kernel_shape[0]), int(kernel_shape[1]), int(pad[0]), int(pad[1]),
@@ -196,7 +198,8 @@ def deform_col2im(data_col, data_offset, im_shape, col_shape, kernel_shape, pad,
                   deformable_group, grad_im):
     """Drop-in for deform_conv_cuda.deform_col2im (deform_conv_cuda.cpp:70-86); accumulates into grad_im."""
     require_cuda(data_col, data_offset, grad_im)
-    assert data_col.is_contiguous() and data_offset.is_contiguous() and grad_im.is_contiguous()
+    data_col, data_offset = f32c(data_col), f32c(data_offset)
+    written(grad_im, torch.float32, "deform_col2im: grad_im")
     check(lib().upsnet_deform_col2im(stream(), ptr(data_col), ptr(data_offset), *_shape_args(im_shape, kernel_shape, pad, stride,
                                                                                             dilation),
                                      int(parallel_imgs), int(deformable_group), ptr(grad_im)), "deform_col2im")
@@ -207,7 +210,8 @@ def deform_col2im_coord(data_col, data_im, data_offset, im_shape, col_shape, ker
                         parallel_imgs, deformable_group, grad_offset):
     """Drop-in for deform_conv_cuda.deform_col2im_coord (deform_conv_cuda.cpp:88-105); overwrites grad_offset."""
     require_cuda(data_col, data_im, data_offset, grad_offset)
-    assert data_col.is_contiguous() and data_im.is_contiguous() and data_offset.is_contiguous() and grad_offset.is_contiguous()
+    data_col, data_im, data_offset = f32c(data_col), f32c(data_im), f32c(data_offset)
+    written(grad_offset, torch.float32, "deform_col2im_coord: grad_offset")
     check(lib().upsnet_deform_col2im_coord(stream(), ptr(data_col), ptr(data_im), ptr(data_offset),
                                            *_shape_args(im_shape, kernel_shape, pad, stride, dilation), int(parallel_imgs),
                                            int(deformable_group), ptr(grad_offset)), "deform_col2im_coord")
@@ -218,7 +222,8 @@ def mod_deform_col2im(data_col, data_offset, data_mask, im_shape, col_shape, ker
                       deformable_group, grad_im):
     """Drop-in for mod_deform_conv_cuda.mod_deform_col2im (mod_deform_conv_cuda.cpp:76-92), batch 1."""
     require_cuda(data_col, data_offset, data_mask, grad_im)
-    assert data_col.is_contiguous() and data_offset.is_contiguous() and data_mask.is_contiguous() and grad_im.is_contiguous()
+    data_col, data_offset, data_mask = f32c(data_col), f32c(data_offset), f32c(data_mask)
+    written(grad_im, torch.float32, "mod_deform_col2im: grad_im")
     a = _shape_args(im_shape, kernel_shape, pad, stride, dilation)
     check(lib().upsnet_mod_deform_col2im(stream(), ptr(data_col), ptr(data_offset), ptr(data_mask), 1, a[0], a[1], a[2],
                                          int(col_shape[1]), int(col_shape[2]), *a[3:], int(deformable_group), ptr(grad_im)),
@@ -230,8 +235,9 @@ def mod_deform_col2im_coord(data_col, data_im, data_offset, data_mask, im_shape,
                             dilation, deformable_group, grad_offset, grad_mask):
     """Drop-in for mod_deform_conv_cuda.mod_deform_col2im_coord (mod_deform_conv_cuda.cpp:94-114), batch 1."""
     require_cuda(data_col, data_im, data_offset, data_mask, grad_offset, grad_mask)
-    assert data_col.is_contiguous() and data_im.is_contiguous() and data_offset.is_contiguous() and data_mask.is_contiguous()
-    assert grad_offset.is_contiguous() and grad_mask.is_contiguous()
+    data_col, data_im, data_offset, data_mask = f32c(data_col), f32c(data_im), f32c(data_offset), f32c(data_mask)
+    written(grad_offset, torch.float32, "mod_deform_col2im_coord: grad_offset")
+    written(grad_mask, torch.float32, "mod_deform_col2im_coord: grad_mask")
     a = _shape_args(im_shape, kernel_shape, pad, stride, dilation)
     check(lib().upsnet_mod_deform_col2im_coord(stream(), ptr(data_col), ptr(data_im), ptr(data_offset), ptr(data_mask), 1, a[0],
                                                a[1], a[2], int(col_shape[1]), int(col_shape[2]), *a[3:], int(deformable_group),
@@ -244,8 +250,8 @@ def roi_align_backward(pooled_h, pooled_w, sampling_ratio, spatial_scale, top_gr
     require_cuda(top_grad, rois, bottom_grad)
     if rois.dim() != 2 or rois.shape[1] != 5:
         return 0
-    assert top_grad.is_contiguous() and rois.is_contiguous() and bottom_grad.is_contiguous()
-    assert top_grad.dtype == torch.float32 and rois.dtype == torch.float32 and bottom_grad.dtype == torch.float32
+    top_grad, rois = f32c(top_grad), f32c(rois)
+    written(bottom_grad, torch.float32, "roi_align_backward: bottom_grad")
     B, C, H, W = bottom_grad.shape
     check(lib().upsnet_roi_align_backward(stream(), ptr(top_grad), float(spatial_scale), B, rois.shape[0], H, W, C, int(pooled_h),
                                           int(pooled_w), int(sampling_ratio), ptr(rois), ptr(bottom_grad)), "roi_align_backward")
@@ -331,6 +337,10 @@ def deform_conv_fused(xs, offsets, wpack, bias, cin, cout, ksize, stride, pad, d
     tensors with batch 1; wpack = (packed weight, ldw) from pack_dcn_weight; returns channels_last outputs."""
     wp, ldw = wpack     # ('frag', packed) or (packed, ldw)
     require_cuda(ldw if isinstance(wp, str) else wp, *xs)
+    if isinstance(wp, str):
+        ldw = ldw.contiguous() if wp == 'frag_bf16' else f32c(ldw)
+    else:
+        wp = f32c(wp)
     n = len(xs)
     assert 1 <= n <= 4 and len(offsets) == n
     xs = [nhwc(x.float()) for x in xs]
@@ -507,8 +517,9 @@ def pyramid_proposals(cls_probs, bbox_preds, im_info, anchors, strides, pre_nms_
     num = torch.empty((1,), dtype=torch.int32, device=dev)
     anc = float_array(np.asarray(anchors, np.float32).reshape(-1).tolist())
     long_array = lambda v: (_lib.c_long * len(v))(*[int(x) for x in v])
+    im_info = f32c(im_info)
     args = (stream(), L, ptr_array(cls_probs), ptr_array(bbox_preds), long_array(cls_cs), long_array(cls_ps), long_array(box_cs), long_array(box_ps),
-            hs, ws_, int_array(strides), anc, A, ptr(f32c(im_info)), int(pre_nms_top_n), int(post_nms_top_n), float(nms_thresh), float(min_size),
+            hs, ws_, int_array(strides), anc, A, ptr(im_info), int(pre_nms_top_n), int(post_nms_top_n), float(nms_thresh), float(min_size),
             ptr(rois), ptr(scores), ptr(num), ptr(ws))
     if joint:
         check(lib().upsnet_pyramid_proposals_joint_strided(*args), "pyramid_proposals")
@@ -538,8 +549,9 @@ def mask_roi(rois, bbox_delta, cls_prob, im_info, class_agnostic, score_thresh, 
     src = torch.empty((cap,), dtype=torch.int32, device=dev)
     num = torch.empty((1,), dtype=torch.int32, device=dev)
     ws = _ws(lib().upsnet_mask_roi_workspace_bytes(N, C, int(class_agnostic)), dev)
+    im_info, num_rois_dev = f32c(im_info.reshape(-1)), i32c(num_rois_dev)
     check(lib().upsnet_mask_roi_ex(stream(), ptr(rois), ptr(bbox_delta), ptr(cls_prob), N, ptr(num_rois_dev), C,
-                                ptr(f32c(im_info.reshape(-1))), int(class_agnostic), int(bool(clip_boxes)), float(score_thresh), float(nms_thresh),
+                                ptr(im_info), int(class_agnostic), int(bool(clip_boxes)), float(score_thresh), float(nms_thresh),
                                 int(max_det), float_array(reg_weights), ptr(boxes), ptr(scores), ptr(cls), ptr(src),
                                 ptr(num), ptr(ws)), "mask_roi")
     return boxes, scores, cls, src, num
@@ -555,8 +567,9 @@ def mask_logit_gather(mask_logit, row, cls, K=None):
         t = t.contiguous()
     K = row.shape[0] if K is None else int(K)
     out = torch.empty((K, 1, mh, mw), dtype=torch.float32, device=t.device)
+    row, cls = i32c(row), i64c(cls)      # (bound before the call: a temporary's block is free again once ptr() returns)
     check(lib().upsnet_mask_logit_gather(stream(), ptr(t), n, C, mh * mw, t.stride(0), t.stride(1), t.stride(3),
-                                         ptr(row.to(torch.int32).contiguous()), ptr(cls.to(torch.int64).contiguous()), K, ptr(out)),
+                                         ptr(row), ptr(cls), K, ptr(out)),
           "mask_logit_gather")
     return out
 
@@ -570,7 +583,7 @@ def mask_removal(mask_rois4, cls_prob, mask_logit, cls_idx, num_thing_classes, i
     m = mask_rois4.shape[0]
     mask_logit = f32c(mask_logit).reshape(m, -1)
     ms = int(round(mask_logit.shape[1] ** 0.5))
-    cls_idx = cls_idx.to(torch.int64).contiguous().reshape(-1)
+    cls_idx, m_dev = i64c(cls_idx).reshape(-1), i32c(m_dev)
     H, W = int(im_shape[0]), int(im_shape[1])
     dev = mask_rois4.device
     keep = torch.empty((m,), dtype=torch.int64, device=dev)   # (the finalize kernel zero-fills the rows past the count)
@@ -588,7 +601,8 @@ def panoptic_tail_pack(keep, num_keep, cls, scores, det_num, pan_num, extra_num)
     (rows past num_keep read row 0) and {det_num, pan_num, extra_num, num_keep} packed for the single host read."""
     require_cuda(keep, cls, scores)
     K = int(cls.shape[0])
-    cls, scores = cls.to(torch.int64).contiguous().reshape(-1), f32c(scores).reshape(-1)
+    cls, scores = i64c(cls).reshape(-1), f32c(scores).reshape(-1)
+    keep, num_keep, det_num, pan_num, extra_num = i64c(keep), i32c(num_keep), i32c(det_num), i32c(pan_num), i32c(extra_num)
     kept_cls = torch.empty((K,), dtype=torch.int64, device=cls.device)
     kept_scores = torch.empty((K,), dtype=torch.float32, device=cls.device)
     counters = torch.empty((4,), dtype=torch.int32, device=cls.device)
@@ -605,6 +619,7 @@ def mask_paste(mask_rois4, mask_logit, keep, num, real, k, im_shape):
     ms = int(round(mask_logit.shape[1] ** 0.5))
     H, W = int(im_shape[0]), int(im_shape[1])
     out = torch.empty((1, k, H, W), dtype=torch.float32, device=mask_rois4.device)
+    keep, num, real = i64c(keep), i32c(num), i32c(real)
     check(lib().upsnet_mask_paste(stream(), ptr(mask_rois4), ptr(mask_logit), ptr(keep), ptr(num), ptr(real), int(k), ms, H, W,
                                   ptr(out)), "mask_paste")
     return out
@@ -617,8 +632,8 @@ def seg_term(fcn_output, boxes4, cls, class_map):
     boxes4 = f32c(boxes4)
     k = boxes4.shape[0]
     out = torch.empty((1, k, H, W), dtype=torch.float32, device=fcn.device)
-    check(lib().upsnet_seg_term(stream(), ptr(fcn), S, H, W, ptr(boxes4), ptr(cls.to(torch.int64).contiguous()),
-                                ptr(class_map), k, ptr(out)), "seg_term")
+    cls, class_map = i64c(cls), i64c(class_map)
+    check(lib().upsnet_seg_term(stream(), ptr(fcn), S, H, W, ptr(boxes4), ptr(cls), ptr(class_map), k, ptr(out)), "seg_term")
     return out
 
 
@@ -647,8 +662,9 @@ def panoptic_fuse(fcn_output, num_stuff, mask_rois5, mask_logit, cls_idx, keep, 
     ms = int(round(mask_logit.shape[1] ** 0.5))
     pan = torch.empty((1, H, W), dtype=torch.int64, device=fcn.device)
     sem = torch.empty((1, H, W), dtype=torch.int64, device=fcn.device) if want_sem else None
+    cls_idx, keep, num, real, class_map = i64c(cls_idx), i64c(keep), i32c(num), i32c(real), i64c(class_map)
     check(lib().upsnet_panoptic_fuse(stream(), ptr(fcn), S, H, W, int(num_stuff), ptr(mask_rois5), ptr(mask_logit),
-                                     ptr(cls_idx.to(torch.int64).contiguous()), ptr(keep), ptr(num), ptr(real), int(min(m, 256)),
+                                     ptr(cls_idx), ptr(keep), ptr(num), ptr(real), int(min(m, 256)),
                                      ms, ptr(class_map), int(bool(enable_void)), ptr(pan), ptr(sem)), "panoptic_fuse")
     return pan, sem
 
@@ -674,6 +690,7 @@ def conv2d_nhwc_multi(xs, wpack, ldw, bias, cout, ksize, stride, pad, relu=False
     out_i = relu?(conv(x_i) + bias + residual_i); residual_up: residual_i is at half resolution and is added through
     a nearest x2 upsampling (FPN top-down path)."""
     require_cuda(wpack, *xs)
+    wpack = f32c(wpack)
     assert 1 <= len(xs) <= 5
     xs = [nhwc(x.float()) for x in xs]
     cin = xs[0].shape[1]
@@ -704,10 +721,11 @@ def conv2d_nhwc_multi(xs, wpack, ldw, bias, cout, ksize, stride, pad, relu=False
             if tuple(r.shape) != want or (residual_up and (o.shape[2] % 2 or o.shape[3] % 2)):
                 raise RuntimeError("conv2d_nhwc: residual shape %s != %s" % (tuple(r.shape), want))
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv2d_nhwc_f32(stream(), len(xs), ptr_array(xs), ptr_array(ress) if ress is not None else None,
                                        ptr_array(outs), int_array([x.shape[0] for x in xs]), int_array([x.shape[2] for x in xs]),
                                        int_array([x.shape[3] for x in xs]), int(cin), ptr(wpack), int(ldw),
-                                       ptr(None if bias is None else f32c(bias)), int(cout), int(ksize), int(ksize), int(stride),
+                                       ptr(bias), int(cout), int(ksize), int(ksize), int(stride),
                                        int(pad), int(bool(relu)), int(bool(residual_up and ress is not None))), "conv2d_nhwc_f32")
     if ev0 is not None:
         npix = sum(o.shape[0] * o.shape[2] * o.shape[3] for o in outs)
@@ -722,6 +740,7 @@ def conv2d_nhwc_multi(xs, wpack, ldw, bias, cout, ksize, stride, pad, relu=False
 def conv2d_nhwc_multiw(xs, wpacks, ldw, cout, ksize, stride, pad, relu=False):
     """Up to 5 maps through the same convolution GEOMETRY, each with its own packed weights, in one launch (no bias / residual)."""
     require_cuda(*xs, *wpacks)
+    wpacks = [f32c(w) for w in wpacks]
     assert 1 <= len(xs) <= 5 and len(wpacks) == len(xs)
     xs = [nhwc(x.float()) for x in xs]
     cin = xs[0].shape[1]
@@ -763,6 +782,7 @@ def conv1x1_frag(x, wpack, bias, cout, stride=1, relu=False, residual=None, resi
     x: logical NCHW (any batch), returns channels_last [N,Cout,Ho,Wo]. out: caller-provided channels_last output (a view of a larger
     tensor); ksplit > 1: the K walk of every tile split over ksplit workgroups + the reduce kernel (no residual_up)."""
     require_cuda(wpack, x)
+    wpack = f32c(wpack)
     x = nhwc(x.float())
     N, cin, H, W = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
@@ -781,12 +801,14 @@ def conv1x1_frag(x, wpack, bias, cout, stride=1, relu=False, residual=None, resi
         if residual_up:
             raise RuntimeError("conv1x1_frag: split-K has no upsampled-residual epilogue")
         ws = _ws(lib().upsnet_conv1x1_splitk_workspace_bytes(N, Ho, Wo, int(cout), int(ksplit)), x.device)
+        bias = None if bias is None else f32c(bias)
         check(lib().upsnet_conv1x1_frag_nhwc_f32_splitk(stream(), ptr(x), ptr(res), ptr(out), N, H, W, int(cin), ptr(wpack),
-                                                        ptr(None if bias is None else f32c(bias)), int(cout), int(stride), int(bool(relu)),
+                                                        ptr(bias), int(cout), int(stride), int(bool(relu)),
                                                         int(ksplit), ptr(ws)), "conv1x1_frag_nhwc_f32_splitk")
     else:
+        bias = None if bias is None else f32c(bias)
         check(lib().upsnet_conv1x1_frag_nhwc_f32(stream(), ptr(x), ptr(res), ptr(out), N, H, W, int(cin), ptr(wpack),
-                                                 ptr(None if bias is None else f32c(bias)), int(cout), int(stride), int(bool(relu)),
+                                                 ptr(bias), int(cout), int(stride), int(bool(relu)),
                                                  int(bool(residual_up and res is not None))), "conv1x1_frag_nhwc_f32")
     if ev0 is not None:
         npix = out.shape[0] * out.shape[2] * out.shape[3]
@@ -812,6 +834,7 @@ def conv1x1_ksw(x, wpack, bias, cout, tile, stride=1, relu=False, residual=None,
     splitting K, {(16, 256), (32, 128), (32, 256)} with split_n (the waves split the channels, each walks all of K).
     x: logical NCHW (any batch), returns channels_last [N,Cout,Ho,Wo]."""
     require_cuda(wpack, x)
+    wpack = f32c(wpack)
     x = nhwc(x.float())
     N, cin, H, W = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
@@ -825,8 +848,9 @@ def conv1x1_ksw(x, wpack, bias, cout, tile, stride=1, relu=False, residual=None,
         if tuple(res.shape) != tuple(out.shape):
             raise RuntimeError("conv1x1_ksw: residual shape %s != %s" % (tuple(res.shape), tuple(out.shape)))
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv1x1_ksw_nhwc_f32(stream(), ptr(x), ptr(res), ptr(out), N, H, W, int(cin), ptr(wpack),
-                                            ptr(None if bias is None else f32c(bias)), int(cout), int(stride), int(bool(relu)),
+                                            ptr(bias), int(cout), int(stride), int(bool(relu)),
                                             int(tile[0]), int(tile[1]), int(bool(split_n))), "conv1x1_ksw_nhwc_f32")
     if ev0 is not None:
         npix = out.shape[0] * out.shape[2] * out.shape[3]
@@ -850,11 +874,13 @@ def conv3x3_ksw(x, wpack, bias, cout, relu=False):
     """3x3 / stride 1 / pad 1 convolution into cout <= 32 channels on the small-tile kernel (csrc/conv1x1_ksw.hip, conv3x3_ksw_f32_kernel):
     the offset predictors of the deformable bottlenecks on small maps. x: logical NCHW, returns channels_last [N,cout,H,W]."""
     require_cuda(wpack, x)
+    wpack = f32c(wpack)
     x = nhwc(x.float())
     N, cin, H, W = x.shape
     out = _nhwc_out(N, cout, H, W, x.device)
     ev0 = _prof_begin()
-    check(lib().upsnet_conv3x3_ksw_nhwc_f32(stream(), ptr(x), ptr(out), N, H, W, int(cin), ptr(wpack), ptr(None if bias is None else f32c(bias)),
+    bias = None if bias is None else f32c(bias)
+    check(lib().upsnet_conv3x3_ksw_nhwc_f32(stream(), ptr(x), ptr(out), N, H, W, int(cin), ptr(wpack), ptr(bias),
                                             int(cout), int(bool(relu))), "conv3x3_ksw_nhwc_f32")
     if ev0 is not None:
         npix = N * H * W
@@ -868,13 +894,15 @@ def conv1x1_siblings(x, wpack, bias, cout_a, cout_b, stride=1, relu_a=True, relu
     -> out_a (ReLU flag relu_a), the remaining cout_b rows -> out_b. wpack: pack_conv1x1_weight(torch.cat([w_a, w_b])); bias: both biases
     concatenated or None. Bit-identical to two conv1x1_frag calls. Returns two channels_last tensors."""
     require_cuda(wpack, x)
+    wpack = f32c(wpack)
     x = nhwc(x.float())
     N, cin, H, W = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     out_a, out_b = _nhwc_out(N, cout_a, Ho, Wo, x.device), _nhwc_out(N, cout_b, Ho, Wo, x.device)
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv1x1_siblings_nhwc_f32(stream(), ptr(x), ptr(out_a), ptr(out_b), N, H, W, int(cin), ptr(wpack),
-                                                 ptr(None if bias is None else f32c(bias)), int(cout_a), int(cout_b), int(stride),
+                                                 ptr(bias), int(cout_a), int(cout_b), int(stride),
                                                  int(bool(relu_a)), int(bool(relu_b))), "conv1x1_siblings_nhwc_f32")
     if ev0 is not None:
         npix, cout = N * Ho * Wo, cout_a + cout_b
@@ -892,6 +920,7 @@ def conv1x1_pair(x, residual, w3pack, bias3, c1, w1pack, bias1, c2):
     out1 = relu(conv1x1(x; w3) + bias3 + residual), out2 = relu(conv1x1(out1; w1) + bias1); both bit-identical to two
     conv1x1_frag calls. x: logical NCHW; returns two channels_last tensors."""
     require_cuda(w3pack, w1pack, x, residual)
+    w3pack, w1pack = f32c(w3pack), f32c(w1pack)
     x, res = nhwc(x.float()), nhwc(residual.float())
     N, c0, H, W = x.shape
     if tuple(res.shape) != (N, c1, H, W):
@@ -901,9 +930,11 @@ def conv1x1_pair(x, residual, w3pack, bias3, c1, w1pack, bias1, c2):
         lib().upsnet_conv1x1_pair32_tuning(PAIR32_WAVES)
         _pair32_waves_set[0] = PAIR32_WAVES
     ev0 = _prof_begin()
+    bias3 = None if bias3 is None else f32c(bias3)
+    bias1 = None if bias1 is None else f32c(bias1)
     check(lib().upsnet_conv1x1_pair_nhwc_f32(stream(), ptr(x), ptr(res), ptr(out1), ptr(out2), N * H * W, int(c0), ptr(w3pack),
-                                             ptr(None if bias3 is None else f32c(bias3)), int(c1), ptr(w1pack),
-                                             ptr(None if bias1 is None else f32c(bias1)), int(c2)), "conv1x1_pair_nhwc_f32")
+                                             ptr(bias3), int(c1), ptr(w1pack),
+                                             ptr(bias1), int(c2)), "conv1x1_pair_nhwc_f32")
     if ev0 is not None:
         npix = N * H * W
         _prof_end(ev0, 'conv', 2.0 * (c1 * c0 + c2 * c1) * npix, 4.0 * (c0 * npix + 2 * c1 * npix + c2 * npix + c1 * c0 + c2 * c1),
@@ -921,7 +952,8 @@ def fcn_score_combine(parts, bias=None):
         if tuple(t.shape) != (1, S, H >> l, W >> l):
             raise RuntimeError("fcn_score_combine: level %d has shape %s, expected %s" % (l, tuple(t.shape), (1, S, H >> l, W >> l)))
     out = _nhwc_out(1, S, H, W, parts[0].device)
-    check(lib().upsnet_fcn_score_combine(stream(), len(parts), ptr_array(parts), S, H, W, ptr(None if bias is None else f32c(bias)),
+    bias = None if bias is None else f32c(bias)
+    check(lib().upsnet_fcn_score_combine(stream(), len(parts), ptr_array(parts), S, H, W, ptr(bias),
                                          ptr(out)), "fcn_score_combine")
     return out
 
@@ -944,8 +976,9 @@ def panoptic_fuse_up(fcn_score, scale, num_stuff, mask_rois5, mask_logit, cls_id
     H, W = Hs * scale, Ws * scale
     pan = torch.empty((1, H, W), dtype=torch.int64, device=sc.device)
     sem = torch.empty((1, H, W), dtype=torch.int64, device=sc.device) if want_sem else None
+    cls_idx, keep, num, real, class_map = i64c(cls_idx), i64c(keep), i32c(num), i32c(real), i64c(class_map)
     args = (stream(), ptr(sc), int(is_nhwc), S, Hs, Ws, int(scale), int(num_stuff), ptr(mask_rois5), ptr(mask_logit),
-            ptr(cls_idx.to(torch.int64).contiguous()), ptr(keep), ptr(num), ptr(real), int(min(m, 256)), ms, ptr(class_map), ptr(pan), ptr(sem))
+            ptr(cls_idx), ptr(keep), ptr(num), ptr(real), int(min(m, 256)), ms, ptr(class_map), ptr(pan), ptr(sem))
     if not want_conf:
         check(lib().upsnet_panoptic_fuse_up(*args), "panoptic_fuse_up")
         return pan, sem
@@ -1002,6 +1035,7 @@ def stem_pool_f32(x4, wpack, bias):
     """max_pool2d(relu(conv7x7/2/3(x) + bias), 3, 2, 1) in one launch; x4: logical [N,4,H,W] channels_last fp32 (image_to_nhwc4 /
     prep_image_u8). Returns channels_last fp32 [N,64,Hp,Wp]."""
     require_cuda(x4, wpack)
+    wpack = f32c(wpack)
     x4 = nhwc(x4.float())
     N, C, H, W = x4.shape
     if C != 4:
@@ -1010,7 +1044,8 @@ def stem_pool_f32(x4, wpack, bias):
     Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
     out = _nhwc_out(N, 64, Hp, Wp, x4.device)
     ev0 = _prof_begin()
-    check(lib().upsnet_stem_pool_f32(stream(), ptr(x4), N, H, W, ptr(wpack), ptr(None if bias is None else f32c(bias)), ptr(out)), "stem_pool_f32")
+    bias = None if bias is None else f32c(bias)
+    check(lib().upsnet_stem_pool_f32(stream(), ptr(x4), N, H, W, ptr(wpack), ptr(bias), ptr(out)), "stem_pool_f32")
     if ev0 is not None:
         _prof_end(ev0, 'conv', 2.0 * 64 * 147 * N * Hc * Wc, 16.0 * N * H * W + 4.0 * 64 * N * Hp * Wp + 4.0 * 64 * 147, 'stem + pool')
     return out
@@ -1031,6 +1066,7 @@ def stem_pool_bf16(x4, wpack, bias):
     """relu(conv7x7/2/3(x) + bias) -> max_pool 3x3/2/1 in one launch; x4: logical [N,4,H,W] channels_last fp32 (image_to_nhwc4 /
     prep_image_u8). Returns a bf16 channels_last [N,64,Hp,Wp]."""
     require_cuda(x4, wpack)
+    wpack = wpack.contiguous()
     x4 = nhwc(x4.float())
     N, C, H, W = x4.shape
     if C != 4:
@@ -1039,7 +1075,8 @@ def stem_pool_bf16(x4, wpack, bias):
     Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
     out = torch.empty((N, Hp, Wp, 64), dtype=torch.bfloat16, device=x4.device).permute(0, 3, 1, 2)
     ev0 = _prof_begin()
-    check(lib().upsnet_stem_pool_bf16(stream(), ptr(x4), N, H, W, ptr(wpack), ptr(None if bias is None else f32c(bias)), ptr(out)), "stem_pool_bf16")
+    bias = None if bias is None else f32c(bias)
+    check(lib().upsnet_stem_pool_bf16(stream(), ptr(x4), N, H, W, ptr(wpack), ptr(bias), ptr(out)), "stem_pool_bf16")
     if ev0 is not None:
         _prof_end(ev0, 'conv_bf16', 2.0 * 64 * 147 * N * Hc * Wc, 16.0 * N * H * W + 2.0 * 64 * N * Hp * Wp)
     return out
@@ -1058,6 +1095,7 @@ def image_to_nhwc4(x):
 def conv2d_stem(x4, wpack, ldw, bias, cout, kh, kw, stride, pad, relu=False):
     """x4: logical [N,4,H,W] channels_last (from image_to_nhwc4 / prep_image_u8). Returns channels_last [N,Cout,Ho,Wo]."""
     require_cuda(x4, wpack)
+    wpack = f32c(wpack)
     x4 = nhwc(x4.float())
     N, C, H, W = x4.shape
     if C != 4:
@@ -1065,7 +1103,8 @@ def conv2d_stem(x4, wpack, ldw, bias, cout, kh, kw, stride, pad, relu=False):
     Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
     out = _nhwc_out(N, cout, Ho, Wo, x4.device)
     ev0 = _prof_begin()
-    check(lib().upsnet_conv2d_stem_nhwc4_f32(stream(), ptr(x4), N, H, W, ptr(wpack), int(ldw), ptr(None if bias is None else f32c(bias)),
+    bias = None if bias is None else f32c(bias)
+    check(lib().upsnet_conv2d_stem_nhwc4_f32(stream(), ptr(x4), N, H, W, ptr(wpack), int(ldw), ptr(bias),
                                              int(cout), int(kh), int(kw), int(stride), int(pad), int(bool(relu)), ptr(out)),
           "conv2d_stem_nhwc4_f32")
     if ev0 is not None:
@@ -1089,11 +1128,13 @@ def pack_deconv2x2_weight(weight):
 def deconv2x2(x, wpack, ldw, bias, cout, relu=False):
     """ConvTranspose2d(k=2, s=2, p=0) (+bias, +ReLU) on a logical NCHW tensor; returns channels_last [N,Cout,2H,2W]."""
     require_cuda(x, wpack)
+    wpack = f32c(wpack)
     x = nhwc(x.float())
     N, C, H, W = x.shape
     out = _nhwc_out(N, cout, 2 * H, 2 * W, x.device)
     ev0 = _prof_begin()
-    check(lib().upsnet_deconv2x2_nhwc_f32(stream(), ptr(x), N, H, W, C, ptr(wpack), int(ldw), ptr(None if bias is None else f32c(bias)),
+    bias = None if bias is None else f32c(bias)
+    check(lib().upsnet_deconv2x2_nhwc_f32(stream(), ptr(x), N, H, W, C, ptr(wpack), int(ldw), ptr(bias),
                                           int(cout), int(bool(relu)), ptr(out)), "deconv2x2_nhwc_f32")
     if ev0 is not None:
         _prof_end(ev0, 'conv', 2.0 * 4 * cout * C * N * H * W, 4.0 * (C * N * H * W + 4 * cout * N * H * W + 4 * cout * C))
@@ -1114,6 +1155,7 @@ def pack_deconv2x2_weight_frag(weight, bias):
 def deconv2x2_frag(x, wpack, bias4, cout, relu=False):
     """ConvTranspose2d(k=2, s=2, p=0) (+bias, +ReLU) on the lean GEMM kernel; returns channels_last [N,Cout,2H,2W]."""
     require_cuda(x, wpack)
+    wpack, bias4 = f32c(wpack), f32c(bias4)
     x = nhwc(x.float())
     N, C, H, W = x.shape
     out = _nhwc_out(N, cout, 2 * H, 2 * W, x.device)
@@ -1140,6 +1182,7 @@ def pack_deconv2x2_weight_bf16(weight):
 def deconv2x2_bf16(x, whi, ldw, bias, cout, relu=False, out_dtype=torch.float32):
     """ConvTranspose2d(k=2, s=2, p=0) (+bias, +ReLU) of a bf16 map on the bf16 matrix cores; channels_last [N,Cout,2H,2W]."""
     require_cuda(x, whi)
+    whi = whi.contiguous()
     if x.dtype != torch.bfloat16:
         raise RuntimeError("deconv2x2_bf16: expects a bf16 map")
     x = nhwc(x)
@@ -1148,7 +1191,8 @@ def deconv2x2_bf16(x, whi, ldw, bias, cout, relu=False, out_dtype=torch.float32)
     out = (torch.empty((N, 2 * H, 2 * W, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2) if out16
            else _nhwc_out(N, cout, 2 * H, 2 * W, x.device))
     ev0 = _prof_begin()
-    check(lib().upsnet_deconv2x2_nhwc_bf16(stream(), ptr(x), N, H, W, C, ptr(whi), int(ldw), ptr(None if bias is None else f32c(bias)),
+    bias = None if bias is None else f32c(bias)
+    check(lib().upsnet_deconv2x2_nhwc_bf16(stream(), ptr(x), N, H, W, C, ptr(whi), int(ldw), ptr(bias),
                                            int(cout), int(bool(relu)), ptr(out), int(out16)), "deconv2x2_nhwc_bf16")
     if ev0 is not None:
         _prof_end(ev0, 'conv_bf16', 2.0 * 4 * cout * C * N * H * W,
@@ -1167,7 +1211,7 @@ def prep_image_u8(image_hwc, pixel_means, im_scale, resized_hw, padded_hw, nhwc4
     (Hr, Wr), (Hp, Wp) = resized_hw, padded_hw
     means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
     out = _nhwc_out(1, 4, Hp, Wp, im.device) if nhwc4 else torch.empty((1, 3, Hp, Wp), dtype=torch.float32, device=im.device)
-    check(lib().upsnet_prep_image_u8(stream(), ptr(im), H, W, ctypes.cast(means, ctypes.c_void_p), float(im_scale), int(Hr), int(Wr),
+    check(lib().upsnet_prep_image_u8(stream(), ptr(im), H, W, means, float(im_scale), int(Hr), int(Wr),
                                      int(Hp), int(Wp), int(bool(nhwc4)), ptr(out)), "prep_image_u8")
     return out
 
@@ -1395,8 +1439,8 @@ def combined_pan_result(segs, boxes, masks, id_last_stuff, score_threshold=0.6, 
         npx = hw[:, 0] * hw[:, 1]
         img = np.zeros((len(ch), 8), np.int64)
         img[:, 0:2] = hw
-        img[:, 2] = [seg_t[i].data_ptr() for i in ch]
-        img[:, 3] = [out[i].data_ptr() for i in ch]
+        img[:, 2] = [addr(seg_t[i]) for i in ch]
+        img[:, 3] = [addr(out[i]) for i in ch]
         img[:, 4], img[:, 5] = cbeg[:-1], cbeg[1:]
         img[:, 6] = np.concatenate([[0], np.cumsum((npx + 63) // 64)[:-1]])
         img[:, 7] = np.concatenate([[0], np.cumsum(npx)[:-1]])
@@ -1434,6 +1478,7 @@ def pq_accumulate(pred_2ch, gt_rgb, segments, cat_known, image_index, max_gt, wo
                      (iou, torch.float64, 256), (status, torch.int64, 1)):
         if t.dtype != dt or t.numel() != n or not t.is_contiguous():
             raise ValueError("pq_accumulate: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
+    written(workspace, None, "pq_accumulate: workspace")
     pred_2ch, gt_rgb, segments = pred_2ch.contiguous(), gt_rgb.contiguous(), segments.contiguous()
     H, W = pred_2ch.shape[:2]
     check(lib().upsnet_pq_accumulate(stream(), ptr(pred_2ch), ptr(gt_rgb), H, W, ptr(segments) if segments.numel() else None,
@@ -1542,7 +1587,9 @@ def mask_roi_dedup(a_src, a_cls, a_num, b_src, b_cls, b_boxes, b_num):
     mp = torch.empty((cap_b,), dtype=torch.int32, device=dev)
     extra = torch.empty((cap_b, 5), dtype=torch.float32, device=dev)
     n_extra = torch.empty((1,), dtype=torch.int32, device=dev)
-    check(lib().upsnet_mask_roi_dedup(stream(), ptr(a_src), ptr(a_cls), ptr(a_num), cap_a, ptr(b_src), ptr(b_cls), ptr(f32c(b_boxes)),
+    a_src, a_cls, a_num = i32c(a_src), i64c(a_cls), i32c(a_num)
+    b_src, b_cls, b_boxes, b_num = i32c(b_src), i64c(b_cls), f32c(b_boxes), i32c(b_num)
+    check(lib().upsnet_mask_roi_dedup(stream(), ptr(a_src), ptr(a_cls), ptr(a_num), cap_a, ptr(b_src), ptr(b_cls), ptr(b_boxes),
                                       ptr(b_num), cap_b, ptr(mp), ptr(extra), ptr(n_extra)), "mask_roi_dedup")
     return mp, extra, n_extra
 
@@ -1570,6 +1617,7 @@ def pack_winograd_weight(weight, tn32=False):
 def conv2d_winograd_splitk(x, wpack, ldw, bias, cout, ksplit, relu=False, residual=None):
     """conv2d_winograd for one small map with the K walk split over `ksplit` workgroups per tile (+ the shared reduce kernel)."""
     require_cuda(x, wpack)
+    wpack = f32c(wpack)
     x = nhwc(x.float())
     N, C, H, W = x.shape
     out = _nhwc_out(N, cout, H, W, x.device)
@@ -1580,8 +1628,9 @@ def conv2d_winograd_splitk(x, wpack, ldw, bias, cout, ksplit, relu=False, residu
             raise RuntimeError("conv2d_winograd_splitk: residual shape %s != %s" % (tuple(res.shape), tuple(out.shape)))
     ws = _ws(lib().upsnet_conv2d_splitk_workspace_bytes(N, H, W, int(cout), 3, 3, 1, 1, int(ksplit)), x.device)
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv2d_winograd_nhwc_f32_splitk(stream(), ptr(x), ptr(res), ptr(out), N, H, W, C, ptr(wpack), int(ldw),
-                                                       ptr(None if bias is None else f32c(bias)), int(cout), int(bool(relu)), int(ksplit),
+                                                       ptr(bias), int(cout), int(bool(relu)), int(ksplit),
                                                        ptr(ws)), "conv2d_winograd_nhwc_f32_splitk")
     if ev0 is not None:
         npix = N * H * W
@@ -1595,12 +1644,14 @@ def conv2d_winograd_tail(x, wpack, ldw, wpack32, ldw32, bias, cout, n_main, relu
     conv_wino16_tail_f32_kernel): images [0, n_main) on 32 x 64 tiles, the rest on 32 x 32 tiles (wpack32 from
     pack_winograd_weight(w, tn32=True)). Bit-identical to conv2d_winograd_multi([x], ...)."""
     require_cuda(wpack, wpack32, x)
+    wpack, wpack32 = f32c(wpack), f32c(wpack32)
     x = nhwc(x.float())
     N, C, H, W = x.shape
     out = _nhwc_out(N, cout, H, W, x.device)
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv2d_winograd_nhwc_f32_tail(stream(), ptr(x), ptr(out), int(N), int(n_main), int(H), int(W), int(C), ptr(wpack), int(ldw),
-                                                     ptr(wpack32), int(ldw32), ptr(None if bias is None else f32c(bias)), int(cout),
+                                                     ptr(wpack32), int(ldw32), ptr(bias), int(cout),
                                                      int(bool(relu))), "conv2d_winograd_nhwc_f32_tail")
     if ev0 is not None:
         npix = N * H * W
@@ -1614,6 +1665,7 @@ def conv2d_winograd_multi(xs, wpack, ldw, bias, cout, relu=False, residuals=None
     conv2d_nhwc_multi. outs: caller-provided channels_last outputs (e.g. batch slices of one tensor); tn32: the 32-channel workgroup
     form (wpack from pack_winograd_weight(w, tn32=True))."""
     require_cuda(wpack, *xs)
+    wpack = f32c(wpack)
     assert 1 <= len(xs) <= 5
     xs = [nhwc(x.float()) for x in xs]
     cin = xs[0].shape[1]
@@ -1636,10 +1688,11 @@ def conv2d_winograd_multi(xs, wpack, ldw, bias, cout, relu=False, residuals=None
                 raise RuntimeError("conv2d_winograd: residual shape %s != %s" % (tuple(r.shape), tuple(o.shape)))
     ev0 = _prof_begin()
     fn = lib().upsnet_conv2d_winograd_nhwc_f32_tn32 if tn32 else lib().upsnet_conv2d_winograd_nhwc_f32
+    bias = None if bias is None else f32c(bias)
     check(fn(stream(), len(xs), ptr_array(xs), ptr_array(ress) if ress is not None else None,
              ptr_array(outs), int_array([x.shape[0] for x in xs]), int_array([x.shape[2] for x in xs]),
              int_array([x.shape[3] for x in xs]), int(cin), ptr(wpack), int(ldw),
-             ptr(None if bias is None else f32c(bias)), int(cout), int(bool(relu))),
+             ptr(bias), int(cout), int(bool(relu))),
           "conv2d_winograd_nhwc_f32")
     if ev0 is not None:
         npix = sum(o.shape[0] * o.shape[2] * o.shape[3] for o in outs)
@@ -1667,6 +1720,7 @@ def conv2d_winograd36_multi(xs, wpack, ldw, bias, cout, relu=False, outs=None):
     """3x3 / stride 1 / pad 1 convolution (+ bias, ReLU) of up to 5 maps (shared weights) by Winograd F(4x4,3x3): the contract of
     conv2d_winograd_multi without residuals (csrc/conv_wino36.hip)."""
     require_cuda(wpack, *xs)
+    wpack = f32c(wpack)
     assert 1 <= len(xs) <= 5
     xs = [nhwc(x.float()) for x in xs]
     cin = xs[0].shape[1]
@@ -1683,9 +1737,10 @@ def conv2d_winograd36_multi(xs, wpack, ldw, bias, cout, relu=False, outs=None):
         else:
             outs.append(_nhwc_out(N, cout, H, W, x.device))
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv2d_winograd36_nhwc_f32(stream(), len(xs), ptr_array(xs), ptr_array(outs), int_array([x.shape[0] for x in xs]),
                                                   int_array([x.shape[2] for x in xs]), int_array([x.shape[3] for x in xs]), int(cin), ptr(wpack),
-                                                  int(ldw), ptr(None if bias is None else f32c(bias)), int(cout), int(bool(relu))),
+                                                  int(ldw), ptr(bias), int(cout), int(bool(relu))),
           "conv2d_winograd36_nhwc_f32")
     if ev0 is not None:
         npix = sum(o.shape[0] * o.shape[2] * o.shape[3] for o in outs)
@@ -1698,13 +1753,15 @@ def conv2d_winograd36_splitk(x, wpack, ldw, bias, cout, ksplit, relu=False):
     """conv2d_winograd36_multi for ONE map with the channel walk of every tile split over `ksplit` workgroups + the reduce / epilogue kernel
     (csrc/conv_wino36.hip, r13): maps with fewer 32-tile x 64-channel workgroups than CUs."""
     require_cuda(wpack, x)
+    wpack = f32c(wpack)
     x = nhwc(x.float())
     N, cin, H, W = x.shape
     out = _nhwc_out(N, cout, H, W, x.device)
     ws = _ws(lib().upsnet_conv2d_winograd36_splitk_workspace_bytes(N, H, W, int(cout), int(ksplit)), x.device)
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv2d_winograd36_nhwc_f32_splitk(stream(), ptr(x), ptr(out), N, H, W, int(cin), ptr(wpack), int(ldw),
-                                                         ptr(None if bias is None else f32c(bias)), int(cout), int(bool(relu)), int(ksplit), ptr(ws)),
+                                                         ptr(bias), int(cout), int(bool(relu)), int(ksplit), ptr(ws)),
           "conv2d_winograd36_nhwc_f32_splitk")
     if ev0 is not None:
         npix = N * H * W
@@ -1735,6 +1792,7 @@ def conv2d_nhwc_bf16_multi(xs, whi, wlo, ldw, bias, cout, ksize, stride, pad, re
     Plain bf16 mode only: inputs / residuals may be torch.bfloat16 tensors (all maps of a launch alike) and out_dtype may be
     torch.bfloat16 -- bf16 activations between layers (the kernels then load / store 2-byte elements, no conversion pass)."""
     require_cuda(whi, *xs)
+    whi, wlo = whi.contiguous(), None if wlo is None else wlo.contiguous()
     assert 1 <= len(xs) <= 5
     in16 = xs[0].dtype == torch.bfloat16
     out16 = out_dtype == torch.bfloat16
@@ -1763,10 +1821,11 @@ def conv2d_nhwc_bf16_multi(xs, whi, wlo, ldw, bias, cout, ksize, stride, pad, re
             if tuple(r.shape) != want:
                 raise RuntimeError("conv2d_nhwc_bf16: residual shape %s != %s" % (tuple(r.shape), want))
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv2d_nhwc_bf16(stream(), len(xs), ptr_array(xs), ptr_array(ress) if ress is not None else None, ptr_array(outs),
                                         int_array([x.shape[0] for x in xs]), int_array([x.shape[2] for x in xs]),
                                         int_array([x.shape[3] for x in xs]), int(cin), ptr(whi), ptr(wlo), int(ldw),
-                                        ptr(None if bias is None else f32c(bias)), int(cout), int(ksize), int(ksize), int(stride), int(pad),
+                                        ptr(bias), int(cout), int(ksize), int(ksize), int(stride), int(pad),
                                         int(bool(relu)) | (2 if (residual_up and ress is not None) else 0) | (4 if in16 else 0) |
                                         (8 if out16 else 0) | (16 if res16 else 0)), "conv2d_nhwc_bf16")
     if ev0 is not None:
@@ -1820,6 +1879,7 @@ def bottleneck_proj_bf16(x, pack, stride):
     """relu(conv3(relu(conv2(relu(conv1_s(x))))) + proj_s(x)) of a stage's first bottleneck in one launch; x, result: bf16 channels_last."""
     w1, w2, w3d, b1, b2, b3d, cm, cin = pack
     require_cuda(x, w1)
+    w1, w2, w3d, b1, b2, b3d = w1.contiguous(), w2.contiguous(), w3d.contiguous(), f32c(b1), f32c(b2), f32c(b3d)
     if x.dtype != torch.bfloat16 or x.shape[1] != cin:
         raise RuntimeError("bottleneck_proj_bf16: expects a bf16 map of %d channels" % cin)
     x = nhwc(x)
@@ -1839,6 +1899,7 @@ def bottleneck_bf16(x, pack):
     """relu(conv3(relu(conv2(relu(conv1(x))))) + x) of an identity bottleneck in one launch; x, result: bf16 NHWC-strided NCHW."""
     w1, w2, w3, b1, b2, b3, cm = pack
     require_cuda(x, w1)
+    w1, w2, w3, b1, b2, b3 = w1.contiguous(), w2.contiguous(), w3.contiguous(), f32c(b1), f32c(b2), f32c(b3)
     if x.dtype != torch.bfloat16 or x.shape[1] != 4 * cm:
         raise RuntimeError("bottleneck_bf16: expects a bf16 map of %d channels" % (4 * cm))
     x = nhwc(x)
@@ -1855,6 +1916,7 @@ def bottleneck_bf16(x, pack):
 def conv2d_nhwc_splitk(x, wpack, ldw, bias, cout, ksize, stride, pad, ksplit, relu=False, residual=None):
     """conv2d_nhwc for one small map with the K walk split over `ksplit` workgroups per tile (+ a reduce/epilogue kernel)."""
     require_cuda(x, wpack)
+    wpack = f32c(wpack)
     x = nhwc(x.float())
     N, C, H, W = x.shape
     Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
@@ -1866,8 +1928,9 @@ def conv2d_nhwc_splitk(x, wpack, ldw, bias, cout, ksize, stride, pad, ksplit, re
             raise RuntimeError("conv2d_nhwc_splitk: residual shape %s != %s" % (tuple(res.shape), tuple(out.shape)))
     ws = _ws(lib().upsnet_conv2d_splitk_workspace_bytes(N, H, W, int(cout), int(ksize), int(ksize), int(stride), int(pad), int(ksplit)), x.device)
     ev0 = _prof_begin()
+    bias = None if bias is None else f32c(bias)
     check(lib().upsnet_conv2d_nhwc_f32_splitk(stream(), ptr(x), ptr(res), ptr(out), N, H, W, C, ptr(wpack), int(ldw),
-                                              ptr(None if bias is None else f32c(bias)), int(cout), int(ksize), int(ksize), int(stride),
+                                              ptr(bias), int(cout), int(ksize), int(ksize), int(stride),
                                               int(pad), int(bool(relu)), int(ksplit), ptr(ws)), "conv2d_nhwc_f32_splitk")
     if ev0 is not None:
         npix = N * Ho * Wo
@@ -1899,6 +1962,7 @@ def proposal_recall(problems, proposals, gt_boxes, max_gt, total_proposals, work
     if not 0 <= int(max_gt) <= PROPOSAL_RECALL_MAX_GT:
         raise ValueError("proposal_recall: %d GT boxes in a problem (at most %d)" % (int(max_gt), PROPOSAL_RECALL_MAX_GT))
     n = int(problems.shape[0])
+    written(workspace, None, "proposal_recall: workspace")
     if workspace.numel() * workspace.element_size() < proposal_recall_workspace_bytes(n, total_proposals):
         raise ValueError("proposal_recall: workspace of %d bytes, %d needed" % (workspace.numel() * workspace.element_size(),
                                                                              proposal_recall_workspace_bytes(n, total_proposals)))
@@ -2010,6 +2074,8 @@ def _pan_track_step(what, pan_2ch, iou_thresh, max_age, frame, workspace, memory
         raise ValueError("pan_track_step: out must be contiguous uint8 [%d,%d,3], got %s %s" % (H, W, tuple(out.shape), out.dtype))
     if memory.dtype != torch.int16 or tuple(memory.shape) != (H, W) or not memory.is_contiguous():
         raise ValueError("pan_track_step: memory must be a contiguous int16 [%d,%d] tensor, got %s %s" % (H, W, tuple(memory.shape), memory.dtype))
+    written(workspace, None, "pan_track_step: workspace")
+    written(motion_workspace, None, "pan_track_step: motion_workspace")
     need = int(lib().upsnet_pan_track_workspace_bytes(H, W))
     if need == 0 or workspace.numel() * workspace.element_size() < need:
         raise ValueError("pan_track_step: workspace too small for (or no workspace exists for) a frame of %d x %d" % (H, W))
@@ -2040,6 +2106,7 @@ def pan_stable_colors(pred_2ch, cat_table, mode, out):
     H, W = int(pred_2ch.shape[0]), int(pred_2ch.shape[1])
     if out.dtype != torch.uint8 or out.numel() != H * W * 3 or not out.is_contiguous():
         raise ValueError("pan_stable_colors: out must be a contiguous uint8 tensor of %d bytes" % (H * W * 3))
+    cat_table = i32c(cat_table)
     check(lib().upsnet_pan_stable_colors(stream(), ptr(pred_2ch), H, W, ptr(cat_table), int(mode), ptr(out)), "pan_stable_colors")
     return out
 

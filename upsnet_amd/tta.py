@@ -140,8 +140,9 @@ def box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_th
     if num.dtype != torch.int32 or num.numel() != 1 or (num_rois_dev is not None and (num_rois_dev.dtype != torch.int32 or num_rois_dev.numel() != 1)):
         raise ValueError("box_vote: the counts must be one int32 each")
     voted = torch.empty((cap, 5), dtype=torch.float32, device=boxes.device)
+    im_info = f32c(im_info.reshape(-1))
     check(lib().upsnet_box_vote(stream(), ptr(rois), ptr(bbox_delta), ptr(cls_prob), N, ptr(num_rois_dev), C,
-                                ptr(f32c(im_info.reshape(-1))), int(bool(clip_boxes)), float_array(reg_weights), float(vote_score_thresh),
+                                ptr(im_info), int(bool(clip_boxes)), float_array(reg_weights), float(vote_score_thresh),
                                 float(vote_iou_thresh), ptr(boxes) if cap else None, ptr(cls) if cap else None, ptr(num), cap,
                                 ptr(voted) if cap else None), "box_vote")
     return voted
@@ -174,8 +175,9 @@ def mask_roi_soft(rois, bbox_delta, cls_prob, im_info, score_thresh, nms_thresh,
     src = torch.empty((cap,), dtype=torch.int32, device=dev)
     num = torch.empty((1,), dtype=torch.int32, device=dev)
     ws = torch.empty((int(lib().upsnet_mask_roi_soft_workspace_bytes(N, C)),), dtype=torch.uint8, device=dev)
+    im_info = f32c(im_info.reshape(-1))
     check(lib().upsnet_mask_roi_soft(stream(), ptr(rois), ptr(bbox_delta), ptr(cls_prob), N, ptr(num_rois_dev), C,
-                                     ptr(f32c(im_info.reshape(-1))), int(bool(clip_boxes)), float(score_thresh), float(nms_thresh),
+                                     ptr(im_info), int(bool(clip_boxes)), float(score_thresh), float(nms_thresh),
                                      int(max_det), float_array(reg_weights), int(method), float(sigma), float(floor), ptr(boxes),
                                      ptr(scores), ptr(cls), ptr(src), ptr(num), ptr(ws)), "mask_roi_soft")
     return boxes, scores, cls, src, num
