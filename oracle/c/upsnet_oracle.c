@@ -35,6 +35,43 @@
 static int orc_threads = 1;
 void orc_set_threads(int n) { orc_threads = n > 0 ? n : 1; }
 
+/* float -> integer conversions with every input defined. C leaves the conversion of a NaN or of a value outside the target's range
+ * undefined (x86 happens to give INT_MIN, and an optimiser may assume it never happens); the reference's kernels run where the
+ * conversion instruction is defined: NaN -> 0, out of range -> the nearest end of the range (CUDA cvt.rzi, AMD v_cvt_i32_f32), and
+ * that is what the restatement takes. In-range values truncate toward zero as the cast does, so no result of an in-range input changes.
+ * orc_mask_removal and orc_seg_term restate numpy / Python host code, not a kernel: there the reference itself is no guide for such
+ * values (astype(int32) gives INT_MIN on x86, int() of inf or NaN raises), and the same saturating rule is taken because it is what
+ * the HIP kernels under test (csrc/panoptic.hip) compute -- a choice that follows the product, not the reference.
+ * orc_wrap_add / orc_wrap_sub: int32 arithmetic that wraps (numpy's int32 scalars and the device's integer unit) instead of
+ * overflowing. */
+static int orc_f2i(float v)
+{
+    if (v != v) return 0;
+    if (v >= 2147483648.0f) return INT32_MAX;
+    if (v <= -2147483648.0f) return INT32_MIN;
+    return (int)v;
+}
+static long orc_f2l(float v)
+{
+    if (v != v) return 0;
+    if (v >= 9223372036854775808.0f) return INT64_MAX;
+    if (v <= -9223372036854775808.0f) return INT64_MIN;
+    return (long)v;
+}
+/* sampling_ratio <= 0: the sampling grid of a bin is ceil(roi size / pooled size) per axis, unbounded in the reference (a ROI of 1e9
+ * or inf asks for 1e8 .. 2^31 samples per bin and axis: its kernel would not return). The restatement REFUSES a ROI whose adaptive
+ * grid is NaN or beyond ORC_MAX_GRID per axis -- a feature map of 2^15 cells pooled to 7 needs 4682 -- : its rows of the forward output
+ * are 0 and it adds nothing in the backward pass. The HIP kernels have no such refusal; no test compares them on such a ROI. */
+#define ORC_MAX_GRID 8192
+static int orc_adaptive_grid(float roi_size, int pooled) /* -1: refused */
+{
+    const float g = ceilf(roi_size / (float)pooled);
+    if (!(g >= 0.0f && g <= (float)ORC_MAX_GRID)) return -1;
+    return (int)g;
+}
+static int orc_wrap_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
+static int orc_wrap_sub(int a, int b) { return (int)((unsigned)a - (unsigned)b); }
+
 
 /* ------------------------------------------------------------------------------------------
  * ROIAlign forward, NCHW.  upsnet/operators/src/roi_align_kernel.cu:43-95 (bilinear_interpolate)
@@ -46,7 +83,7 @@ static float orc_roi_bilinear(const float *data, int height, int width, float y,
     if (y < -1.0f || y > (float)height || x < -1.0f || x > (float)width) return 0.0f;
     if (y <= 0) y = 0; /* :56-61 */
     if (x <= 0) x = 0;
-    int y_low = (int)y, x_low = (int)x, y_high, x_high; /* :63-66 */
+    int y_low = orc_f2i(y), x_low = orc_f2i(x), y_high, x_high; /* :63-66; only a NaN gets here out of range (it fails no test above) */
     if (y_low >= height - 1) { y_high = y_low = height - 1; y = (float)y_low; } else { y_high = y_low + 1; }
     if (x_low >= width - 1) { x_high = x_low = width - 1; x = (float)x_low; } else { x_high = x_low + 1; }
     float ly = y - (float)y_low, lx = x - (float)x_low; /* :82-84 */
@@ -77,8 +114,12 @@ void orc_roi_align_forward(const float *feat, int channels, int height, int widt
         float roi_height = fmaxf(roi_end_h - roi_start_h, 1.0f);
         float bin_size_h = roi_height / (float)pooled_h;
         float bin_size_w = roi_width / (float)pooled_w;
-        int grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_height / (float)pooled_h);
-        int grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_width / (float)pooled_w);
+        int grid_h = sampling_ratio > 0 ? sampling_ratio : orc_adaptive_grid(roi_height, pooled_h);
+        int grid_w = sampling_ratio > 0 ? sampling_ratio : orc_adaptive_grid(roi_width, pooled_w);
+        if (grid_h < 0 || grid_w < 0) {                   /* refused, see ORC_MAX_GRID */
+            memset(out + (size_t)n * channels * pooled_h * pooled_w, 0, sizeof(float) * (size_t)channels * pooled_h * pooled_w);
+            continue;
+        }
         const float count = (float)(grid_h * grid_w);     /* :212 */
         for (int c = 0; c < channels; ++c) {
             const float *plane = feat + ((size_t)roi_batch_ind * channels + c) * height * width;
@@ -110,7 +151,7 @@ void orc_roi_align_forward(const float *feat, int channels, int height, int widt
  * ---------------------------------------------------------------------------------------- */
 static float orc_dcn_bilinear(const float *plane, int height, int width, float h, float w)
 {
-    int h_low = (int)floorf(h), w_low = (int)floorf(w);
+    int h_low = orc_f2i(floorf(h)), w_low = orc_f2i(floorf(w));    /* the callers' range tests let a NaN through, nothing else */
     int h_high = h_low + 1, w_high = w_low + 1;
     float lh = h - (float)h_low, lw = w - (float)w_low;
     float hh = 1.0f - lh, hw = 1.0f - lw;
@@ -182,8 +223,9 @@ void orc_roi_align_backward(const float *top_diff, const float *rois, int num_ro
         float roi_end_w = r[3] * spatial_scale, roi_end_h = r[4] * spatial_scale;
         float roi_width = fmaxf(roi_end_w - roi_start_w, 1.0f), roi_height = fmaxf(roi_end_h - roi_start_h, 1.0f);
         float bin_size_h = roi_height / (float)pooled_h, bin_size_w = roi_width / (float)pooled_w;
-        int grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_height / (float)pooled_h);
-        int grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_width / (float)pooled_w);
+        int grid_h = sampling_ratio > 0 ? sampling_ratio : orc_adaptive_grid(roi_height, pooled_h);
+        int grid_w = sampling_ratio > 0 ? sampling_ratio : orc_adaptive_grid(roi_width, pooled_w);
+        if (grid_h < 0 || grid_w < 0) continue;           /* refused, see ORC_MAX_GRID */
         const float count = (float)(grid_h * grid_w);
         for (int c = 0; c < channels; ++c) {
             float *plane = bottom_diff + ((size_t)b * channels + c) * height * width;
@@ -198,7 +240,7 @@ void orc_roi_align_backward(const float *top_diff, const float *rois, int num_ro
                             if (y < -1.0f || y > (float)height || x < -1.0f || x > (float)width) continue;   /* :112-117 */
                             if (y <= 0) y = 0;
                             if (x <= 0) x = 0;
-                            int y_low = (int)y, x_low = (int)x, y_high, x_high;
+                            int y_low = orc_f2i(y), x_low = orc_f2i(x), y_high, x_high;
                             if (y_low >= height - 1) { y_high = y_low = height - 1; y = (float)y_low; } else y_high = y_low + 1;
                             if (x_low >= width - 1) { x_high = x_low = width - 1; x = (float)x_low; } else x_high = x_low + 1;
                             float ly = y - (float)y_low, lx = x - (float)x_low, hy = 1.0f - ly, hx = 1.0f - lx;
@@ -217,7 +259,7 @@ void orc_roi_align_backward(const float *top_diff, const float *rois, int num_ro
 static float orc_dcn_grad_weight(float ah, float aw, int h, int w, int height, int width)
 {
     if (ah <= -1 || ah >= (float)height || aw <= -1 || aw >= (float)width) return 0.f;
-    int hl = (int)floorf(ah), wl = (int)floorf(aw), hh = hl + 1, wh = wl + 1;
+    int hl = orc_f2i(floorf(ah)), wl = orc_f2i(floorf(aw)), hh = hl + 1, wh = wl + 1;
     float weight = 0.f;
     if (h == hl && w == wl) weight = ((float)(h + 1) - ah) * ((float)(w + 1) - aw);
     if (h == hl && w == wh) weight = ((float)(h + 1) - ah) * (aw + 1.0f - (float)w);
@@ -249,6 +291,10 @@ void orc_deform_col2im(const float *col, const float *offset, const float *mask,
                             const float iw = (float)(w_out * stride_w - pad_w + j * dil_w) + off_w;
                             float top = col[index];
                             if (mask) top = top * mask[(((size_t)b * deformable_group + g) * kh * kw + (i * kw + j)) * plane_col + pix];
+                            /* Only a sample inside (-1, height) x (-1, width) has a pixel within one of it -- the window test
+                             * below and orc_dcn_grad_weight both say so -- and testing that first keeps the truncation in range
+                             * (offsets of 1e9 or NaN reach this line). */
+                            if (!(ih > -1 && ih < (float)height && iw > -1 && iw < (float)width)) continue;
                             const int cur_h = (int)ih, cur_w = (int)iw;        /* truncation, :339-340 */
                             for (int dy = -2; dy <= 2; ++dy)
                                 for (int dx = -2; dx <= 2; ++dx) {
@@ -263,7 +309,7 @@ void orc_deform_col2im(const float *col, const float *offset, const float *mask,
 static float orc_dcn_coord_weight(float ah, float aw, int height, int width, const float *im, int bp_dir)
 {
     if (ah <= -1 || ah >= (float)height || aw <= -1 || aw >= (float)width) return 0.f;
-    int hl = (int)floorf(ah), wl = (int)floorf(aw), hh = hl + 1, wh = wl + 1;
+    int hl = orc_f2i(floorf(ah)), wl = orc_f2i(floorf(aw)), hh = hl + 1, wh = wl + 1;
     float weight = 0.f;
     if (bp_dir == 0) {
         if (hl >= 0 && wl >= 0) weight += -1.0f * ((float)(wl + 1) - aw) * im[hl * width + wl];
@@ -478,21 +524,23 @@ int orc_mask_removal(const float *rois, const float *mask_logit, const int64_t *
         const int64_t i = order[ii];
         const int cls = (int)cls_idx[i] - 1;             /* :54 */
         int bx[4];
-        for (int q = 0; q < 4; ++q) bx[q] = (int)rois[i * 4 + q]; /* astype(int32): trunc, :60 */
-        int w = bx[2] - bx[0] + 1, h = bx[3] - bx[1] + 1;
+        for (int q = 0; q < 4; ++q) bx[q] = orc_f2i(rois[i * 4 + q]); /* astype(int32): trunc, :60 */
+        /* numpy int32 arithmetic: wraps for boxes beyond +-2^30 */
+        int w = orc_wrap_add(orc_wrap_sub(bx[2], bx[0]), 1), h = orc_wrap_add(orc_wrap_sub(bx[3], bx[1]), 1);
         if (w < 1) w = 1;
         if (h < 1) h = 1;
-        int x_0 = bx[0] > 0 ? bx[0] : 0, x_1 = bx[2] + 1 < W ? bx[2] + 1 : W;
-        int y_0 = bx[1] > 0 ? bx[1] : 0, y_1 = bx[3] + 1 < H ? bx[3] + 1 : H;
+        const int bx2p = orc_wrap_add(bx[2], 1), bx3p = orc_wrap_add(bx[3], 1);
+        int x_0 = bx[0] > 0 ? bx[0] : 0, x_1 = bx2p < W ? bx2p : W;
+        int y_0 = bx[1] > 0 ? bx[1] : 0, y_1 = bx3p < H ? bx3p : H;
         const float *src = mask_logit + (size_t)i * msize * msize;
         uint8_t *occ = occupancy + (size_t)cls * H * W;
         long mask_sum = 0, overlap = 0;
         /* python slicing mask[(y_0-by):(y_1-by), (x_0-bx):(x_1-bx)] clamps the stop to (h, w) */
         for (int y = y_0; y < y_1; ++y) {
-            int ly = y - bx[1];
+            int ly = orc_wrap_sub(y, bx[1]);
             if (ly < 0 || ly >= h) continue;
             for (int x = x_0; x < x_1; ++x) {
-                int lx = x - bx[0];
+                int lx = orc_wrap_sub(x, bx[0]);
                 if (lx < 0 || lx >= w) continue;
                 if (orc_resize_at(src, msize, w, h, lx, ly) > 0) {
                     ++mask_sum;
@@ -506,10 +554,10 @@ int orc_mask_removal(const float *rois, const float *mask_logit, const int64_t *
         float *plane = mask_energy ? mask_energy + (size_t)k * H * W : NULL;
         if (plane) memset(plane, 0, (size_t)H * W * sizeof(float));
         for (int y = y_0; y < y_1; ++y) {
-            int ly = y - bx[1];
+            int ly = orc_wrap_sub(y, bx[1]);
             if (ly < 0 || ly >= h) continue;
             for (int x = x_0; x < x_1; ++x) {
-                int lx = x - bx[0];
+                int lx = orc_wrap_sub(x, bx[0]);
                 if (lx < 0 || lx >= w) continue;
                 float v = orc_resize_at(src, msize, w, h, lx, ly);
                 if (v > 0) occ[(size_t)y * W + x] += 1;     /* uint8 += , :85 */
@@ -535,10 +583,10 @@ void orc_seg_term(const float *fcn, int S, int H, int W, const float *boxes, con
     memset(seg_inst, 0, (size_t)k * H * W * sizeof(float));
     for (int i = 0; i < k; ++i) {
         if (cls[i] == 0) continue;                          /* :97-98 */
-        long y0 = (long)boxes[i * 4 + 1];                    /* int() truncates */
-        long y1 = (long)(rintf(boxes[i * 4 + 3]) + 1.0f);    /* numpy round = half-even, :100 */
-        long x0 = (long)boxes[i * 4 + 0];
-        long x1 = (long)(rintf(boxes[i * 4 + 2]) + 1.0f);
+        long y0 = orc_f2l(boxes[i * 4 + 1]);                    /* int() truncates */
+        long y1 = orc_f2l(rintf(boxes[i * 4 + 3]) + 1.0f);    /* numpy round = half-even, :100 */
+        long x0 = orc_f2l(boxes[i * 4 + 0]);
+        long x1 = orc_f2l(rintf(boxes[i * 4 + 2]) + 1.0f);
         int ys = orc_py_slice_lo(y0, H), ye = orc_py_slice_lo(y1, H);
         int xs = orc_py_slice_lo(x0, W), xe = orc_py_slice_lo(x1, W);
         const float *src = fcn + (size_t)class_map[cls[i]] * H * W;

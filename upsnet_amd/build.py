@@ -1,6 +1,6 @@
 """Build libupsnet_hip.so (hand-written HIP kernels for gfx950 / MI355X) in-tree.
 
-    python -m upsnet_amd.build [--force]
+    python -m upsnet_amd.build [--force] [--host-sanitize]
 
 hipcc cross-compiles for gfx950 without a GPU. The selection / sampling kernels must reproduce fp32
 decisions bit-for-bit, hence -ffp-contract=off (no FMA contraction).
@@ -23,14 +23,24 @@ SOURCES = ["capi.cpp", "fill.hip", "roi_align.hip", "nms.hip", "deform_conv.hip"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
+# Host-instrumented twin for tools/host_probe.cpp (tests/test_host_probe_cpu.py): the HOST half of every translation unit under
+# AddressSanitizer + UndefinedBehaviorSanitizer, device code as in the default build. It is never loaded into Python and never run
+# on a GPU: the probe calls only entry points that return before any device call. Own file, own objects, own stamp.
+HOST_SANITIZE_FLAGS = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
+                       "-Xarch_host", "-fno-omit-frame-pointer", "-g1"]
+LIB_HOSTSAN = os.path.join(CSRC, "libupsnet_hip_hostsan.so")
+
+
 _COMMENT = re.compile(rb"//[^\n]*|/\*.*?\*/", re.S)
 
 
-def _source_hash():
+def _source_hash(extra_flags=()):
     """sha1 over the compile flags and every source / header the library is built from, comments and whitespace runs removed (mtimes
     are not trusted: a shipped .so and a checked-out source can carry the same timestamp; and a comment edit must neither rebuild the
     library nor orphan the PMC profile that is stamped with this hash, tools/make_pmc_json.py)."""
     h = hashlib.sha1(" ".join(FLAGS + SOURCES).encode())
+    if extra_flags:
+        h.update(" ".join(extra_flags).encode())
     deps = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h")))
     deps.append(os.path.join(INCLUDE, "upsnet_hip.h"))
     for d in deps:
@@ -40,22 +50,25 @@ def _source_hash():
     return h.hexdigest()
 
 
-def _stale():
-    if not os.path.exists(LIB) or not os.path.exists(STAMP):
+def _stale(lib=LIB, extra_flags=()):
+    stamp = lib + ".srchash"
+    if not os.path.exists(lib) or not os.path.exists(stamp):
         return True
-    with open(STAMP) as f:
-        return f.read().strip() != _source_hash()
+    with open(stamp) as f:
+        return f.read().strip() != _source_hash(extra_flags)
 
 
-def build(force=False, verbose=True):
-    if not force and not _stale():
-        return LIB
+def build(force=False, verbose=True, host_sanitize=False):
+    """Build the product library; host_sanitize=True builds libupsnet_hip_hostsan.so (see HOST_SANITIZE_FLAGS) instead."""
+    lib, extra, tag = (LIB_HOSTSAN, HOST_SANITIZE_FLAGS, ".hostsan.o") if host_sanitize else (LIB, [], ".o")
+    if not force and not _stale(lib, extra):
+        return lib
     hipcc = os.environ.get("HIPCC", "hipcc")
     objs = []
     procs = []
     for src in SOURCES:
-        obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
-        cmd = [hipcc] + FLAGS + ["-I" + INCLUDE, "-I" + CSRC, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
+        obj = os.path.join(CSRC, os.path.splitext(src)[0] + tag)
+        cmd = [hipcc] + FLAGS + extra + ["-I" + INCLUDE, "-I" + CSRC, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd)))
@@ -63,14 +76,14 @@ def build(force=False, verbose=True):
     for src, p in procs:
         if p.wait() != 0:
             raise RuntimeError("hipcc failed on %s" % src)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    with open(STAMP, "w") as f:
-        f.write(_source_hash() + "\n")
-    return LIB
+    with open(lib + ".srchash", "w") as f:
+        f.write(_source_hash(extra) + "\n")
+    return lib
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv))
+    print(build(force="--force" in sys.argv, host_sanitize="--host-sanitize" in sys.argv))

@@ -72,6 +72,9 @@ extern "C" int upsnet_roi_align_backward(void *stream, const float *top_diff, fl
 {
     (void)batch_size;
     UPS_REQUIRE(top_diff && rois && bottom_diff, "roi_align_backward: null pointer");
+    UPS_REQUIRE(num_rois >= 0 && channels > 0 && height > 0 && width > 0 && pooled_height > 0 && pooled_width > 0,
+                "roi_align_backward: bad sizes (%d rois, %d x %d x %d map, %d x %d bins)", num_rois, channels, height, width, pooled_height,
+                pooled_width);
     const long n = (long)num_rois * channels * pooled_height * pooled_width;
     if (n == 0) return 0;
     int blocks = (int)((n + 255) / 256);

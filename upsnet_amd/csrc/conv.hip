@@ -681,7 +681,9 @@ int conv_splitk_reduce(hipStream_t st, const float *partial, int ksplit, long m_
 extern "C" size_t upsnet_conv2d_splitk_workspace_bytes(int batch, int height, int width, int Cout, int KH, int KW, int stride, int pad,
                                                        int ksplit)
 {
-    const long Ho = (height + 2 * pad - KH) / stride + 1, Wo = (width + 2 * pad - KW) / stride + 1;
+    if (batch < 1 || height < 1 || width < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0 || ksplit < 1) return 0;
+    const long Ho = ((long)height + 2L * pad - KH) / stride + 1, Wo = ((long)width + 2L * pad - KW) / stride + 1;   // widened first
+    if (Ho <= 0 || Wo <= 0) return 0;
     const long M = (long)batch * Ho * Wo;
     const long m_pad = (M + 127) / 128 * 128;   // (tile-aligned for both split-K instances: 64- and 128-pixel tiles)
     return (size_t)ksplit * m_pad * Cout * sizeof(float);

@@ -50,7 +50,7 @@ __global__ void conv1x1_ksw_pack_kernel(const float *__restrict__ w, int cout, i
 extern "C" size_t upsnet_conv1x1_ksw_packed_weight_floats(int cout, int cin)
 {
     if (cout <= 0 || cin <= 0) return 0;
-    return (size_t)((cout + 16 * KSW_MAXCB - 1) / (16 * KSW_MAXCB)) * (16 * KSW_MAXCB) * (size_t)cin;
+    return (((size_t)cout + 16 * KSW_MAXCB - 1) / (16 * KSW_MAXCB)) * (16 * KSW_MAXCB) * (size_t)cin;
 }
 
 extern "C" int upsnet_conv1x1_ksw_pack_weight(void *stream, const float *weight, int cout, int cin, float *wpack)

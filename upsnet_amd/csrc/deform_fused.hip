@@ -58,7 +58,7 @@ __global__ void dcn_pack_weight_frag_kernel(const float *__restrict__ w, int cou
 extern "C" size_t upsnet_dcn_packed_weight_floats(int cout, int cin, int kh, int kw)
 {
     if (cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) return 0;
-    return (size_t)((cout + DF_BN - 1) / DF_BN) * DF_BN * (size_t)cin * kh * kw;
+    return (((size_t)cout + DF_BN - 1) / DF_BN) * DF_BN * (size_t)cin * kh * kw;
 }
 
 extern "C" int upsnet_dcn_pack_weight(void *stream, const float *weight, int cout, int cin, int kh, int kw, float *wpack)
@@ -473,8 +473,10 @@ extern "C" int upsnet_deform_conv_fused_nhwc(void *stream, int nlev, const float
 extern "C" size_t upsnet_deform_conv_fused_splitk_workspace_bytes(int height, int width, int cout, int kh, int kw, int pad, int stride,
                                                                    int dil, int ksplit)
 {
-    const long Ho = (height + 2 * pad - (dil * (kh - 1) + 1)) / stride + 1, Wo = (width + 2 * pad - (dil * (kw - 1) + 1)) / stride + 1;
-    if (Ho <= 0 || Wo <= 0 || ksplit < 1) return 0;
+    if (height < 1 || width < 1 || cout < 1 || kh < 1 || kw < 1 || pad < 0 || stride < 1 || dil < 1 || ksplit < 1) return 0;
+    const long Ho = ((long)height + 2L * pad - ((long)dil * (kh - 1) + 1)) / stride + 1;   // widened first: every int argument fits
+    const long Wo = ((long)width + 2L * pad - ((long)dil * (kw - 1) + 1)) / stride + 1;
+    if (Ho <= 0 || Wo <= 0) return 0;
     return (size_t)ksplit * Ho * Wo * cout * sizeof(float);
 }
 

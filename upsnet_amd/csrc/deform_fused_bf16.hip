@@ -48,7 +48,7 @@ __global__ void dcn_pack_weight_bf16_kernel(const float *__restrict__ w, int cou
 extern "C" size_t upsnet_dcn_packed_weight_bf16_elems(int cout, int cin, int kh, int kw)
 {
     if (cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0) return 0;
-    return (size_t)((cout + DFB_BN - 1) / DFB_BN) * DFB_BN * (size_t)cin * kh * kw;
+    return (((size_t)cout + DFB_BN - 1) / DFB_BN) * DFB_BN * (size_t)cin * kh * kw;
 }
 
 extern "C" int upsnet_dcn_pack_weight_bf16(void *stream, const float *weight, int cout, int cin, int kh, int kw, void *wpack)

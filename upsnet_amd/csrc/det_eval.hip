@@ -317,7 +317,7 @@ struct BndTile { int d, TX, WS, grid_x; size_t lds; };
 // the tile of bnd_erode_kernel for dilation d on an H x W image; false when the window does not fit the LDS budget
 static bool bnd_tile(int H, int W, int d, BndTile *t)
 {
-    const int nw = (H + 63) / 64;
+    const int nw = (int)(((long)H + 63) / 64);
     if (2L * d + 1 > H || 2L * d + 1 > W) {   // every window leaves the image: nothing survives
         t->d = -1; t->WS = std::min(nw, 16); t->TX = std::min(W, BND_LDS_WORDS / t->WS); t->lds = 0;
     } else {
@@ -327,7 +327,9 @@ static bool bnd_tile(int H, int W, int d, BndTile *t)
         t->TX = std::min(std::min(W, 256), BND_LDS_WORDS / t->WS - 2 * d);
         t->lds = sizeof(de_u64) * (size_t)(t->TX + 2 * d) * t->WS;
     }
-    t->grid_x = ((W + t->TX - 1) / t->TX) * ((nw + t->WS - 1) / t->WS);
+    const long grid = (((long)W + t->TX - 1) / t->TX) * (((long)nw + t->WS - 1) / t->WS);
+    if (grid > 0x7fffffffL) return false;
+    t->grid_x = (int)grid;
     return true;
 }
 
@@ -514,16 +516,16 @@ static inline size_t de_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static DetAccLayout det_acc_layout(void *ws, long N, int K, size_t *bytes)
 {
     DetAccLayout L;
-    char *p = (char *)ws;
     size_t o = 0;
-    L.cnt = (int *)(p + o); o += de_align(sizeof(int) * K * DE_M);
-    L.off = (int *)(p + o); o += de_align(sizeof(int) * K * DE_M);
-    L.fill = (int *)(p + o); o += de_align(sizeof(int) * K);
-    L.total = (int *)(p + o); o += de_align(sizeof(int));
-    L.bscore = (double *)(p + o); o += de_align(sizeof(double) * N);
-    L.bucket = (int *)(p + o); o += de_align(sizeof(int) * N);
-    L.bkey = (int *)(p + o); o += de_align(sizeof(int) * N);
-    L.sorted = (int *)(p + o); o += de_align(sizeof(int) * N * DE_M);
+    const auto at = [ws](size_t off) { return ws ? (char *)ws + off : nullptr; };   // (a size-only call passes no workspace)
+    L.cnt = (int *)at(o); o += de_align(sizeof(int) * K * DE_M);
+    L.off = (int *)at(o); o += de_align(sizeof(int) * K * DE_M);
+    L.fill = (int *)at(o); o += de_align(sizeof(int) * K);
+    L.total = (int *)at(o); o += de_align(sizeof(int));
+    L.bscore = (double *)at(o); o += de_align(sizeof(double) * N);
+    L.bucket = (int *)at(o); o += de_align(sizeof(int) * N);
+    L.bkey = (int *)at(o); o += de_align(sizeof(int) * N);
+    L.sorted = (int *)at(o); o += de_align(sizeof(int) * N * DE_M);
     if (bytes) *bytes = o;
     return L;
 }
@@ -713,12 +715,12 @@ det_curve_kernel(const int K, const int64_t *__restrict__ npig, const int *__res
 static size_t det_img_workspace_bytes(int num_det, int num_rows, int num_gt, int height, int width, int segm)
 {
     if (num_det < 0 || num_rows < 1 || num_gt < 0 || height < 1 || width < 1) return 0;
-    const size_t plane = (size_t)width * ((height + 63) / 64) * 8;
+    const size_t plane = (size_t)width * (((size_t)height + 63) / 64) * 8;
     const size_t nplanes = std::min((size_t)num_det, (size_t)DE_MAXDET * num_rows);   // evaluated dets only
-    size_t b = de_align(sizeof(int) * ((size_t)num_rows * (DE_MAXDET + 1) + 1)) + de_align(sizeof(int) * (num_det + 1))
+    size_t b = de_align(sizeof(int) * ((size_t)num_rows * (DE_MAXDET + 1) + 1)) + de_align(sizeof(int) * ((size_t)num_det + 1))
              + de_align(sizeof(double) * DE_MAXDET * (size_t)num_gt + 8) + de_align((size_t)DE_A * DE_T * num_gt + 1);
-    if (segm) b += de_align(sizeof(int) * 6 * (size_t)(num_det + 1)) + plane * nplanes + de_align(sizeof(int) * (num_gt + 1)) + plane * num_gt;
-    if (segm == 2) b += de_align(sizeof(int) * (size_t)(num_det + 1)) + plane * nplanes + de_align(sizeof(int) * 5 * (size_t)(num_gt + 1)) + plane * num_gt;
+    if (segm) b += de_align(sizeof(int) * 6 * ((size_t)num_det + 1)) + plane * nplanes + de_align(sizeof(int) * ((size_t)num_gt + 1)) + plane * num_gt;
+    if (segm == 2) b += de_align(sizeof(int) * ((size_t)num_det + 1)) + plane * nplanes + de_align(sizeof(int) * 5 * ((size_t)num_gt + 1)) + plane * num_gt;
     return b;
 }
 
@@ -893,8 +895,8 @@ extern "C" int upsnet_boundary_dilation_fits(int height, int width, int dilation
 extern "C" size_t upsnet_boundary_masks_workspace_bytes(int num_masks, int height, int width)
 {
     if (num_masks < 0 || height < 1 || width < 1) return 0;
-    const size_t plane = (size_t)width * ((height + 63) / 64) * 8;
-    return 2 * plane * num_masks + de_align(sizeof(int) * 5 * (size_t)(num_masks + 1));
+    const size_t plane = (size_t)width * (((size_t)height + 63) / 64) * 8;
+    return 2 * plane * num_masks + de_align(sizeof(int) * 5 * ((size_t)num_masks + 1));
 }
 
 extern "C" int upsnet_boundary_masks(void *stream, int dilation, int height, int width, int num_masks, const unsigned char *masks_u8,

@@ -200,9 +200,11 @@ static void mroi_dims(int N, int C, int agn, int *P, int *nmax)
 
 extern "C" int upsnet_mask_roi_capacity(int N, int C, int agn)
 {
+    if (C < 2) return 0;                          // no foreground class: no capacity (never a negative one)
     int P, nmax;
     mroi_dims(N, C, agn, &P, &nmax);
-    return P * nmax;
+    const long cap = (long)P * nmax;
+    return cap > 0x7fffffffL ? 0 : (int)cap;     // beyond an int: no capacity (the launcher's row indices are ints)
 }
 
 struct MroiPlan { size_t boxes, scores, src, cls, counts, keep, keepcnt, status, flat, nms, total; };
@@ -225,6 +227,7 @@ static MroiPlan mroi_plan(int P, int nmax)
 
 extern "C" size_t upsnet_mask_roi_workspace_bytes(int N, int C, int agn)
 {
+    if (N < 1 || C < 2) return 256;                // (what upsnet_mask_roi_ex refuses: no negative problem count reaches the plan)
     int P, nmax;
     mroi_dims(N, C, agn, &P, &nmax);
     return mroi_plan(P, nmax).total;

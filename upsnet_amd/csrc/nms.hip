@@ -377,7 +377,7 @@ static NmsWs nms_carve(void *ws, int P, int nmax)
 extern "C" size_t upsnet_nms_workspace_bytes(int P, int nmax)
 {
     if (P <= 0 || nmax <= 0) return 256;
-    size_t CB = (nmax + 63) / 64;
+    size_t CB = ((size_t)nmax + 63) / 64;
     return align256((size_t)P * nmax * sizeof(float4)) + align256((size_t)P * nmax * sizeof(int)) +
            align256((size_t)P * nmax * sizeof(u64)) + align256((size_t)P * nmax * CB * sizeof(u64)) + 256;
 }

@@ -294,7 +294,7 @@ static MrPlan mr_plan(int m, int ncls, int H, int W)
     MrPlan p;
     if (m < 1) m = 1;
     if (ncls < 1) ncls = 1;
-    p.WW = (W + 63) / 64;
+    p.WW = (int)(((long)W + 63) / 64);
     size_t o = 0;
     p.occ = o; o += al256((size_t)ncls * H * p.WW * 8);
     p.bits = o; o += al256((size_t)m * H * p.WW * 8);

@@ -327,16 +327,16 @@ struct PrLayout {
 static PrLayout pr_layout(void *ws, long TV, long N, size_t *bytes)
 {
     PrLayout L;
-    char *p = (char *)ws;
     size_t o = 0;
+    const auto at = [ws](size_t off) { return ws ? (char *)ws + off : nullptr; };   // (a size-only call passes no workspace)
     const long big = TV > N ? TV : N;
-    L.xy = (int2 *)(p + o); o += pr_align(sizeof(int2) * TV);
-    L.cnt = (int *)(p + o); o += pr_align(sizeof(int) * TV);
-    L.eoff = (int *)(p + o); o += pr_align(sizeof(int) * (TV + 1));
-    L.part = (int *)(p + o); o += pr_align(sizeof(int) * ((big + PR_TILE) / PR_TILE + 1));
-    L.flag = (int *)(p + o); o += pr_align(sizeof(int) * N);
-    L.rank = (int *)(p + o); o += pr_align(sizeof(int) * (N + 1));
-    L.keys = (pr_u64 *)(p + o); o += pr_align(sizeof(pr_u64) * pr_pow2(N));
+    L.xy = (int2 *)at(o); o += pr_align(sizeof(int2) * TV);
+    L.cnt = (int *)at(o); o += pr_align(sizeof(int) * TV);
+    L.eoff = (int *)at(o); o += pr_align(sizeof(int) * (TV + 1));
+    L.part = (int *)at(o); o += pr_align(sizeof(int) * ((big + PR_TILE) / PR_TILE + 1));
+    L.flag = (int *)at(o); o += pr_align(sizeof(int) * N);
+    L.rank = (int *)at(o); o += pr_align(sizeof(int) * (N + 1));
+    L.keys = (pr_u64 *)at(o); o += pr_align(sizeof(pr_u64) * pr_pow2(N));
     if (bytes) *bytes = o;
     return L;
 }

@@ -534,7 +534,9 @@ extern "C" size_t upsnet_proposal_workspace_bytes(int nlev, const int *heights, 
                                                   int pre_nms_top_n, int post_nms_top_n)
 {
     (void)post_nms_top_n;
-    if (nlev <= 0 || nlev > PROP_MAXLEV || !heights || !widths) return 0;
+    if (nlev <= 0 || nlev > PROP_MAXLEV || !heights || !widths || num_anchors < 1 || num_anchors > 4 || pre_nms_top_n < 0) return 0;
+    for (int l = 0; l < nlev; ++l)     // the launchers index a level's anchors with 32 bits: more is refused here too, before any product
+        if (heights[l] < 0 || widths[l] < 0 || (long)heights[l] * widths[l] > ((1L << 31) - 1) / num_anchors) return 0;
     return prop_plan(nlev, heights, widths, num_anchors, pre_nms_top_n).total;
 }
 
