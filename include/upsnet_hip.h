@@ -4,6 +4,12 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless the name ends in _host;
+ *   - Alignment: every device pointer is 16-byte aligned. The kernels use 128-bit loads and stores, 64-bit atomics on parts carved from
+ *     byte workspaces at 16-byte steps, and 4-byte fills; none of the entry points checks the address (the Python binding does, before
+ *     the call: upsnet_amd/_lib.py). Exempt, element alignment suffices: mask_logit of upsnet_mask_logit_gather; the maps behind
+ *     cls_prob[] and bbox_pred[] of upsnet_pyramid_proposals_strided / _strided_ordered / _joint_strided; sseg and pano of
+ *     upsnet_restore_label_maps; src of upsnet_restore_plane_u8. Their kernels read one element per access at a caller-given stride.
+ *     Host pointers only feed copies or launch arithmetic and are outside the rule;
  *   - `stream` is a hipStream_t passed as void* (the caller's current stream; NULL = default stream);
  *   - the caller allocates every output and every workspace (the reference does the same:
  *     functions/deform_conv.py:44-45, functions/roialign.py:37); the library never allocates

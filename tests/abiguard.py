@@ -22,10 +22,11 @@ Rules for a non-NULL pointer argument (``stream`` and ctypes host arrays -- int_
   type      float -> float32, double -> float64, int / unsigned -> int32, int64_t / long -> int64, (unsigned) char -> uint8 / int8 /
             bool, unsigned short and the 16-bit typedefs -> bfloat16 / float16 / int16 / uint16, void -> anything;
   density   the tensor is contiguous in some memory format, or (symbol, parameter) is in STRIDED with the stride parameter named;
-  device    a CUDA tensor lives on torch.cuda.current_device() (``stream()`` is that device's stream).
+  device    a CUDA tensor lives on torch.cuda.current_device() (``stream()`` is that device's stream);
+  alignment its address is a multiple of 16, or (symbol, parameter) is in UNALIGNED: the parameters whose kernels were read and found
+            to access them at element width only. Host parameters (``*_host``, HOST) are outside this rule.
 
-What the guard cannot know is how many bytes an entry point reads (the guard bands of tests/memguard.py cover that) and whether an
-address is aligned enough for a kernel's 128-bit accesses.
+What the guard cannot know is how many bytes an entry point reads (the guard bands of tests/memguard.py cover that).
 """
 import ast
 import collections
@@ -305,6 +306,25 @@ STRIDED = {
     ('upsnet_restore_plane_u8', 'src'): "rows of the source plane at src_stride bytes (a crop of a padded plane)",
 }
 
+# (symbol, parameter) pairs that may be given an address that is only element-aligned (a view that starts inside an allocation), each
+# with the reading that allows it: in every kernel the entry point launches, every access through the pointer is one element wide, and
+# no pointer derived from it is reinterpreted wider or used for an atomic. Everything else -- every output, workspace, accumulator and
+# counter in particular -- is held to ALIGN bytes without a reading. None of the HOST / *_host parameters is read by a kernel directly:
+# each feeds a copy or host-side launch arithmetic.
+ALIGN = 16
+UNALIGNED = {
+    ('upsnet_mask_logit_gather', 'mask_logit'): "detect.hip mask_logit_gather_kernel: one float load sp[e * s_e] per output element, nothing wider",
+    ('upsnet_pyramid_proposals_strided', 'cls_prob'): "forwards to _strided_ordered: proposal.hip reads s[a * cs + pix * ps], one float per key",
+    ('upsnet_pyramid_proposals_strided', 'bbox_pred'): "forwards to _strided_ordered: proposal.hip reads d[0], d[bcs], d[2 bcs], d[3 bcs] as single floats",
+    ('upsnet_pyramid_proposals_strided_ordered', 'cls_prob'): "proposal.hip key kernels read s[a * cs + pix * ps], one float per key, nothing wider",
+    ('upsnet_pyramid_proposals_strided_ordered', 'bbox_pred'): "proposal.hip decode reads d[0], d[bcs], d[2 bcs], d[3 bcs] as single floats at a run-time stride",
+    ('upsnet_pyramid_proposals_joint_strided', 'cls_prob'): "proposal.hip joint key kernel reads s[a * cs + pix * ps], one float per key, nothing wider",
+    ('upsnet_pyramid_proposals_joint_strided', 'bbox_pred'): "proposal.hip decode reads d[0], d[bcs], d[2 bcs], d[3 bcs] as single floats at a run-time stride",
+    ('upsnet_restore_label_maps', 'sseg'): "restore.hip rs_gather_chunk: one int64 load row[sx] per output byte; the 16-byte store is on the output",
+    ('upsnet_restore_label_maps', 'pano'): "restore.hip rs_gather_chunk: one int64 load row[sx] per output byte; the 16-byte store is on the output",
+    ('upsnet_restore_plane_u8', 'src'): "restore.hip rs_gather_chunk: one byte load row[sx] per output byte; the 16-byte store is on the output",
+}
+
 # pointer parameters that take HOST memory although their name does not end in _host (the header's convention for host pointers):
 # numpy buffers that the entry point reads before it returns. The origin rule does not apply to them.
 HOST = {
@@ -319,7 +339,8 @@ Record = collections.namedtuple('Record', 'ref base dtype shape stride device si
 def _site():
     f = sys._getframe(1)
     here = os.path.abspath(__file__)
-    while f is not None and os.path.abspath(f.f_code.co_filename) == here:
+    # (the binding's own frames are skipped too: ptr_unaligned / ptr_array_unaligned call ptr on the wrapper's behalf)
+    while f is not None and (os.path.abspath(f.f_code.co_filename) == here or os.path.basename(f.f_code.co_filename) == '_lib.py'):
         f = f.f_back
     if f is None:
         return '?'
@@ -346,9 +367,10 @@ def _current_device():
 
 
 class Guard:
-    def __init__(self, header, strided):
+    def __init__(self, header, strided, unaligned=None):
         self.header = header
         self.strided = strided
+        self.unaligned = UNALIGNED if unaligned is None else unaligned
         self.registry = {}                          # address -> Record (the latest ptr() of that address)
         self.calls = collections.Counter()          # symbol -> calls that reached the library
         self.violations = []
@@ -356,8 +378,8 @@ class Guard:
 
     # ---- the replacements of _lib.ptr / ptr_array / addr
     def make_ptr(self, real):
-        def ptr(t):
-            p = real(t)
+        def ptr(t, unaligned=False):
+            p = real(t, unaligned) if unaligned else real(t)       # (a tree from before the rule has no such argument, and no caller of it)
             if t is not None:
                 rec = _record(t, _site())
                 self.registry[rec.address] = rec
@@ -366,9 +388,9 @@ class Guard:
         return ptr
 
     def make_ptr_array(self, real):
-        def ptr_array(tensors):
+        def ptr_array(tensors, unaligned=False):
             tensors = list(tensors)
-            arr = real(tensors)
+            arr = real(tensors, unaligned) if unaligned else real(tensors)
             site = _site()
             recs = [None if t is None else _record(t, site) for t in tensors]
             for r in recs:
@@ -379,8 +401,8 @@ class Guard:
         return ptr_array
 
     def make_addr(self, real):
-        def addr(t):
-            a = real(t)
+        def addr(t, unaligned=False):
+            a = real(t, unaligned) if unaligned else real(t)
             rec = _record(t, _site())
             self.registry[rec.address] = rec
             return a
@@ -406,6 +428,10 @@ class Guard:
         if rec.device.type == 'cuda' and rec.device.index != _current_device():
             self._fail(sym, pname, rec.site, 'device', "the tensor is on %s, the current device (whose stream the call gets) is cuda:%d"
                        % (rec.device, _current_device()))
+        if rec.address % ALIGN and (sym, key or pname) not in self.unaligned:
+            self._fail(sym, pname, rec.site, 'alignment', "0x%x is %d bytes past a multiple of %d (%s %s, a view that starts inside an "
+                       "allocation?), and the pair is not in abiguard.UNALIGNED" % (rec.address, rec.address % ALIGN, ALIGN,
+                                                                                   str(rec.dtype).replace('torch.', ''), rec.shape))
 
     def check_call(self, sym, args):
         ret, params = self.header[sym]
@@ -426,12 +452,12 @@ class Guard:
                         if v:
                             self._by_address(sym, '%s[%d]' % (pname, i), elem, int(v), pname)
                 continue                                            # (int_array, float_array and their like: host arrays of scalars)
+            if pname.endswith('_host') or (sym, pname) in HOST:
+                continue                                            # (host memory by the header's convention / by the HOST table)
             rec = getattr(a, '_abiguard', None)
             if rec is not None:
                 self._check_record(sym, pname, elem, rec)
                 continue
-            if pname.endswith('_host') or (sym, pname) in HOST:
-                continue                                            # (host memory by the header's convention / by the HOST table)
             value = a.value if isinstance(a, ctypes.c_void_p) else a
             if isinstance(value, int):
                 if value:
@@ -473,11 +499,11 @@ class _LibProxy:
 
 
 @contextlib.contextmanager
-def guard(library=None, strided=None):
+def guard(library=None, strided=None, unaligned=None):
     """Patch ptr / ptr_array / addr and lib in upsnet_amd._lib and in every module that imported them by name; yields the Guard.
     `library`: an object standing in for the loaded library (CPU tests); default: the real one, loaded on first use."""
     lib_mod = importlib.import_module(PACKAGE + '._lib')
-    g = Guard(header_abi(), STRIDED if strided is None else strided)
+    g = Guard(header_abi(), STRIDED if strided is None else strided, unaligned)
     found = holders()
     mods = {m: importlib.import_module(m) for m in found}
     makers = {'ptr': g.make_ptr, 'ptr_array': g.make_ptr_array, 'addr': g.make_addr}

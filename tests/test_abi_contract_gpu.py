@@ -3,14 +3,18 @@
 a. Canonical sweep. Every case of tests/test_poisoned_memory_gpu.py (CASES) and of EXTRA_CASES below -- the wrappers that call the
    library but allocate nothing, which that table does not list -- runs its existing test body once under abiguard.guard(), on
    ordinary memory: the body's own reference comparison stays in force, no pointer argument may break a rule, and every entry point the
-   case lists must have been called. One more case runs an eager forward of each model preset.
+   case lists must have been called. Two more cases run an eager forward of each model preset, and one an eager forward at the
+   smallest size of tests/size_population.py at which a pyramid level has an odd pixel count. The guard's alignment rule holds every
+   pointer of these runs to 16 bytes, so they check every carve-out the package makes inside its own buffers.
 
 b. Form sweep. For each wrapper (a module-level function whose body calls an upsnet_* symbol with a pointer parameter) the arguments
    of its first call in its case are captured (tensors cloned) and the call is replayed under the guard with ONE tensor argument at a
    time replaced by a variant of equal values:
      strided  a view that is contiguous in no memory format (the innermost dimension of the physical layout taken ::2 out of a buffer
               twice as long); tensors of at most one element have none;
-     dtype    float32 -> float64, int32 -> int64, int64 -> int32, bool -> uint8; other dtypes have none.
+     dtype    float32 -> float64, int32 -> int64, int64 -> int32, bool -> uint8; other dtypes have none;
+     offset   the same sizes and strides one element into a buffer one element longer, so that the address is a multiple of the element
+              size and not of 16; only a tensor without elements has none.
    Every argument is cloned afresh for each replay. A replay must end as
      same     the returned tensors (their defined region) and every tensor argument after the call (workspaces apart: scratch) are
               bitwise what the canonical replay gave, and no rule was broken, or
@@ -18,8 +22,9 @@ b. Form sweep. For each wrapper (a module-level function whose body calls an ups
               (a size query such as upsnet_*_workspace_bytes takes no pointer and launches nothing: many wrappers need its answer
               to judge the workspace they were given, so it does not count).
    An AbiViolation, a different result or an exception after a launch fails the test: the wrapper is to be fixed.
-   The guard raises before the library is entered, so no variant reaches a kernel mistyped, dangling or mis-strided; variants change
-   dtype and strides only, never a value and never an alignment below the allocator's.
+   The guard raises before the library is entered, so no variant reaches a kernel mistyped, dangling, mis-strided or off alignment
+   (abiguard.UNALIGNED lists the few parameters whose kernels were read and found to access them at element width only: their offset
+   variant does reach the kernel, and must come out `same`); variants never change a value.
 
 c. A form that a wrapper's docstring promises must come out `same` (PROMISED). tools/abi_forms.py writes the outcome table of this
    sweep for two trees side by side (profiles/abi_forms.txt): no row may go from same to refused.
@@ -121,6 +126,26 @@ PROMISED = {
     ('ops.pan_boundary_map', 'pred_2ch', 'strided'): "A non-contiguous map is copied",
     ('ops.pan_boundary_map', 'gt_rgb', 'strided'): "A non-contiguous map is copied",
     ('ops.mask_logit_gather', 'mask_logit', 'channels_last'): "any dense layout (NCHW or channels_last)",
+    ('ops.mask_logit_gather', 'mask_logit', 'offset'): "it may start anywhere in an allocation (element-aligned)",
+    ('ops.pyramid_proposals', 'cls_probs', 'offset'): "a channel slice of a wider map is read in place, wherever it starts",
+    ('ops.pyramid_proposals', 'bbox_preds', 'offset'): "a channel slice of a wider map is read in place, wherever it starts",
+    ('ops.restore_label_maps', 'sseg', 'offset'): "a crop may start at any element of the padded map",
+    ('ops.restore_label_maps', 'pano', 'offset'): "a crop may start at any element of the padded map",
+    ('ops.restore_plane_u8', 'plane', 'offset'): "a crop may start at any byte of the padded plane",
+}
+
+# abiguard.UNALIGNED parameter -> the wrapper argument that reaches it, whose `offset` row above is the run that confirms the reading
+UNALIGNED_SLOT = {
+    ('upsnet_mask_logit_gather', 'mask_logit'): ('ops.mask_logit_gather', 'mask_logit'),
+    ('upsnet_pyramid_proposals_strided', 'cls_prob'): ('ops.pyramid_proposals', 'cls_probs'),         # (forwards to _strided_ordered,
+    ('upsnet_pyramid_proposals_strided', 'bbox_pred'): ('ops.pyramid_proposals', 'bbox_preds'),       #  which the wrapper calls)
+    ('upsnet_pyramid_proposals_strided_ordered', 'cls_prob'): ('ops.pyramid_proposals', 'cls_probs'),
+    ('upsnet_pyramid_proposals_strided_ordered', 'bbox_pred'): ('ops.pyramid_proposals', 'bbox_preds'),
+    ('upsnet_pyramid_proposals_joint_strided', 'cls_prob'): ('ops.pyramid_proposals', 'cls_probs'),
+    ('upsnet_pyramid_proposals_joint_strided', 'bbox_pred'): ('ops.pyramid_proposals', 'bbox_preds'),
+    ('upsnet_restore_label_maps', 'sseg'): ('ops.restore_label_maps', 'sseg'),
+    ('upsnet_restore_label_maps', 'pano'): ('ops.restore_label_maps', 'pano'),
+    ('upsnet_restore_plane_u8', 'src'): ('ops.restore_plane_u8', 'plane'),
 }
 
 _MODULES = {}
@@ -205,14 +230,27 @@ def test_canonical_forms_cross_the_abi_clean(case):
     assert set(calls) == set(case.entries), "entry points listed but never called: %s" % sorted(set(case.entries) - set(calls))
 
 
-@pytest.mark.parametrize('preset', ['CITYSCAPES_R50', 'COCO_R101_DCN'])
-def test_eager_forward_crosses_the_abi_clean(preset):
+def odd_level_size():
+    """The smallest padded size of tests/size_population.py at which some pyramid level (strides 4 .. 64) has an odd number of pixels:
+    a map of 15, 18 or 27 channels at that level then ends off 16 bytes, and whatever is carved behind it starts there unless padded."""
+    import size_population
+    pairs = size_population.one_per_padded(size_population.coco_padded_sizes()) + size_population.cityscapes_sizes()
+    odd = [p for _, p in pairs if any((-(-p[0] // s)) * (-(-p[1] // s)) % 2 for s in (4, 8, 16, 32, 64))]
+    return min(odd, key=lambda p: (p[0] * p[1], p))
+
+
+@pytest.mark.parametrize('preset,size', [('CITYSCAPES_R50', (256, 512)), ('COCO_R101_DCN', (256, 512)), ('COCO_R101_DCN', 'odd')],
+                         ids=['CITYSCAPES_R50', 'COCO_R101_DCN', 'COCO_R101_DCN-odd-level'])
+def test_eager_forward_crosses_the_abi_clean(preset, size):
+    """'odd': odd_level_size(), 800 x 800 with 25 x 25 and 13 x 13 levels, on the preset with 15-channel RPN heads and 18 / 27-channel
+    offset maps (padded blobs are multiples of 32, so the levels down to stride 16 are always even)."""
     cfg = importlib.import_module('upsnet_amd.config.config')
+    height, width = odd_level_size() if size == 'odd' else size
     with sweep._saved_config():
         cfg.update_config_dict(getattr(cfg, preset))
         from upsnet_amd.synthetic import build_model, make_image
         model = build_model()
-        data = make_image(256, 512, seed=3, device='cuda')
+        data = make_image(height, width, seed=3, device='cuda')
         model.use_graph = False
         model._graphs.clear()
         with torch.no_grad(), abiguard.guard() as g:
@@ -264,6 +302,23 @@ def strided_variant(t):
     return view
 
 
+def offset_variant(t):
+    """Equal values, sizes and strides (so memory format too) and the attached attributes, one element into a buffer one element longer:
+    the address is a multiple of the element size and not of 16. None only where the tensor has no elements."""
+    if t.numel() == 0:
+        return None
+    extent = 1 + sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+    buf = torch.empty((extent + 1,), dtype=t.dtype, device=t.device)
+    if t.is_pinned():
+        buf = buf.pin_memory()
+    assert buf.data_ptr() % 16 == 0 and t.element_size() < 16
+    buf[1:].copy_(t.as_strided((extent,), (1,)))       # (the whole span t's strides reach, so an expanded or gapped view copies too)
+    view = buf.as_strided(tuple(t.shape), tuple(t.stride()), 1)
+    assert view.data_ptr() % 16 != 0 and view.shape == t.shape and view.stride() == t.stride()
+    view.__dict__.update(t.__dict__)
+    return view
+
+
 def dtype_variant(t):
     if t.dtype not in DTYPE_VARIANT:
         return None
@@ -288,7 +343,7 @@ def channels_last_variant(t):
     return t.contiguous(memory_format=torch.channels_last)
 
 
-VARIANTS = (('strided', strided_variant), ('dtype', dtype_variant))
+VARIANTS = (('strided', strided_variant), ('dtype', dtype_variant), ('offset', offset_variant))
 PROMISED_VARIANTS = {'rows': rows_variant, 'host': lambda t: t.cpu() if t.is_cuda else None, 'channels_last': channels_last_variant}
 
 

@@ -1,5 +1,6 @@
 """CPU: the three copies of every C-ABI signature agree (include/upsnet_hip.h, the extern "C" definitions in upsnet_amd/csrc, the
-argtypes rows of upsnet_amd/_lib.py); tests/abiguard.py detects what it claims, on a stub library and host tensors; the guard patches
+argtypes rows of upsnet_amd/_lib.py); tests/abiguard.py detects what it claims, on a stub library and host tensors (the alignment rule
+and its UNALIGNED table included, with the binding's normalisers and refusals and the sweep's offset variant); the guard patches
 every module that holds ptr / ptr_array / lib; no address leaves a tensor outside _lib.py; and every function of the package that hands a
 pointer to the library is an entry of a case of tests/test_abi_contract_gpu.py (or excluded with a reason)."""
 import ast
@@ -277,6 +278,168 @@ def test_device_rule(monkeypatch):
     assert g.launches() == 1
 
 
+def test_alignment_rule_and_the_unaligned_table():
+    """Host tensors stand in for device ones: the rule is a remainder of the recorded address. The binding's own refusal (_lib.ptr) is
+    opted out of here, so that the guard's rule is the one under test; the binding's is tested below."""
+    from upsnet_amd import _lib
+    logits, row, cls, out = _tensors()
+    far = lambda t: _lib.ptr(t, unaligned=True)       # noqa: E731
+    off_row = torch.zeros(6, dtype=torch.int32)[1:]
+    off_cls = torch.zeros(6, dtype=torch.int64)[1:]
+    off_out = torch.zeros(21)[1:].view(5, 1, 2, 2)
+    off_logits = torch.zeros(49)[1:].view(3, 4, 2, 2)
+    assert all(t.data_ptr() % 16 for t in (off_row, off_cls, off_out, off_logits)) and row.data_ptr() % 16 == 0
+    msg = _refused(lambda: _gather(_lib.lib, far, logits, off_row, cls, out), 'alignment', 'upsnet_mask_logit_gather(row)', '4 bytes past')
+    assert 'int32' in msg and 'UNALIGNED' in msg
+    _refused(lambda: _gather(_lib.lib, far, logits, row, off_cls, out), 'alignment', 'upsnet_mask_logit_gather(cls)', '8 bytes past')
+    _refused(lambda: _gather(_lib.lib, far, logits, row, cls, off_out), 'alignment', 'upsnet_mask_logit_gather(out)')
+    stub = Stub()
+    with abiguard.guard(library=stub) as g:
+        _gather(_lib.lib, far, logits, row, cls, out)                 # aligned: passes
+        _gather(_lib.lib, far, off_logits, row, cls, out)             # listed in UNALIGNED: passes
+        _gather(_lib.lib, far, logits, torch.zeros(9, dtype=torch.int32)[4:], cls, out)       # 16 bytes into a buffer: aligned
+    assert g.launches() == 3 and not g.violations
+    with abiguard.guard(library=Stub(), unaligned={}) as g:
+        with pytest.raises(abiguard.AbiViolation, match='alignment'):
+            _gather(_lib.lib, far, off_logits, row, cls, out)
+    # every element of a ptr_array, named with its index, and a NULL element passes
+    parts = [logits, off_logits]
+    msg = _refused(lambda: _lib.lib().upsnet_fcn_score_combine(None, 2, _lib.ptr_array(parts, unaligned=True), 4, 2, 2, None, _lib.ptr(out)),
+                   'alignment', 'upsnet_fcn_score_combine(part[1])')
+    with abiguard.guard(library=Stub()) as g:
+        _lib.lib().upsnet_fcn_score_combine(None, 2, _lib.ptr_array([logits, None]), 4, 2, 2, None, _lib.ptr(out))
+    assert g.launches() == 1
+    # ... and of a ptr_array of an UNALIGNED parameter: the key is the parameter, not the element
+    h = abiguard.header_abi()
+    sym = 'upsnet_pyramid_proposals_joint_strided'
+    args = [None] * len(h[sym][1])
+    names = [n for n, _ in h[sym][1]]
+    with abiguard.guard(library=Stub()) as g:
+        args[names.index('cls_prob')] = _lib.ptr_array([off_logits, logits], unaligned=True)
+        getattr(_lib.lib(), sym)(*args)
+    assert g.launches() == 1 and not g.violations
+    # an address recorded through addr(): a table of bare addresses where the header wants an array of pointers
+    feats = [torch.zeros(17)[1:].view(1, 2, 2, 4)] + [torch.zeros(1, 2, 2, 4) for _ in range(3)]
+    rois, out4 = torch.zeros(1, 5), torch.zeros(1, 7, 7, 4)
+    four = _lib.int_array([2] * 4)
+
+    def by_address():
+        arr = (ctypes.c_void_p * 4)(*[_lib.addr(f, unaligned=True) for f in feats])
+        _lib.lib().upsnet_fpn_roi_align_forward(None, arr, four, four, _lib.float_array([1.] * 4), 4, _lib.ptr(rois), 1, None, 7, 7, 2,
+                                                _lib.ptr(out4), None)
+    _refused(by_address, 'alignment', 'upsnet_fpn_roi_align_forward(feat_nhwc[0])')
+
+
+def test_the_unaligned_table_is_well_formed():
+    import test_abi_contract_gpu as contract
+    h = abiguard.header_abi()
+    _, callers, _, _ = abiguard.scan_package()
+    calls = {m.rsplit('.', 1)[-1] + '.' + q: syms for m, fs in callers.items() for q, syms in fs.items()}
+    assert abiguard.ALIGN == 16 and abiguard.UNALIGNED
+    assert set(contract.UNALIGNED_SLOT) == set(abiguard.UNALIGNED)
+    for (sym, pname), why in abiguard.UNALIGNED.items():
+        assert sym in h, sym
+        params = dict(h[sym][1])
+        assert pname in params and params[pname].endswith('*') and pname != 'stream', (sym, pname)
+        assert 'workspace' not in pname and not pname.endswith('_host') and (sym, pname) not in abiguard.HOST, (sym, pname)
+        assert len(why) > 40 and len(why.split()) > 8 and '.hip' in why, "%s(%s): the justification names no kernel file" % (sym, pname)
+        entry, arg = contract.UNALIGNED_SLOT[(sym, pname)]
+        assert (entry, arg, 'offset') in contract.PROMISED, "%s(%s) has no PROMISED offset row" % (sym, pname)
+        # the wrapper of the row reaches the symbol: it calls it, or an entry point whose definition forwards to it
+        reached = calls[entry]
+        assert sym in reached or any(s.startswith(sym) for s in reached), (entry, sym, sorted(reached))
+    # and every promised offset row belongs to an UNALIGNED parameter
+    for (entry, arg, variant) in contract.PROMISED:
+        if variant == 'offset':
+            assert (entry, arg) in set(contract.UNALIGNED_SLOT.values()), (entry, arg)
+
+
+def test_the_binding_normalises_reads_and_refuses_writes_off_alignment():
+    from upsnet_amd import _lib
+    base32, base64 = torch.arange(9, dtype=torch.float32), torch.arange(9, dtype=torch.int64)
+    cases = ((_lib.f32c, base32), (_lib.i32c, base32.to(torch.int32)), (_lib.i64c, base64), (_lib.dense, base32.to(torch.bfloat16)),
+             (_lib.dense, base32.to(torch.uint8)), (_lib.aligned, base64))
+    for fn, t in cases:
+        assert t.data_ptr() % 16 == 0 and fn(t) is t, fn.__name__                 # aligned and in form: the same object
+        off = t[1:]
+        off.tag = 'kept'
+        got = fn(off)
+        assert off.data_ptr() % 16 and got is not off and got.data_ptr() % 16 == 0, fn.__name__
+        assert got.dtype == off.dtype and torch.equal(got, off) and got.is_contiguous() and got.tag == 'kept'
+        assert torch.equal(t, torch.arange(9).to(t.dtype)), "the input was modified"
+    assert _lib.f32c(None) is None and _lib.dense(None) is None and _lib.aligned(None) is None
+    assert _lib.f32c(base64[1:]).data_ptr() % 16 == 0 and _lib.f32c(base64[1:]).dtype == torch.float32       # converted: a fresh block
+    # nhwc: channels_last kept, values equal, aligned; an aligned channels_last tensor is the same object
+    x = torch.arange(2 * 3 * 2 * 2, dtype=torch.float32).view(2, 3, 2, 2).contiguous(memory_format=torch.channels_last)
+    assert _lib.nhwc(x) is x
+    buf = torch.zeros(x.numel() + 1)
+    off = buf.as_strided(tuple(x.shape), tuple(x.stride()), 1)
+    off.copy_(x)
+    got = _lib.nhwc(off)
+    assert off.data_ptr() % 16 and got.data_ptr() % 16 == 0 and torch.equal(got, x) and got.stride() == x.stride()
+    # written: taken as it is, or refused with the word
+    w = torch.zeros(8, dtype=torch.uint8)
+    assert _lib.written(w, None, "x: workspace") is w and _lib.written(None, None, "x") is None
+    for t, dt in ((w[1:], None), (base32[1:], torch.float32), (base64[1:], torch.int64)):
+        with pytest.raises(ValueError, match='x: out must be 16-byte aligned'):
+            _lib.written(t, dt, "x: out")
+    with pytest.raises(ValueError, match='contiguous'):
+        _lib.written(base32[::2], torch.float32, "x: out")
+    # the last line of defence, and its opt-out
+    assert _lib.ptr(base32).value == base32.data_ptr() and _lib.ptr(None) is None
+    for call in (lambda: _lib.ptr(base32[1:]), lambda: _lib.ptr_array([base32, base32[1:]]), lambda: _lib.addr(base64[1:])):
+        with pytest.raises(ValueError, match='not 16-byte aligned'):
+            call()
+    assert _lib.ptr(base32[1:], unaligned=True).value == base32.data_ptr() + 4
+    assert list(_lib.ptr_array([base32[1:], None], unaligned=True)) == [base32.data_ptr() + 4, None]
+    assert _lib.addr(base64[1:], unaligned=True) == base64.data_ptr() + 8 and _lib.addr(base64) == base64.data_ptr()
+    # the spelling the wrappers use: one-argument calls of whatever `ptr` / `ptr_array` is at the moment, so that a guard that stands
+    # in for them (also one written before the second argument existed) records the tensor; the opt-out ends with the call
+    assert _lib.ptr_unaligned(base32[1:]).value == base32.data_ptr() + 4 and _lib.ptr_unaligned(None) is None
+    assert list(_lib.ptr_array_unaligned([base32[1:], None])) == [base32.data_ptr() + 4, None]
+    with pytest.raises(ValueError, match='not 16-byte aligned'):
+        _lib.ptr(base32[1:])
+    seen = []
+    real = _lib.ptr
+    try:
+        _lib.ptr = lambda t: (seen.append(t), real(t))[1]          # a stand-in that takes one argument only
+        off = base32[1:]
+        assert _lib.ptr_unaligned(off).value == off.data_ptr() and seen == [off]
+    finally:
+        _lib.ptr = real
+    logits, row, cls, out = _tensors()
+    off_logits = torch.zeros(49)[1:].view(3, 4, 2, 2)
+    with abiguard.guard(library=Stub()) as g:
+        _gather(_lib.lib, lambda t: _lib.ptr_unaligned(t) if t is off_logits else _lib.ptr(t), off_logits, row, cls, out)
+    assert g.launches() == 1 and not g.violations
+    msg = _refused(lambda: _gather(_lib.lib, _lib.ptr_unaligned, logits, torch.zeros(6, dtype=torch.int32)[1:], cls, out), 'alignment', '(row)')
+    assert '_lib.py' not in msg, "the site must be the caller's, not the binding's"
+
+
+def test_the_offset_variant_builder():
+    import test_abi_contract_gpu as contract
+    make = contract.offset_variant
+    for dt in (torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8, torch.int8, torch.bool, torch.int16, torch.bfloat16,
+               torch.float16):
+        t = (torch.arange(24) % 2 if dt == torch.bool else torch.arange(24)).to(dt).view(2, 3, 4)
+        t.note = 'kept'
+        v = make(t)
+        assert v.dtype == dt and v.shape == t.shape and v.stride() == t.stride() and torch.equal(v, t) and v.note == 'kept'
+        assert v.data_ptr() % 16 == t.element_size() and v.is_contiguous()
+    x = torch.arange(2 * 3 * 2 * 2, dtype=torch.float32).view(2, 3, 2, 2).contiguous(memory_format=torch.channels_last)
+    v = make(x)
+    assert v.is_contiguous(memory_format=torch.channels_last) and not v.is_contiguous() and v.stride() == x.stride() and torch.equal(v, x)
+    assert v.data_ptr() % 16 == 4
+    one = torch.tensor([7], dtype=torch.int64)
+    v = make(one)
+    assert v.shape == (1,) and int(v[0]) == 7 and v.data_ptr() % 16 == 8
+    assert make(torch.zeros(0)) is None and make(torch.zeros(3, 0, dtype=torch.int32)) is None
+    rows = torch.arange(12.).view(3, 4)[:, :2]                       # a view with gaps keeps its pitch
+    v = make(rows)
+    assert v.stride() == rows.stride() and torch.equal(v, rows) and v.data_ptr() % 16 == 4
+    assert dict(contract.VARIANTS)['offset'] is make and [n for n, _ in contract.VARIANTS] == ['strided', 'dtype', 'offset']
+
+
 def test_argument_count_is_checked_against_the_header():
     from upsnet_amd import _lib
     with abiguard.guard(library=Stub()):
@@ -354,11 +517,11 @@ def test_no_pointer_is_taken_of_an_expression_s_temporary():
     for path, rel, mod in abiguard._package_files():
         tree = ast.parse(open(path).read(), rel)
         for n in ast.walk(tree):
-            if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id in ('ptr', 'ptr_array') and n.args:
+            if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id in ('ptr', 'ptr_array', 'ptr_unaligned', 'ptr_array_unaligned') and n.args:
                 a = n.args[0]
-                if n.func.id == 'ptr_array' and isinstance(a, ast.Call) and isinstance(a.func, ast.Name) and a.func.id == 'list' and plain(a.args[0]):
+                if n.func.id.startswith('ptr_array') and isinstance(a, ast.Call) and isinstance(a.func, ast.Name) and a.func.id == 'list' and plain(a.args[0]):
                     continue
-                if n.func.id == 'ptr_array' and isinstance(a, ast.BinOp):          # [None] * A
+                if n.func.id.startswith('ptr_array') and isinstance(a, ast.BinOp):          # [None] * A
                     continue
                 if not plain(a):
                     bad.append("%s:%d: %s(%s)" % (rel, n.lineno, n.func.id, ast.unparse(a)))

@@ -124,8 +124,9 @@ def test_in_place():
 
 
 def test_unaligned_base_pointer_and_width():
-    """Maps that start 3 bytes into their allocation (byte loads instead of 16-byte ones): one with H * W and W multiples of 16, one
-    with W % 16 != 0, where a thread's 16 pixels run over the end of a row."""
+    """Maps that start 3 bytes into their allocation: one with H * W and W multiples of 16, one with W % 16 != 0, where a thread's 16
+    pixels run over the end of a row. The input is read-only and is handed on as an aligned copy; an output that starts there is
+    refused before any launch, so the kernels' byte path for such bases is no longer reached from Python."""
     from upsnet_amd import ops
     rng = np.random.default_rng(91)
     for H, W in ((40, 160), (40, 157)):
@@ -135,8 +136,12 @@ def test_unaligned_base_pointer_and_width():
         src = cuda(np.concatenate([pan.reshape(-1, 3)[:1], pan.reshape(-1, 3)]))[1:].view(H, W, 3)
         dst = torch.zeros((H * W + 1, 3), dtype=torch.uint8, device='cuda')[1:].view(H, W, 3)
         assert src.data_ptr() % 16 and dst.data_ptr() % 16 and src.is_contiguous()
-        out, stats, _ = ops.pan_absorb(src, 4, 8, True, out=dst)
+        with pytest.raises(ValueError, match='aligned'):
+            ops.pan_absorb(src, 4, 8, True, out=dst)
+        assert not dst.any()
+        out, stats, _ = ops.pan_absorb(src, 4, 8, True)
         assert np.array_equal(out.cpu().numpy(), exp[0]) and np.array_equal(stats.cpu().numpy(), exp[2])
+        assert np.array_equal(src.cpu().numpy(), pan)
         out, stats, _ = ops.pan_absorb(cuda(pan), 4, 8, True)           # and aligned: the 16-byte path of the same map
         assert np.array_equal(out.cpu().numpy(), exp[0]) and np.array_equal(stats.cpu().numpy(), exp[2])
 

@@ -93,7 +93,9 @@ def test_in_place():
 
 
 def test_unaligned_input_and_output():
-    """Maps that start 3 bytes into their allocation (byte loads instead of 16-byte ones), with H * W a multiple of 16 and W too."""
+    """Maps that start 3 bytes into their allocation, with H * W a multiple of 16 and W too. The input is read-only and is handed on as
+    an aligned copy; an output that starts there is refused before any launch, so the kernels' byte path for such bases
+    is no longer reached from Python."""
     from upsnet_amd import ops
     rng = np.random.default_rng(77)
     pan = ref.blobs(rng, 40, 160, 11, ref.KEYS, 0.02)
@@ -101,8 +103,12 @@ def test_unaligned_input_and_output():
     src = cuda(np.concatenate([pan.reshape(-1, 3)[:1], pan.reshape(-1, 3)]))[1:].view(40, 160, 3)
     dst = torch.zeros((40 * 160 + 1, 3), dtype=torch.uint8, device='cuda')[1:].view(40, 160, 3)
     assert src.data_ptr() % 16 and dst.data_ptr() % 16 and src.is_contiguous()
-    out, stats, _ = ops.pan_components(src, 4, 8, True, out=dst)
+    with pytest.raises(ValueError, match='aligned'):
+        ops.pan_components(src, 4, 8, True, out=dst)
+    assert not dst.any()
+    out, stats, _ = ops.pan_components(src, 4, 8, True)
     assert np.array_equal(out.cpu().numpy(), exp[0]) and np.array_equal(stats.cpu().numpy(), exp[2])
+    assert np.array_equal(src.cpu().numpy(), pan)
     out, stats, _ = ops.pan_components(cuda(pan), 4, 8, True)          # and aligned: the 16-byte path of the same map
     assert np.array_equal(out.cpu().numpy(), exp[0]) and np.array_equal(stats.cpu().numpy(), exp[2])
 

@@ -224,6 +224,8 @@ def test_used_workspace_gives_the_bytes_of_a_fresh_one():
 
 @pytest.mark.parametrize('shift', [1, 2, 3])
 def test_misaligned_bases_take_the_byte_path(shift):
+    """The map and the image start `shift` bytes into their buffers: read-only inputs, handed on as aligned copies; an output that
+    starts there is refused before any launch, so the kernel's byte path for such bases is no longer reached from Python."""
     from upsnet_amd.dataset import pan_vis
     H, W = 70, 37                                      # 111 bytes per row: the rows' alignment changes from row to row as well
     pred, image = scene(80 + shift, H, W, 25)
@@ -237,9 +239,13 @@ def test_misaligned_bases_take_the_byte_path(shift):
 
     r = pan_vis.PanopticRenderer(CATS19, 'cuda')
     out = off(np.zeros((H, W, 3), np.uint8))
+    with pytest.raises(ValueError, match='aligned'):
+        r.submit(off(pred), off(image), 'overlay', 30, out=out)
+    assert not out.any()
+    out = torch.zeros((H, W, 3), dtype=torch.uint8, device='cuda')
     r.submit(off(pred), off(image), 'overlay', 30, out=out)
     same(out.cpu().numpy(), pan_vis_ref.render_overlay(pred, CATS19, image, font(), 30)[0], 'overlay')
-    out = off(np.zeros((H, W, 3), np.uint8))
+    out = torch.zeros((H, W, 3), dtype=torch.uint8, device='cuda')
     r.submit(off(pred), None, 'flat', out=out)
     same(out.cpu().numpy(), pan_vis_ref.render_flat(pred, CATS19), 'flat')
 

@@ -6,7 +6,8 @@ The sweep writes one JSON row per (entry point, argument, variant) when UPSNET_A
     UPSNET_ABI_FORMS_JSON=new.jsonl    python -m pytest -m gpu tests/test_abi_contract_gpu.py -k test_every_argument_form   # in this tree
     python tools/abi_forms.py parent.jsonl new.jsonl > profiles/abi_forms.txt
 
-The guard and the sweep are test-side, so the same test files run against either tree's package. Exit status 1 if a row goes from
+The guard and the sweep are test-side, so the same test files run against either tree's package (the `offset` rows of a parent from
+before the alignment rule are made that way: this tree's tests/ over the parent's upsnet_amd/). Exit status 1 if a row goes from
 `same` to `refused`, or is neither `same` nor `refused` in the new column.
 """
 import collections
@@ -27,7 +28,7 @@ def load(path):
 
 def short(outcome, detail):
     if outcome == 'violation':
-        m = re.search(r': (origin|liveness|element type|density|device): ', detail)
+        m = re.search(r': (origin|liveness|element type|density|device|alignment): ', detail)
         return 'VIOLATION (%s)' % (m.group(1) if m else '?')
     return outcome if outcome in ('same', 'refused') else outcome.upper()
 
@@ -42,6 +43,8 @@ def main(parent_path, new_path):
     print("# Argument forms across the C ABI: tests/test_abi_contract_gpu.py, form sweep, parent tree and this tree (tools/abi_forms.py)")
     print("# rows: %d (parent %d)   parent: %s   new: %s" % (len(new), len(parent), count(parent), count(new)))
     print("# findings (rows that are neither same nor refused at the parent): %d" % len(findings))
+    for v in sorted({k[2] for k in keys}, key=[k[2] for k in keys].index):
+        print("#   %-14s parent: %s   new: %s" % (v, count({k: r for k, r in parent.items() if k[2] == v}), count({k: r for k, r in new.items() if k[2] == v})))
     print("# same -> refused: %d   neither same nor refused in the new column: %d" % (len(tightened), len(open_rows)))
     print("# refused: ValueError / TypeError / RuntimeError from the wrapper before any entry point that takes a pointer was called (size")
     print("#   queries such as upsnet_*_workspace_bytes take none and launch nothing: they do not count)")

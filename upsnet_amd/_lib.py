@@ -5,6 +5,7 @@ The HIP library IS the product: there is no CPU / eager fallback. If the shared 
 """
 import ctypes
 import os
+import threading
 
 import torch
 
@@ -243,9 +244,35 @@ def check(rc, what):
         raise RuntimeError("upsnet_amd.%s failed: %s" % (what, lib().upsnet_last_error().decode()))
 
 
-def ptr(t):
-    """Device pointer of a tensor (None -> NULL)."""
-    return None if t is None else c_void_p(t.data_ptr())
+_ELEMENT = threading.local()      # depth of ptr_unaligned / ptr_array_unaligned calls in flight on this thread
+
+ALIGN = 16      # bytes: every address handed to an entry point is a multiple of this (include/upsnet_hip.h, "Alignment")
+
+
+def _address(t, unaligned, what):
+    """t.data_ptr(), refused unless it is a multiple of ALIGN. unaligned=True: one of the few parameters the header promises to read at
+    element width only (tests/abiguard.py: UNALIGNED); the wrapper says so where it takes the address."""
+    a = t.data_ptr()
+    if a % ALIGN and not unaligned and not getattr(_ELEMENT, 'depth', 0):
+        raise ValueError("%s: the %s tensor of shape %s at 0x%x is not %d-byte aligned (a view that starts inside an allocation?): read-only "
+                         "inputs go through f32c / i32c / i64c / nhwc / dense, which copy, written ones through written(), which refuses"
+                         % (what, str(t.dtype).replace('torch.', ''), tuple(t.shape), a, ALIGN))
+    return a
+
+
+def ptr(t, unaligned=False):
+    """Device pointer of a tensor (None -> NULL). An address that is not 16-byte aligned is a ValueError unless unaligned=True."""
+    return None if t is None else c_void_p(_address(t, unaligned, 'ptr'))
+
+
+def ptr_unaligned(t):
+    """ptr(t, unaligned=True) as the wrappers spell it: through the module's `ptr` of the moment with one argument, so that whatever
+    stands in for `ptr` (tests/abiguard.py, this tree's or an earlier one's, which knows no second argument) sees the tensor."""
+    _ELEMENT.depth = getattr(_ELEMENT, 'depth', 0) + 1
+    try:
+        return ptr(t)
+    finally:
+        _ELEMENT.depth -= 1
 
 
 def stream():
@@ -258,13 +285,29 @@ def require_cuda(*tensors):
             raise Exception("not implemented")  # same behaviour as functions/deform_conv.py:40-41
 
 
+def aligned(t):
+    """t itself if its address is a multiple of 16, else a copy of equal values, strides and attached attributes in a fresh allocation
+    (the allocator's blocks are aligned far beyond 16 bytes). For READ-ONLY inputs: a copy would swallow a kernel's writes."""
+    if t is None or t.data_ptr() % ALIGN == 0:
+        return t
+    c = t.clone()                       # (preserve_format: a dense view keeps its strides, channels_last stays channels_last)
+    c.__dict__.update(t.__dict__)       # (rois._ups_roi_order and its like travel with the values)
+    return c
+
+
+def dense(t):
+    """contiguous + aligned, the element type kept: a read-only input whose type the wrapper has checked or converted already (bf16
+    packs, uint8 maps, converted counts); None passes through."""
+    return None if t is None else aligned(t.contiguous())
+
+
 def f32c(t):
     """fp32 + contiguous (plumbing); None passes through."""
     if t is None:
         return None
     if t.dtype != torch.float32:
         t = t.float()
-    return t.contiguous()
+    return aligned(t.contiguous())
 
 
 def i32c(t):
@@ -273,7 +316,7 @@ def i32c(t):
         return None
     if t.dtype != torch.int32:
         t = t.to(torch.int32)
-    return t.contiguous()
+    return aligned(t.contiguous())
 
 
 def i64c(t):
@@ -282,22 +325,25 @@ def i64c(t):
         return None
     if t.dtype != torch.int64:
         t = t.to(torch.int64)
-    return t.contiguous()
+    return aligned(t.contiguous())
 
 
 def written(t, dtype, what):
     """A tensor the kernel writes (an output, a workspace, a device counter) is taken as it is or refused: `dtype` (None: any, a
-    workspace of bytes) and contiguous."""
+    workspace of bytes), contiguous and 16-byte aligned."""
     if t is not None and ((dtype is not None and t.dtype != dtype) or not t.is_contiguous()):
         raise ValueError("%s must be a contiguous %s tensor (got %s, strides %s): the kernel writes it, a converted copy would swallow the writes"
                          % (what, 'any-type' if dtype is None else str(dtype).replace('torch.', ''), str(t.dtype).replace('torch.', ''),
                             tuple(t.stride())))
+    if t is not None and t.data_ptr() % ALIGN:
+        raise ValueError("%s must be %d-byte aligned (got a view %d bytes past a multiple of %d): the kernel writes it, an aligned copy would "
+                         "swallow the writes" % (what, ALIGN, t.data_ptr() % ALIGN, ALIGN))
     return t
 
 
 def nhwc(t):
     """Physical NHWC view of a logical NCHW tensor (plumbing; no copy if already channels_last)."""
-    return t.contiguous(memory_format=torch.channels_last)
+    return aligned(t.contiguous(memory_format=torch.channels_last))
 
 
 def int_array(vals):
@@ -308,10 +354,21 @@ def float_array(vals):
     return (c_float * len(vals))(*[float(v) for v in vals])
 
 
-def ptr_array(tensors):
-    return (c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+def ptr_array(tensors, unaligned=False):
+    """Host array of device pointers (None -> NULL); every element is held to 16-byte alignment like ptr()'s."""
+    return (c_void_p * len(tensors))(*[None if t is None else _address(t, unaligned, 'ptr_array') for t in tensors])
 
 
-def addr(t):
-    """Device address of a tensor as a plain int, for a table of addresses that a kernel reads (the caller keeps `t` alive)."""
-    return t.data_ptr()
+def ptr_array_unaligned(tensors):
+    """ptr_array(tensors, unaligned=True) as the wrappers spell it (see ptr_unaligned)."""
+    _ELEMENT.depth = getattr(_ELEMENT, 'depth', 0) + 1
+    try:
+        return ptr_array(tensors)
+    finally:
+        _ELEMENT.depth -= 1
+
+
+def addr(t, unaligned=False):
+    """Device address of a tensor as a plain int, for a table of addresses that a kernel reads (the caller keeps `t` alive); held to
+    16-byte alignment like ptr()'s."""
+    return _address(t, unaligned, 'addr')

@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import check, dense, lib, ptr, stream
 
 
 def check_dilation_ratio(dilation_ratio):
@@ -80,7 +80,7 @@ def mask_to_boundary(masks, dilation_ratio=0.02, size=None, device=None):
         if size is not None and tuple(int(v) for v in size) != (H, W):
             raise ValueError("size %s differs from the masks' %s" % (tuple(size), (H, W)))
         dev = masks.device
-        src = masks.contiguous()
+        src = dense(masks)
         src = src.view(torch.uint8) if src.dtype == torch.bool else src
     if H < 1 or W < 1 or H * W >= 1 << 31:
         raise ValueError("image size %dx%d out of range" % (H, W))

@@ -37,7 +37,7 @@ import warnings
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import aligned, check, lib, ptr, stream
 from .coco_eval import rle_counts
 from .rle import decode_rle_strings
 
@@ -235,12 +235,12 @@ class InstanceEvaluator(object):
         dev = self._dev()
         # one pinned host buffer, one upload: classes | scores | offsets | transitions (all 4-byte items)
         parts = [cls.view(np.uint8), scores.view(np.uint8), off.view(np.uint8), trans.view(np.uint8)]
-        host = torch.empty((sum(p.size for p in parts) + 4,), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        host = torch.empty((sum((p.size + 15) // 16 * 16 for p in parts) + 16,), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
         hn, o, views = host.numpy(), 0, []
         for p in parts:
             hn[o:o + p.size] = p
             views.append((o, p.size))
-            o += p.size
+            o += (p.size + 15) // 16 * 16       # (every part starts on a 16-byte boundary of the upload)
         with torch.cuda.device(dev):
             d = host.to(dev, non_blocking=True)
             d_cls, d_score, d_off = (d[a:a + max(b, 4)].view(dt) for (a, b), dt in zip(views[:3], (torch.int32, torch.float32, torch.int32)))
@@ -286,11 +286,18 @@ class InstanceEvaluator(object):
         transposed = masks is None and n > 0 and self.walk == 'transposed'
         gt_t = torch.empty((W, H), dtype=torch.int16, device=dev) if transposed else None
         b = self._n
+        # the image's records land behind those of the images before it: a part that starts off 16 bytes is written into an aligned
+        # buffer of its own and copied into place
+        dst = [t[b:b + n] if n else t for t in (self._score, self._cls, self._code)]
+        r_score, r_cls, r_code = land = [aligned(d) for d in dst]
         check(l.upsnet_cs_inst_image(stream(), ptr(gt), H, W, n, ptr(d_cls) if n else None, ptr(d_score) if n else None,
                                      ptr(d_trans) if n else None, ptr(d_off) if n else None, ptr(masks) if n else None,
                                      int(self.walk == 'strided'), ptr(gt_t), self._thr, len(OVERLAPS), ptr(counts), ptr(ws),
-                                     ptr(self._score[b:]) if n else None, ptr(self._cls[b:]) if n else None,
-                                     ptr(self._code[b:]) if n else None, ptr(self._state)), "cs_inst_image")
+                                     ptr(r_score) if n else None, ptr(r_cls) if n else None,
+                                     ptr(r_code) if n else None, ptr(self._state)), "cs_inst_image")
+        for d, t in zip(dst, land):
+            if t is not d:
+                d.copy_(t)
         self._n += n
         self.num_images += 1
         self._last = (counts, n)

@@ -37,7 +37,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .._lib import check, i32c, lib, ptr, stream, written
+from .._lib import aligned, check, dense, i32c, lib, ptr, stream, written
 from .cityscapes_eval import CLASS_LABEL_IDS, CLASS_NAMES, MAX_PREDS, NUM_CLASSES, _transitions
 from .pan_format import MAX_ENCODE_THREADS
 
@@ -90,8 +90,14 @@ def _expand_into(d_trans, d_off, n, H, W, one_bit, out, max_bytes):
     flat = written(out, torch.uint8, "expand_masks: out").view(-1)
     for m0 in range(0, n, step):
         nm = min(step, n - m0)
-        check(lib().upsnet_cs_inst_expand(stream(), ptr(d_trans), ptr(d_off[m0:]), nm, H, W, 1 if one_bit else 8, ptr(flat[m0 * per:])),
-              "cs_inst_expand")
+        # a chunk's offsets and planes start wherever the chunk does: the offsets are read from an aligned copy, and a chunk of planes
+        # that starts off 16 bytes (H * W or the bit rows need not be a multiple of 16) is expanded into a buffer of its own and copied
+        off = aligned(d_off[m0:m0 + nm + 1])
+        dst = flat[m0 * per:(m0 + nm) * per]
+        planes = aligned(dst)
+        check(lib().upsnet_cs_inst_expand(stream(), ptr(d_trans), ptr(off), nm, H, W, 1 if one_bit else 8, ptr(planes)), "cs_inst_expand")
+        if planes is not dst:
+            dst.copy_(planes)
 
 
 def expand_masks(trans, off, H, W, one_bit=False, out=None, max_bytes=None):
@@ -125,8 +131,8 @@ def expand_masks(trans, off, H, W, one_bit=False, out=None, max_bytes=None):
             out = torch.empty(shape, dtype=torch.uint8, device=dev)
         if n == 0:
             return out
-        d_trans = trans.contiguous() if isinstance(trans, torch.Tensor) else torch.from_numpy(t_np).to(dev)
-        d_off = off.contiguous() if isinstance(off, torch.Tensor) else torch.from_numpy(o_np).to(dev)
+        d_trans = dense(trans) if isinstance(trans, torch.Tensor) else torch.from_numpy(t_np).to(dev)
+        d_off = dense(off) if isinstance(off, torch.Tensor) else torch.from_numpy(o_np).to(dev)
         if d_trans.numel() == 0:
             d_trans = torch.zeros((1,), dtype=torch.int32, device=dev)       # never empty (a valid address)
         _expand_into(d_trans, d_off, n, H, W, one_bit, out, max_bytes)
@@ -230,16 +236,17 @@ class InstanceMaskFormatter(object):
         off = off.astype(np.int32)
         n = off.size - 1
         check_runs(trans, off, H, W)
-        # one pinned host buffer, one upload: offsets | transitions (all 4-byte items)
-        host = torch.empty((off.size + trans.size + 1,), dtype=torch.int32, pin_memory=True)
+        # one pinned host buffer, one upload: offsets | transitions (all 4-byte items; the transitions start on a 16-byte boundary)
+        t0 = (off.size + 3) // 4 * 4
+        host = torch.empty((t0 + trans.size + 1,), dtype=torch.int32, pin_memory=True)
         hn = host.numpy()
         hn[:off.size] = off
-        hn[off.size:off.size + trans.size] = trans
+        hn[t0:t0 + trans.size] = trans
         per = plane_bytes(H, W, self.one_bit)
         step = max(1, MAX_LAUNCH_BYTES // per)
         with torch.cuda.device(self.device):
             d = host.to(self.device, non_blocking=True)
-            d_off, d_trans = d[:off.size], d[off.size:]          # (d_trans is never empty: the spare item)
+            d_off, d_trans = d[:off.size], d[t0:]          # (d_trans is never empty: the spare item)
             for m0 in range(0, n, step):
                 nm = min(step, n - m0)
                 planes = torch.empty((nm, H, per // H), dtype=torch.uint8, device=self.device)

@@ -34,7 +34,7 @@ import math
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import aligned, check, lib, ptr, stream
 from .cityscapes_eval import CLASS_LABEL_IDS, CLASS_NAMES, VOID_VALUES
 
 logger = logging.getLogger(__name__)
@@ -174,7 +174,7 @@ class PixelEvaluator(object):
         self.images_without_ids = 0
         self.names = []
         self._conf = self._wsum = None
-        self._bad = []          # blocks of int32 [_BAD_BLOCK][2], one row per image
+        self._bad = []          # blocks of int32 [_BAD_BLOCK][4], one row per image: two counters, padded so every row starts on 16 bytes
         self._luts = {}
         self._last = None
 
@@ -189,8 +189,8 @@ class PixelEvaluator(object):
             self._conf = torch.zeros((NUM_LABELS, NUM_LABELS), dtype=torch.int64, device=dev)
             self._wsum = torch.zeros((len(WSUM_ROWS), 4), dtype=torch.float64, device=dev)
         if self.num_images == len(self._bad) * _BAD_BLOCK:
-            self._bad.append(torch.zeros((_BAD_BLOCK, 2), dtype=torch.int32, device=dev))
-        return self._bad[-1][self.num_images % _BAD_BLOCK]
+            self._bad.append(torch.zeros((_BAD_BLOCK, 4), dtype=torch.int32, device=dev))
+        return self._bad[-1][self.num_images % _BAD_BLOCK][:2]
 
     def add(self, gt_labels, gt_ids, pred, train_ids=True, name=None):
         """One image: gt_labels uint8 [H, W] (label ids), gt_ids uint16 [H, W] (the instance-id map) or None (IoU only), pred uint8
@@ -214,6 +214,7 @@ class PixelEvaluator(object):
                 self._luts[train_ids] = torch.from_numpy(lookup_table(train_ids)).to(dev)
             gl, pr = gl.to(dev, non_blocking=True), pr.to(dev, non_blocking=True)
             gi = None if gi is None else gi.to(dev, non_blocking=True)
+            gl, pr, gi = aligned(gl), aligned(pr), aligned(gi)
             inst = None if gi is None else torch.empty((lib().upsnet_cs_pixel_inst_ints(),), dtype=torch.int32, device=dev)
             check(lib().upsnet_cs_pixel_image(stream(), ptr(gl), ptr(gi), ptr(pr), ptr(self._luts[train_ids]), H, W, self._avg,
                                               ptr(self._conf), ptr(inst), ptr(self._wsum), ptr(bad)), "cs_pixel_image")
@@ -242,10 +243,10 @@ class PixelEvaluator(object):
         self._conf += other._conf.to(dev)
         self._wsum += other._wsum.to(dev)
         # (the error counters stay one row per image: this evaluator's rows, then the other's)
-        mine = torch.cat(self._bad)[:self.num_images] if self._bad else torch.zeros((0, 2), dtype=torch.int32, device=dev)
+        mine = torch.cat(self._bad)[:self.num_images] if self._bad else torch.zeros((0, 4), dtype=torch.int32, device=dev)
         rows = torch.cat([mine, torch.cat(other._bad)[:other.num_images].to(dev)])
         pad = (-rows.shape[0]) % _BAD_BLOCK
-        rows = torch.cat([rows, torch.zeros((pad, 2), dtype=torch.int32, device=dev)])
+        rows = torch.cat([rows, torch.zeros((pad, 4), dtype=torch.int32, device=dev)])
         self._bad = list(rows.split(_BAD_BLOCK))
         self.names += other.names
         self.num_images += other.num_images

@@ -25,7 +25,7 @@ import logging
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, ptr_array, stream
+from .._lib import aligned, check, lib, ptr, ptr_array, stream
 from .boundary import check_dilation_ratio, checked_dilation
 from .polygon import PolygonView
 
@@ -417,7 +417,13 @@ class DetectionEvaluator(object):
         o = self._n_rec
         u8_p = u8_ptrs if n_u8 else None          # (host arrays: of the planes' device addresses, of their rows)
         u8_d = u8_dst if n_u8 else None
-        recs = (ptr(rec['score'][o:]), ptr(rec['img'][o:]), ptr(rec['rk'][o:]), ptr(rec['match'][o:]), ptr(rec['ign'][o:]), ptr(st['npig']))
+        # the image's records land behind those of the images before it, so their start is element-aligned only: a part that starts
+        # off 16 bytes is written into an aligned buffer of its own and copied into place (rows past n are not touched by the launch)
+        names = ('score', 'img', 'rk', 'match', 'ign')
+        dst = [rec[k][o:o + n] if n else rec[k] for k in names]
+        land = [aligned(d) for d in dst]
+        keep += land
+        recs = tuple(ptr(t) for t in land) + (ptr(st['npig']),)
         if self.boundary:
             check(lib().upsnet_det_eval_boundary_image(
                 stream(), dilation, H, W, K, n, ptr(score), ptr(cls), ptr(st['lut']), st['lut'].numel(), ptr(box_f32), ptr(masks), C, Ms,
@@ -430,7 +436,10 @@ class DetectionEvaluator(object):
                 st['lut'].numel(), ptr(box_f32), ptr(masks), C, Ms, ptr(det_trans), ptr(det_off), g['n'], ptr(gt_row_off), ptr(gt_box),
                 ptr(gt_area), ptr(gt_crowd), ptr(gt_trans), ptr(gt_off), ptr(gt_dst), n_rle, u8_p, u8_d, n_u8, ptr(rows),
                 len(g['rows_with_gt']), ptr(st['params']), self.num_images, ptr(ws), *recs), "det_eval_image")
-        del keep   # the caching allocator orders the reuse of these blocks after the queued launches
+        for d, t in zip(dst, land):
+            if t is not d:
+                d.copy_(t)
+        del keep, land   # the caching allocator orders the reuse of these blocks after the queued launches
         self._n_rec += n
         self.image_ids.append(image_id)
         self._ids.add(image_id)

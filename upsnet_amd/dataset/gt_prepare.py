@@ -4,7 +4,7 @@ re-exports these functions."""
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, require_cuda, stream, written
+from .._lib import check, dense, lib, ptr, require_cuda, stream, written
 
 GT_PREPARE_SEGMENTS = 4096      # default segment capacity of gt_prepare (a Cityscapes image holds a few hundred)
 GT_ROW = 9                      # ints per segment row: v, label, train id, iscrowd, area, x_min, y_min, x_max, y_max
@@ -48,8 +48,7 @@ def gt_prepare_launch(ids, tables, label_ids=None, seg_capacity=GT_PREPARE_SEGME
     trans_capacity = gt_prepare_default_transitions(H, W) if trans_capacity is None else int(trans_capacity)
     if not 1 <= seg_capacity <= 65536 or not 0 <= trans_capacity < 1 << 31:
         raise ValueError("gt_prepare: capacities %d segments / %d transitions" % (seg_capacity, trans_capacity))
-    ids, tables = ids.contiguous(), tables.contiguous()
-    label_ids = label_ids.contiguous() if label_ids is not None else None
+    ids, tables, label_ids = dense(ids), dense(tables), dense(label_ids)
     dev = ids.device
     if workspace is None:
         workspace = gt_prepare_workspace(dev, seg_capacity)

@@ -38,7 +38,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, require_cuda, stream, written
+from .._lib import check, dense, lib, ptr, require_cuda, stream, written
 from .pq import MAX_CATEGORY, _check_image
 
 logger = logging.getLogger(__name__)
@@ -185,7 +185,7 @@ class PanopticFormatter(object):
             pred_host = np.ascontiguousarray(pred_2ch)
             pred_2ch = torch.from_numpy(pred_host).to(self.device, non_blocking=True)
         require_cuda(pred_2ch)
-        pred_2ch = pred_2ch.contiguous()
+        pred_2ch = dense(pred_2ch)
         H, W = int(pred_2ch.shape[0]), int(pred_2ch.shape[1])
         if H * W == 0 or H * W >= 1 << 31:
             raise ValueError("pred_2ch of %d x %d pixels" % (H, W))
@@ -371,7 +371,7 @@ def relabel(rgb, table, image_index, status):
     written(status, torch.int64, "relabel: status")
     table = np.ascontiguousarray(table, np.int32).reshape(-1, 3)
     n = int(table.shape[0])
-    rgb = rgb.contiguous()
+    rgb = dense(rgb)
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
     out = torch.empty((H, W, 3), dtype=torch.uint8, device=rgb.device)
     counts = torch.zeros((max(n, 1),), dtype=torch.int32, device=rgb.device)

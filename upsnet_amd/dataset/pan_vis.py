@@ -21,7 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import check, dense, lib, ptr, stream, written
 from .pan_format import PanopticFormatter, category_dict, png_name
 from .pq import _check_image
 from .vis import MAX_DECODE_THREADS, MAX_ENCODE_THREADS, _save_png, load_image
@@ -103,13 +103,13 @@ class PanopticRenderer(object):
             pred_2ch = torch.from_numpy(np.ascontiguousarray(pred_2ch)).to(dev, non_blocking=True)
         if not pred_2ch.is_cuda:
             raise RuntimeError("render_panoptic: the map must be on the device (there is no CPU fallback)")
-        pred_2ch = pred_2ch.contiguous()
+        pred_2ch = dense(pred_2ch)
         if mode == 'overlay':
             if isinstance(image, np.ndarray):
                 image = torch.from_numpy(np.ascontiguousarray(image)).to(dev, non_blocking=True)
             if not image.is_cuda:
                 raise RuntimeError("render_panoptic: the image must be on the device (there is no CPU fallback)")
-            image = image.contiguous()
+            image = dense(image)
         with torch.cuda.device(dev):
             handle = self.formatter.submit(pred_2ch)
             table = handle.buf[handle.offset:].view(torch.int32)
@@ -118,6 +118,7 @@ class PanopticRenderer(object):
             elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (H, W, 3)
                       and out.is_contiguous()):
                 raise ValueError("out must be a contiguous uint8 device tensor of shape %s" % ((H, W, 3),))
+            written(out, torch.uint8, "render_panoptic: out")
             info = torch.empty((2,), dtype=torch.int32, device=dev)
             overlay = mode == 'overlay'
             colours = handle.buf

@@ -10,7 +10,7 @@ format, restated from the published algorithm).
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import check, f32c, i64c, lib, ptr, stream
 
 
 def counts_from_transitions(positions, num_pixels):
@@ -42,9 +42,7 @@ def mask_transitions(pred_boxes, pred_masks, cls_inds, im_h, im_w, cap=4096):
     n = pred_boxes.shape[0]
     if n == 0:
         return []
-    boxes = pred_boxes.float().contiguous()
-    masks = pred_masks.float().contiguous()
-    cls = cls_inds.to(torch.int64).contiguous()
+    boxes, masks, cls = f32c(pred_boxes), f32c(pred_masks), i64c(cls_inds)
     if not (boxes.is_cuda and masks.is_cuda and cls.is_cuda):
         raise RuntimeError("mask_transitions: CUDA tensors required")
     C, M = masks.shape[1], masks.shape[-1]

@@ -21,7 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import check, dense, lib, ptr, stream
 
 logger = logging.getLogger(__name__)
 
@@ -116,7 +116,7 @@ def render_detections(image_rgb, boxes, labels, colours, trans, trans_off):
         raise ValueError("image_rgb must be uint8 [H, W, 3], got %r" % (getattr(image_rgb, 'shape', type(image_rgb)),))
     if not image_rgb.is_cuda:
         raise RuntimeError("render_detections: the image must be on the device (there is no CPU fallback)")
-    image_rgb = image_rgb.contiguous()
+    image_rgb = dense(image_rgb)
     dev = image_rgb.device
     H, W = int(image_rgb.shape[0]), int(image_rgb.shape[1])
     boxes = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 4))
@@ -144,17 +144,17 @@ def render_detections(image_rgb, boxes, labels, colours, trans, trans_off):
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         views = [None] * 6
         if n:
-            # one pinned host buffer, one upload: the 4-byte items first, then the bytes
+            # one pinned host buffer, one upload: the 4-byte items first, then the bytes; every part starts on a 16-byte boundary
             parts = [boxes.view(np.uint8).reshape(-1), label_len.view(np.uint8), trans_off.astype(np.int32).view(np.uint8), trans.view(np.uint8),
                      label_bytes.reshape(-1), colours.reshape(-1)]
-            host = torch.empty((sum(p.size for p in parts) + 4,), dtype=torch.uint8, pin_memory=True)
+            host = torch.empty((sum((p.size + 15) // 16 * 16 for p in parts) + 16,), dtype=torch.uint8, pin_memory=True)
             hn, o, spans = host.numpy(), 0, []
             for p in parts:
                 hn[o:o + p.size] = p
                 spans.append((o, max(p.size, 4)))
-                o += p.size
+                o += (p.size + 15) // 16 * 16
             d = host.to(dev, non_blocking=True)
-            kinds = (torch.float32, torch.int32, torch.int32, torch.int32, torch.uint8, torch.uint8)       # (the 4-byte items start at multiples of 4)
+            kinds = (torch.float32, torch.int32, torch.int32, torch.int32, torch.uint8, torch.uint8)
             views = [d[a:a + b].view(k) for (a, b), k in zip(spans, kinds)]
         d_boxes, d_len, d_off, d_trans, d_labels, d_colours = views
         check(lib().upsnet_vis_render(stream(), ptr(image_rgb), H, W, n, ptr(d_boxes), ptr(d_colours), ptr(d_labels), ptr(d_len),

@@ -9,7 +9,7 @@ place; nothing is cached.
 """
 import torch
 
-from ._lib import check, int_array, lib, ptr, ptr_array, require_cuda, stream
+from ._lib import aligned, check, int_array, lib, ptr, ptr_array, require_cuda, stream
 
 GROUPS = 32
 MAX_MAPS = 5
@@ -31,7 +31,7 @@ def _nhwc(x):
         x = x.float()
     if not x.permute(0, 2, 3, 1).is_contiguous():
         x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    return x
+    return aligned(x)
 
 
 def _affine(gamma, beta, channels):
@@ -40,7 +40,7 @@ def _affine(gamma, beta, channels):
     for t in (gamma, beta):
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise RuntimeError("group_norm: gamma / beta must be contiguous fp32 (they are read in place)")
-    return gamma.detach(), beta.detach()
+    return aligned(gamma.detach()), aligned(beta.detach())
 
 
 def _out_like(x):
@@ -101,6 +101,7 @@ def group_norm_small(x, gamma, beta, eps=1e-5, relu=False):
     if x.dim() == 2:
         if x.dtype != torch.float32 or not x.is_contiguous():
             x = x.float().contiguous()
+        x = aligned(x)
         n, C = x.shape
         h = w = 1
         out = torch.empty((n, C), dtype=torch.float32, device=x.device)

@@ -68,7 +68,9 @@ class DeformConvFunction(Function):
         data, offset = data.detach().float().contiguous(), offset.detach().float().contiguous()
         grad_output = grad_output.detach().float().contiguous()
         w2d = weight.detach().float().reshape(out_channels, -1)
-        grad_data, grad_offset = torch.zeros_like(data), torch.zeros_like(offset)
+        # one gradient tensor per image, stacked at the end: image i of one [N,...] tensor starts wherever image i - 1 ends, which is
+        # 16-byte aligned only for some shapes, and the kernels write these
+        grad_data, grad_offset = [torch.zeros_like(t) for t in data], [torch.zeros_like(t) for t in offset]
         grad_weight = torch.zeros_like(w2d)
         Ho, Wo = grad_output.shape[2:]
         shape = tuple(data.shape)
@@ -84,4 +86,4 @@ class DeformConvFunction(Function):
                                            deformable_groups, col_buffer)
             grad_weight += torch.mm(go, col_buffer.view(cshape[0], -1).t())
         grad_bias = grad_output.sum(dim=(0, 2, 3)) if bias is not None else None
-        return (grad_data, grad_offset, grad_weight.view_as(weight), grad_bias) + (None,) * 8
+        return (torch.stack(grad_data), torch.stack(grad_offset), grad_weight.view_as(weight), grad_bias) + (None,) * 8

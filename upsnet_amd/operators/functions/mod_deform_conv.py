@@ -60,7 +60,8 @@ class ModDeformConvFunction(Function):
         data, offset, mask = (t.detach().float().contiguous() for t in (data, offset, mask))
         grad_output = grad_output.detach().float().contiguous()
         w2d = weight.detach().float().reshape(out_channels, -1)
-        grad_data, grad_offset, grad_mask = torch.zeros_like(data), torch.zeros_like(offset), torch.zeros_like(mask)
+        # (one gradient tensor per image, stacked at the end: see functions/deform_conv.py)
+        grad_data, grad_offset, grad_mask = ([torch.zeros_like(t) for t in x] for x in (data, offset, mask))
         grad_weight = torch.zeros_like(w2d)
         Ho, Wo = grad_output.shape[2:]
         shape = tuple(data.shape)
@@ -77,4 +78,4 @@ class ModDeformConvFunction(Function):
                                                    dilation, deformable_groups, col_buffer)
             grad_weight += torch.mm(go, col_buffer.view(cshape[0], -1).t())
         grad_bias = grad_output.sum(dim=(0, 2, 3)) if bias is not None else None
-        return (grad_data, grad_offset, grad_mask, grad_weight.view_as(weight), grad_bias) + (None,) * 8
+        return (torch.stack(grad_data), torch.stack(grad_offset), torch.stack(grad_mask), grad_weight.view_as(weight), grad_bias) + (None,) * 8

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import addr, check, f32c, float_array, i32c, i64c, int_array, lib, nhwc, ptr, ptr_array, require_cuda, stream, written
+from ._lib import addr, aligned, check, dense, f32c, float_array, i32c, i64c, int_array, lib, nhwc, ptr, ptr_array, ptr_array_unaligned, ptr_unaligned, require_cuda, stream, written
 
 
 # bench.py sets PROFILE['enabled'] to bracket the dominant kernel with events on the launch stream
@@ -338,7 +338,7 @@ def deform_conv_fused(xs, offsets, wpack, bias, cin, cout, ksize, stride, pad, d
     wp, ldw = wpack     # ('frag', packed) or (packed, ldw)
     require_cuda(ldw if isinstance(wp, str) else wp, *xs)
     if isinstance(wp, str):
-        ldw = ldw.contiguous() if wp == 'frag_bf16' else f32c(ldw)
+        ldw = dense(ldw) if wp == 'frag_bf16' else f32c(ldw)
     else:
         wp = f32c(wp)
     n = len(xs)
@@ -416,13 +416,13 @@ def nms_batched(boxes, scores, counts, thresh, pre_removed=None):
     """boxes [P,nmax,4], scores [P,nmax], counts [P] int32 (device) -> keep_idx [P,nmax] int32, keep_cnt [P]."""
     require_cuda(boxes, scores, counts)
     boxes, scores = f32c(boxes), f32c(scores)
-    counts = counts.to(torch.int32).contiguous()
+    counts = i32c(counts)
     Pn, nmax = scores.shape
     dev = boxes.device
     keep = torch.empty((Pn, nmax), dtype=torch.int32, device=dev)
     cnt = torch.empty((Pn,), dtype=torch.int32, device=dev)
     ws = _ws(lib().upsnet_nms_workspace_bytes(Pn, nmax), dev)
-    pr = None if pre_removed is None else pre_removed.to(torch.uint8).contiguous()
+    pr = None if pre_removed is None else dense(pre_removed.to(torch.uint8))
     check(lib().upsnet_nms_batched(stream(), ptr(boxes), ptr(scores), ptr(counts), ptr(pr), Pn, nmax, float(thresh),
                                    ptr(keep), ptr(cnt), ptr(ws)), "nms_batched")
     return keep, cnt
@@ -468,7 +468,7 @@ def soft_nms_batched(boxes, counts=None, sigma=0.5, Nt=0.3, threshold=0.001, met
     inds = torch.empty((Pn, max(nmax, 1)), dtype=torch.int64, device=b.device)
     n_out = torch.zeros((max(Pn, 1),), dtype=torch.int32, device=b.device)
     if Pn and nmax:
-        cnt = None if counts is None else counts.to(device=b.device, dtype=torch.int32).contiguous()
+        cnt = None if counts is None else i32c(counts.to(device=b.device))
         ws = _ws(lib().upsnet_soft_nms_batched_workspace_bytes(Pn, nmax), b.device)
         check(lib().upsnet_soft_nms_batched(stream(), ptr(b), ptr(inds), ptr(cnt), Pn, nmax, float(sigma), float(Nt), float(threshold),
                                             int(method), ptr(n_out), ptr(ws)), "soft_nms_batched")
@@ -487,7 +487,8 @@ def pyramid_proposals(cls_probs, bbox_preds, im_info, anchors, strides, pre_nms_
                       min_size, joint=False):
     """Device-side PyramidProposal. cls_probs[l] [1,A,H,W], bbox_preds[l] [1,4A,H,W]; im_info device [3].
     Returns fixed-size (rois [post,5], scores [post], num device int32). joint = the individual_proposals=False branch
-    (functions/pyramid_proposal.py:181-208): kept boxes in NMS order, before the reference's random padding."""
+    (functions/pyramid_proposal.py:181-208): kept boxes in NMS order, before the reference's random padding.
+    A channel slice of a wider map is read in place, wherever it starts (element-aligned: the kernels read one float per access)."""
     require_cuda(im_info, *cls_probs)
     L = len(cls_probs)
 
@@ -518,7 +519,7 @@ def pyramid_proposals(cls_probs, bbox_preds, im_info, anchors, strides, pre_nms_
     anc = float_array(np.asarray(anchors, np.float32).reshape(-1).tolist())
     long_array = lambda v: (_lib.c_long * len(v))(*[int(x) for x in v])
     im_info = f32c(im_info)
-    args = (stream(), L, ptr_array(cls_probs), ptr_array(bbox_preds), long_array(cls_cs), long_array(cls_ps), long_array(box_cs), long_array(box_ps),
+    args = (stream(), L, ptr_array_unaligned(cls_probs), ptr_array_unaligned(bbox_preds), long_array(cls_cs), long_array(cls_ps), long_array(box_cs), long_array(box_ps),
             hs, ws_, int_array(strides), anc, A, ptr(im_info), int(pre_nms_top_n), int(post_nms_top_n), float(nms_thresh), float(min_size),
             ptr(rois), ptr(scores), ptr(num), ptr(ws))
     if joint:
@@ -559,16 +560,17 @@ def mask_roi(rois, bbox_delta, cls_prob, im_info, class_agnostic, score_thresh, 
 
 def mask_logit_gather(mask_logit, row, cls, K=None):
     """pan_logit [K,1,ms,ms] with pan_logit[k] = mask_logit[row[k], cls[k]] (rows / classes clamped): one gather kernel instead of
-    clamp + index_select + expand + gather. mask_logit: [n,C,ms,ms] in any dense layout (NCHW or channels_last)."""
+    clamp + index_select + expand + gather. mask_logit: [n,C,ms,ms] in any dense layout (NCHW or channels_last); it may start anywhere
+    in an allocation (element-aligned: the kernel reads one float per access), every other tensor is held to 16 bytes."""
     require_cuda(mask_logit, row, cls)
     n, C, mh, mw = mask_logit.shape
     t = mask_logit if mask_logit.dtype == torch.float32 else mask_logit.float()
     if not (t.stride(2) == mw * t.stride(3)):
-        t = t.contiguous()
+        t = dense(t)
     K = row.shape[0] if K is None else int(K)
     out = torch.empty((K, 1, mh, mw), dtype=torch.float32, device=t.device)
     row, cls = i32c(row), i64c(cls)      # (bound before the call: a temporary's block is free again once ptr() returns)
-    check(lib().upsnet_mask_logit_gather(stream(), ptr(t), n, C, mh * mw, t.stride(0), t.stride(1), t.stride(3),
+    check(lib().upsnet_mask_logit_gather(stream(), ptr_unaligned(t), n, C, mh * mw, t.stride(0), t.stride(1), t.stride(3),
                                          ptr(row), ptr(cls), K, ptr(out)),
           "mask_logit_gather")
     return out
@@ -966,7 +968,7 @@ def panoptic_fuse_up(fcn_score, scale, num_stuff, mask_rois5, mask_logit, cls_id
     sc = fcn_score.float()
     _, S, Hs, Ws = sc.shape
     is_nhwc = (not sc.is_contiguous()) and sc.is_contiguous(memory_format=torch.channels_last)
-    sc = sc if is_nhwc else sc.contiguous()
+    sc = aligned(sc) if is_nhwc else dense(sc)
     mask_rois5 = f32c(mask_rois5)
     m = mask_rois5.shape[0]
     if m > 256:   # the kernels keep their instance table in LDS (FUSE_MAXK); more rows would be dropped silently
@@ -1066,7 +1068,7 @@ def stem_pool_bf16(x4, wpack, bias):
     """relu(conv7x7/2/3(x) + bias) -> max_pool 3x3/2/1 in one launch; x4: logical [N,4,H,W] channels_last fp32 (image_to_nhwc4 /
     prep_image_u8). Returns a bf16 channels_last [N,64,Hp,Wp]."""
     require_cuda(x4, wpack)
-    wpack = wpack.contiguous()
+    wpack = dense(wpack)
     x4 = nhwc(x4.float())
     N, C, H, W = x4.shape
     if C != 4:
@@ -1182,7 +1184,7 @@ def pack_deconv2x2_weight_bf16(weight):
 def deconv2x2_bf16(x, whi, ldw, bias, cout, relu=False, out_dtype=torch.float32):
     """ConvTranspose2d(k=2, s=2, p=0) (+bias, +ReLU) of a bf16 map on the bf16 matrix cores; channels_last [N,Cout,2H,2W]."""
     require_cuda(x, whi)
-    whi = whi.contiguous()
+    whi = dense(whi)
     if x.dtype != torch.bfloat16:
         raise RuntimeError("deconv2x2_bf16: expects a bf16 map")
     x = nhwc(x)
@@ -1206,7 +1208,7 @@ def prep_image_u8(image_hwc, pixel_means, im_scale, resized_hw, padded_hw, nhwc4
     require_cuda(image_hwc)
     if image_hwc.dtype != torch.uint8 or image_hwc.dim() != 3 or image_hwc.shape[2] != 3:
         raise RuntimeError("prep_image_u8: expected a uint8 [H,W,3] image")
-    im = image_hwc.contiguous()
+    im = dense(image_hwc)
     H, W = im.shape[:2]
     (Hr, Wr), (Hp, Wp) = resized_hw, padded_hw
     means = (ctypes.c_double * 3)(*[float(m) for m in pixel_means])
@@ -1218,8 +1220,8 @@ def prep_image_u8(image_hwc, pixel_means, im_scale, resized_hw, padded_hw, nhwc4
 
 def restore_label_maps(sseg, pano, y_ofs, x_ofs):
     """Nearest-neighbour gather of one image's label maps (include/upsnet_hip.h: upsnet_restore_label_maps): sseg / pano int64 [H,W]
-    or [1,H,W] device tensors (pano may be None; rows may be strided, columns contiguous), y_ofs / x_ofs int32 index tables (host
-    or device; dataset/restore.py builds them). Returns (uint8 [len(y_ofs), len(x_ofs)] for sseg, the same for pano or None);
+    or [1,H,W] device tensors (pano may be None; rows may be strided, columns contiguous; a crop may start at any element of the padded
+    map), y_ofs / x_ofs int32 index tables (host or device; dataset/restore.py builds them). Returns (uint8 [len(y_ofs), len(x_ofs)] for sseg, the same for pano or None);
     out[y, x] = low byte of src[y_ofs[y], x_ofs[x]]. Both maps come out of one launch."""
     require_cuda(sseg, pano)
     maps = [m.reshape(m.shape[-2], m.shape[-1]) if m is not None else None for m in (sseg, pano)]
@@ -1228,27 +1230,27 @@ def restore_label_maps(sseg, pano, y_ofs, x_ofs):
             raise ValueError("restore_label_maps: int64 maps with contiguous rows required, got %s stride %s" % (m.dtype, m.stride()))
     s, p = maps
     if p is not None and (p.shape != s.shape or p.stride() != s.stride()):
-        s, p = s.contiguous(), p.contiguous()
+        s, p = dense(s), dense(p)
     H, W = s.shape
     ys = torch.as_tensor(y_ofs, dtype=torch.int32).reshape(-1)
     xs = torch.as_tensor(x_ofs, dtype=torch.int32).reshape(-1)
     for name, t, n in (("y_ofs", ys, H), ("x_ofs", xs, W)):
         if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
             raise ValueError("restore_label_maps: %s outside 0..%d" % (name, n - 1))
-    ys, xs = ys.to(s.device).contiguous(), xs.to(s.device).contiguous()
+    ys, xs = dense(ys.to(s.device)), dense(xs.to(s.device))
     H0, W0 = ys.numel(), xs.numel()
     out_s = torch.empty((H0, W0), dtype=torch.uint8, device=s.device)
     out_p = torch.empty((H0, W0), dtype=torch.uint8, device=s.device) if p is not None else None
     if H0 == 0 or W0 == 0:
         return out_s, out_p
-    check(lib().upsnet_restore_label_maps(stream(), ptr(s), ptr(p), int(s.stride(0)), H, W, ptr(ys), H0, ptr(xs), W0, ptr(out_s),
+    check(lib().upsnet_restore_label_maps(stream(), ptr_unaligned(s), ptr_unaligned(p), int(s.stride(0)), H, W, ptr(ys), H0, ptr(xs), W0, ptr(out_s),
                                           ptr(out_p)), "restore_label_maps")
     return out_s, out_p
 
 
 def restore_plane_u8(plane, y_ofs, x_ofs, *, out=None):
     """restore_label_maps' gather for one uint8 plane (include/upsnet_hip.h: upsnet_restore_plane_u8): plane uint8 [H,W] or [1,H,W]
-    device tensor (rows may be strided, columns contiguous), the same index tables. Returns uint8 [len(y_ofs), len(x_ofs)] =
+    device tensor (rows may be strided, columns contiguous; a crop may start at any byte of the padded plane), the same index tables. Returns uint8 [len(y_ofs), len(x_ofs)] =
     plane[y_ofs[y], x_ofs[x]]: the panoptic confidence at the original image size, by the rule of the label maps. out= is taken
     instead of being allocated."""
     require_cuda(plane)
@@ -1261,7 +1263,7 @@ def restore_plane_u8(plane, y_ofs, x_ofs, *, out=None):
     for name, t, n in (("y_ofs", ys, H), ("x_ofs", xs, W)):
         if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
             raise ValueError("restore_plane_u8: %s outside 0..%d" % (name, n - 1))
-    ys, xs = ys.to(s.device).contiguous(), xs.to(s.device).contiguous()
+    ys, xs = dense(ys.to(s.device)), dense(xs.to(s.device))
     H0, W0 = ys.numel(), xs.numel()
     if out is None:
         out = torch.zeros((H0, W0), dtype=torch.uint8, device=s.device)
@@ -1269,18 +1271,18 @@ def restore_plane_u8(plane, y_ofs, x_ofs, *, out=None):
         raise ValueError("restore_plane_u8: out must be a contiguous uint8 [%d,%d] tensor on the plane's device" % (H0, W0))
     if H0 == 0 or W0 == 0:
         return out
-    check(lib().upsnet_restore_plane_u8(stream(), ptr(s), int(s.stride(0)), H, W, ptr(ys), H0, ptr(xs), W0, ptr(out)), "restore_plane_u8")
+    check(lib().upsnet_restore_plane_u8(stream(), ptr_unaligned(s), int(s.stride(0)), H, W, ptr(ys), H0, ptr(xs), W0, ptr(out)), "restore_plane_u8")
     return out
 
 
 def unified_pan_result(pan, seg, cls_inds, id_last_stuff, num_seg_classes, stuff_area_limit=4 * 64 * 64):
     """get_unified_pan_result of ONE image on the device: pan / seg int64 [H,W] (or [1,H,W]), cls_inds int64 [k] -> uint8 [H,W,3]."""
     require_cuda(pan, seg)
-    pan = pan.reshape(pan.shape[-2], pan.shape[-1]).to(torch.int64).contiguous()
-    seg = seg.reshape(seg.shape[-2], seg.shape[-1]).to(torch.int64).contiguous()
+    pan = i64c(pan.reshape(pan.shape[-2], pan.shape[-1]))
+    seg = i64c(seg.reshape(seg.shape[-2], seg.shape[-1]))
     if pan.shape != seg.shape:
         raise RuntimeError("unified_pan_result: pan %s and seg %s differ in shape" % (tuple(pan.shape), tuple(seg.shape)))
-    cls_inds = cls_inds.to(device=pan.device, dtype=torch.int64).contiguous().reshape(-1)
+    cls_inds = i64c(cls_inds.to(device=pan.device)).reshape(-1)
     H, W = pan.shape
     ws = torch.empty((int(lib().upsnet_unified_pan_workspace_bytes()),), dtype=torch.uint8, device=pan.device)
     out = torch.empty((H, W, 3), dtype=torch.uint8, device=pan.device)
@@ -1340,7 +1342,7 @@ def combined_pan_result(segs, boxes, masks, id_last_stuff, score_threshold=0.6, 
         r = torch.stack([torch.stack([t.min(), t.max()]).to(torch.int64) for t in wide]).cpu()
         if int(r[:, 0].min()) < 0 or int(r[:, 1].max()) > 255:
             raise ValueError("combined_pan_result: semantic labels must be integers in 0..255")
-    seg_t = [t.to(torch.uint8).contiguous() for t in seg_t]
+    seg_t = [dense(t.to(torch.uint8)) for t in seg_t]
     thr = float(score_threshold)
     strings, cls_of, npix_of, img_ncand = [], [], [], []
     for i, t in enumerate(seg_t):
@@ -1478,8 +1480,9 @@ def pq_accumulate(pred_2ch, gt_rgb, segments, cat_known, image_index, max_gt, wo
                      (iou, torch.float64, 256), (status, torch.int64, 1)):
         if t.dtype != dt or t.numel() != n or not t.is_contiguous():
             raise ValueError("pq_accumulate: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
+        written(t, dt, "pq_accumulate: accumulator / table")
     written(workspace, None, "pq_accumulate: workspace")
-    pred_2ch, gt_rgb, segments = pred_2ch.contiguous(), gt_rgb.contiguous(), segments.contiguous()
+    pred_2ch, gt_rgb, segments = dense(pred_2ch), dense(gt_rgb), dense(segments)
     H, W = pred_2ch.shape[:2]
     check(lib().upsnet_pq_accumulate(stream(), ptr(pred_2ch), ptr(gt_rgb), H, W, ptr(segments) if segments.numel() else None,
                                      int(segments.shape[0]), ptr(cat_known), int(image_index), int(max_gt), ptr(workspace), ptr(tp), ptr(fp),
@@ -1510,6 +1513,7 @@ def pq_boundary_accumulate(dilation, pred_2ch, gt_rgb, segments, cat_known, imag
                      (iou, torch.float64, 256), (status, torch.int64, 1)):
         if t.dtype != dt or t.numel() != n or not t.is_contiguous():
             raise ValueError("pq_boundary_accumulate: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
+        written(t, dt, "pq_boundary_accumulate: accumulator / table")
     if int(dilation) < 1:
         raise ValueError("pq_boundary_accumulate: dilation %d < 1" % dilation)
     H, W = pred_2ch.shape[:2]
@@ -1517,7 +1521,8 @@ def pq_boundary_accumulate(dilation, pred_2ch, gt_rgb, segments, cat_known, imag
     if need == 0 or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
         raise ValueError("pq_boundary_accumulate: a uint8 workspace of at least %d bytes expected for max_gt %d and %dx%d, got %s %s"
                          % (need, max_gt, H, W, tuple(workspace.shape), workspace.dtype))
-    pred_2ch, gt_rgb, segments = pred_2ch.contiguous(), gt_rgb.contiguous(), segments.contiguous()
+    written(workspace, torch.uint8, "pq_boundary_accumulate: workspace")     # (64-bit counters are carved from it at 16-byte steps)
+    pred_2ch, gt_rgb, segments = dense(pred_2ch), dense(gt_rgb), dense(segments)
     check(lib().upsnet_pq_boundary_accumulate(stream(), int(dilation), ptr(pred_2ch), ptr(gt_rgb), H, W,
                                               ptr(segments) if segments.numel() else None, int(segments.shape[0]), ptr(cat_known),
                                               int(image_index), int(max_gt), ptr(workspace), ptr(tp), ptr(fp), ptr(fn), ptr(iou), ptr(status)),
@@ -1552,10 +1557,11 @@ def pan_boundary_map(dilation, pred_2ch, gt_rgb, workspace, out):
     if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
         raise ValueError("pan_boundary_map: a uint8 workspace of at least %d bytes expected, got %s %s"
                          % (nbytes, tuple(workspace.shape), workspace.dtype))
+    written(workspace, torch.uint8, "pan_boundary_map: workspace")
     if out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or not out.is_contiguous():
         raise ValueError("pan_boundary_map: out must be a contiguous uint8 [%d,%d], got %s %s" % (H, W, tuple(out.shape), out.dtype))
-    pred_2ch = pred_2ch.contiguous() if pred_2ch is not None else None
-    gt_rgb = gt_rgb.contiguous() if gt_rgb is not None else None
+    written(out, torch.uint8, "pan_boundary_map: out")
+    pred_2ch, gt_rgb = dense(pred_2ch), dense(gt_rgb)
     with torch.cuda.device(out.device):
         check(lib().upsnet_pan_boundary_map(stream(), int(dilation), ptr(pred_2ch) if pred_2ch is not None else None,
                                             ptr(gt_rgb) if gt_rgb is not None else None, H, W, ptr(workspace), ptr(out)), "pan_boundary_map")
@@ -1572,7 +1578,8 @@ def confusion_accumulate(gt_label, pred_label, class_num, ignore_label, confusio
                          % (tuple(gt_label.shape), gt_label.dtype, tuple(pred_label.shape), pred_label.dtype))
     if confusion.dtype != torch.int64 or tuple(confusion.shape) != (class_num, class_num) or not confusion.is_contiguous():
         raise ValueError("confusion_accumulate: confusion must be a contiguous int64 [%d,%d] tensor" % (class_num, class_num))
-    gt_label, pred_label = gt_label.contiguous(), pred_label.contiguous()
+    written(confusion, torch.int64, "confusion_accumulate: confusion")
+    gt_label, pred_label = dense(gt_label), dense(pred_label)
     check(lib().upsnet_confusion_accumulate(stream(), ptr(gt_label), ptr(pred_label), int(gt_label.numel()), int(class_num),
                                             int(ignore_label), ptr(confusion)), "confusion_accumulate")
     return confusion
@@ -1792,7 +1799,7 @@ def conv2d_nhwc_bf16_multi(xs, whi, wlo, ldw, bias, cout, ksize, stride, pad, re
     Plain bf16 mode only: inputs / residuals may be torch.bfloat16 tensors (all maps of a launch alike) and out_dtype may be
     torch.bfloat16 -- bf16 activations between layers (the kernels then load / store 2-byte elements, no conversion pass)."""
     require_cuda(whi, *xs)
-    whi, wlo = whi.contiguous(), None if wlo is None else wlo.contiguous()
+    whi, wlo = dense(whi), dense(wlo)
     assert 1 <= len(xs) <= 5
     in16 = xs[0].dtype == torch.bfloat16
     out16 = out_dtype == torch.bfloat16
@@ -1879,7 +1886,7 @@ def bottleneck_proj_bf16(x, pack, stride):
     """relu(conv3(relu(conv2(relu(conv1_s(x))))) + proj_s(x)) of a stage's first bottleneck in one launch; x, result: bf16 channels_last."""
     w1, w2, w3d, b1, b2, b3d, cm, cin = pack
     require_cuda(x, w1)
-    w1, w2, w3d, b1, b2, b3d = w1.contiguous(), w2.contiguous(), w3d.contiguous(), f32c(b1), f32c(b2), f32c(b3d)
+    w1, w2, w3d, b1, b2, b3d = dense(w1), dense(w2), dense(w3d), f32c(b1), f32c(b2), f32c(b3d)
     if x.dtype != torch.bfloat16 or x.shape[1] != cin:
         raise RuntimeError("bottleneck_proj_bf16: expects a bf16 map of %d channels" % cin)
     x = nhwc(x)
@@ -1899,7 +1906,7 @@ def bottleneck_bf16(x, pack):
     """relu(conv3(relu(conv2(relu(conv1(x))))) + x) of an identity bottleneck in one launch; x, result: bf16 NHWC-strided NCHW."""
     w1, w2, w3, b1, b2, b3, cm = pack
     require_cuda(x, w1)
-    w1, w2, w3, b1, b2, b3 = w1.contiguous(), w2.contiguous(), w3.contiguous(), f32c(b1), f32c(b2), f32c(b3)
+    w1, w2, w3, b1, b2, b3 = dense(w1), dense(w2), dense(w3), f32c(b1), f32c(b2), f32c(b3)
     if x.dtype != torch.bfloat16 or x.shape[1] != 4 * cm:
         raise RuntimeError("bottleneck_bf16: expects a bf16 map of %d channels" % (4 * cm))
     x = nhwc(x)
@@ -1962,12 +1969,12 @@ def proposal_recall(problems, proposals, gt_boxes, max_gt, total_proposals, work
     if not 0 <= int(max_gt) <= PROPOSAL_RECALL_MAX_GT:
         raise ValueError("proposal_recall: %d GT boxes in a problem (at most %d)" % (int(max_gt), PROPOSAL_RECALL_MAX_GT))
     n = int(problems.shape[0])
+    problems, proposals, gt_boxes = aligned(problems), aligned(proposals), aligned(gt_boxes)
     written(workspace, None, "proposal_recall: workspace")
     if workspace.numel() * workspace.element_size() < proposal_recall_workspace_bytes(n, total_proposals):
         raise ValueError("proposal_recall: workspace of %d bytes, %d needed" % (workspace.numel() * workspace.element_size(),
                                                                              proposal_recall_workspace_bytes(n, total_proposals)))
-    if out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("proposal_recall: out must be contiguous float32")
+    written(out, torch.float32, "proposal_recall: out")
     check(lib().upsnet_proposal_recall(stream(), n, ptr(problems), ptr(proposals), ptr(gt_boxes), int(max_gt), int(total_proposals),
                                        ptr(workspace), ptr(out)), "proposal_recall")
     return out
@@ -2085,6 +2092,7 @@ def _pan_track_step(what, pan_2ch, iou_thresh, max_age, frame, workspace, memory
                 or not host_table.is_contiguous():
             raise ValueError("pan_track_step: host_table must be contiguous pinned int32 host memory of at least 8 ints")
         host_rows = (host_table.numel() - 8) // 8
+    pan_2ch = aligned(pan_2ch)
     args = (stream(), ptr(pan_2ch), H, W, float(iou_thresh), int(max_age), int(frame), ptr(workspace), ptr(memory), ptr(out),
             ptr(host_table), host_rows)
     if motion_workspace is None:
@@ -2106,7 +2114,7 @@ def pan_stable_colors(pred_2ch, cat_table, mode, out):
     H, W = int(pred_2ch.shape[0]), int(pred_2ch.shape[1])
     if out.dtype != torch.uint8 or out.numel() != H * W * 3 or not out.is_contiguous():
         raise ValueError("pan_stable_colors: out must be a contiguous uint8 tensor of %d bytes" % (H * W * 3))
-    cat_table = i32c(cat_table)
+    cat_table, pred_2ch = i32c(cat_table), aligned(pred_2ch)
     check(lib().upsnet_pan_stable_colors(stream(), ptr(pred_2ch), H, W, ptr(cat_table), int(mode), ptr(out)), "pan_stable_colors")
     return out
 
@@ -2197,6 +2205,7 @@ def _pan_clean(name, workspace_bytes, entry, nstats, pan_2ch, min_area, connecti
         if labels is None and want_labels:
             labels = torch.zeros((H, W), dtype=torch.int32, device=dev)
         stats = torch.zeros((nstats,), dtype=torch.int32, device=dev)
+        pan_2ch = aligned(pan_2ch)
         check(entry(stream(), ptr(pan_2ch), H, W, int(connectivity), int(min_area), int(bool(keep_largest)), ptr(workspace), ptr(out),
                     ptr(labels), ptr(stats)), name)
     return out, stats, labels
@@ -2238,6 +2247,7 @@ def pan_segment_scores(pan_2ch, conf, *, workspace=None, table=None):
             workspace = torch.zeros((need,), dtype=torch.uint8, device=dev)
         if table is None:
             table = torch.zeros((nints,), dtype=torch.int32, device=dev)
+        pan_2ch, conf = aligned(pan_2ch), aligned(conf)
         check(lib().upsnet_pan_segment_scores(stream(), ptr(pan_2ch), ptr(conf), H, W, ptr(workspace), ptr(table)), "pan_segment_scores")
     return table
 
@@ -2257,6 +2267,7 @@ def pan_score_filter(pan_2ch, table, min_score, *, out=None):
     with torch.cuda.device(pan_2ch.device):
         if out is None:
             out = pan_2ch.clone()
+        pan_2ch, table = aligned(pan_2ch), aligned(table)
         check(lib().upsnet_pan_score_filter(stream(), ptr(pan_2ch), H, W, ptr(table), float(min_score), ptr(out)), "pan_score_filter")
     return out
 
@@ -2276,6 +2287,7 @@ def _video_eval_check_workspace(what, workspace, max_gt, H, W, max_window):
     if need == 0 or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
         raise ValueError("%s: workspace too small for (or no workspace exists for) max_gt %d, a frame of %d x %d and max_window %d"
                          % (what, max_gt, H, W, max_window))
+    written(workspace, torch.uint8, what + ": workspace")
 
 
 def video_eval_frame(pred_2ch, gt_rgb, table, num_rows, num_crowd, max_gt, windows, frame, sequence, cat_known, workspace, tp, fp, fn,
@@ -2301,7 +2313,8 @@ def video_eval_frame(pred_2ch, gt_rgb, table, num_rows, num_crowd, max_gt, windo
                      (iou, torch.float64, nw * 256), (status, torch.int64, 2)):
         if t.dtype != dt or t.numel() != n or not t.is_contiguous():
             raise ValueError("video_eval_frame: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
-    pred_2ch, gt_rgb = pred_2ch.contiguous(), gt_rgb.contiguous()
+        written(t, dt, "video_eval_frame: accumulator / table")
+    pred_2ch, gt_rgb = dense(pred_2ch), dense(gt_rgb)
     H, W = int(pred_2ch.shape[0]), int(pred_2ch.shape[1])
     _video_eval_check_workspace("video_eval_frame", workspace, max_gt, H, W, windows[-1])
     check(lib().upsnet_video_eval_frame(stream(), ptr(pred_2ch), ptr(gt_rgb), H, W, ptr(table) if table.numel() else None, num_rows, num_crowd,
@@ -2317,6 +2330,7 @@ def video_eval_end(height, width, max_gt, max_window, workspace, sequence_out, h
     ints = int(lib().upsnet_video_eval_sequence_ints())
     if sequence_out.dtype != torch.int32 or sequence_out.numel() != ints or not sequence_out.is_contiguous():
         raise ValueError("video_eval_end: sequence_out must be contiguous int32 of %d ints, got %s %s" % (ints, tuple(sequence_out.shape), sequence_out.dtype))
+    written(sequence_out, torch.int32, "video_eval_end: sequence_out")
     if host_out is not None and (host_out.is_cuda or not host_out.is_pinned() or host_out.dtype != torch.int32 or host_out.numel() != ints
                                  or not host_out.is_contiguous()):
         raise ValueError("video_eval_end: host_out must be contiguous pinned int32 host memory of %d ints" % ints)
@@ -2338,6 +2352,7 @@ def _mots_eval_check(what, workspace, table, num_rows, max_gt, H, W):
     need = int(lib().upsnet_mots_eval_workspace_bytes(int(max_gt), H, W))
     if need == 0 or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
         raise ValueError("%s: workspace too small for (or no workspace exists for) max_gt %d and a frame of %d x %d" % (what, max_gt, H, W))
+    written(workspace, torch.uint8, what + ": workspace")
     if table.dtype != torch.int32 or not table.is_contiguous() or table.numel() != 2 * num_rows or not 0 <= num_rows <= max_gt:
         raise ValueError("%s: table must be contiguous int32 of 2 * %d ints with at most max_gt %d rows, got %s %s"
                          % (what, num_rows, max_gt, tuple(table.shape), table.dtype))
@@ -2357,7 +2372,8 @@ def mots_eval_frame(pred_2ch, gt_rgb, table, num_rows, max_gt, frame, sequence, 
     for t, dt, n in ((cat_info, torch.uint8, 256), (counts, torch.int64, 7 * 256), (soft, torch.float64, 256), (status, torch.int64, 2)):
         if t.dtype != dt or t.numel() != n or not t.is_contiguous():
             raise ValueError("mots_eval_frame: accumulator / table of %d %s expected, got %s %s" % (n, dt, tuple(t.shape), t.dtype))
-    pred_2ch, gt_rgb = pred_2ch.contiguous(), gt_rgb.contiguous()
+        written(t, dt, "mots_eval_frame: accumulator / table")
+    pred_2ch, gt_rgb = dense(pred_2ch), dense(gt_rgb)
     H, W = int(pred_2ch.shape[0]), int(pred_2ch.shape[1])
     _mots_eval_check("mots_eval_frame", workspace, table, num_rows, max_gt, H, W)
     check(lib().upsnet_mots_eval_frame(stream(), ptr(pred_2ch), ptr(gt_rgb), H, W, ptr(table) if table.numel() else None, num_rows, int(max_gt),
@@ -2371,6 +2387,7 @@ def mots_eval_end(height, width, table, num_rows, max_gt, workspace, mtl):
     require_cuda(table, workspace, mtl)
     if mtl.dtype != torch.int64 or mtl.numel() != 3 * 256 or not mtl.is_contiguous():
         raise ValueError("mots_eval_end: mtl must be contiguous int64 of 768 words, got %s %s" % (tuple(mtl.shape), mtl.dtype))
+    written(mtl, torch.int64, "mots_eval_end: mtl")
     num_rows = int(num_rows)
     _mots_eval_check("mots_eval_end", workspace, table, num_rows, max_gt, int(height), int(width))
     check(lib().upsnet_mots_eval_end(stream(), int(height), int(width), ptr(table) if table.numel() else None, num_rows, int(max_gt),
@@ -2392,4 +2409,5 @@ def pan_rle_transitions(pan_2ch, pairs, count):
         raise ValueError("pan_rle_transitions: pairs must be contiguous int64 [cap] and count int32 [1], got %s %s and %s %s"
                          % (tuple(pairs.shape), pairs.dtype, tuple(count.shape), count.dtype))
     cap = int(pairs.numel())
+    pan_2ch = aligned(pan_2ch)
     check(lib().upsnet_pan_rle_transitions(stream(), ptr(pan_2ch), H, W, cap, ptr(pairs) if cap else None, ptr(count)), "pan_rle_transitions")

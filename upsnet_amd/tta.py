@@ -25,7 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from ._lib import check, f32c, float_array, int_array, lib, nhwc, ptr, ptr_array, require_cuda, stream
+from ._lib import aligned, check, dense, f32c, float_array, int_array, lib, nhwc, ptr, ptr_array, require_cuda, stream
 from .config.config import config
 from .operators.modules.mask_roi import check_count, check_count_soft
 
@@ -72,6 +72,7 @@ def roi_union(rois, delta, prob, num_rois_dev, r, resized_w, flip):
                              % (a, tuple(rois[a].shape), tuple(delta[a].shape), tuple(prob[a].shape), (R, 5), (R, D), (R, C)))
         if num_rois_dev[a].dtype != torch.int32 or num_rois_dev[a].numel() != 1:
             raise ValueError("tta_roi_union: the count of augmentation %d must be one int32" % a)
+    num_rois_dev = [dense(t) for t in num_rois_dev]
     if A * R > 8192:
         raise ValueError("tta_roi_union: %d x %d rows exceed the 8192 the detection selection takes" % (A, R))
     dev = rois[0].device
@@ -79,7 +80,7 @@ def roi_union(rois, delta, prob, num_rois_dev, r, resized_w, flip):
     delta_out = torch.empty((A * R, D), dtype=torch.float32, device=dev)
     prob_out = torch.empty((A * R, C), dtype=torch.float32, device=dev)
     num = torch.empty((1,), dtype=torch.int32, device=dev)
-    check(lib().upsnet_tta_roi_union(stream(), A, ptr_array(rois), ptr_array(delta), ptr_array(prob), ptr_array(list(num_rois_dev)),
+    check(lib().upsnet_tta_roi_union(stream(), A, ptr_array(rois), ptr_array(delta), ptr_array(prob), ptr_array(num_rois_dev),
                                      float_array(r), float_array(resized_w), int_array([bool(f) for f in flip]), R, D, C,
                                      ptr(rois_out), ptr(delta_out), ptr(prob_out), ptr(num)), "tta_roi_union")
     return rois_out, delta_out, prob_out, num
@@ -112,7 +113,7 @@ def mask_merge(logits, flip):
         raise ValueError("tta_mask_merge: square masks expected, got %s" % (tuple(first.shape),))
     is_nhwc = (not first.is_contiguous()) and first.is_contiguous(memory_format=torch.channels_last)
     fmt = torch.channels_last if is_nhwc else torch.contiguous_format
-    logits = [t.float().contiguous(memory_format=fmt) for t in logits]
+    logits = [aligned(t.float().contiguous(memory_format=fmt)) for t in logits]
     for t in logits:
         if tuple(t.shape) != (n, C, ms, ms):
             raise ValueError("tta_mask_merge: shapes differ: %s and %s" % (tuple(t.shape), (n, C, ms, ms)))
@@ -129,7 +130,7 @@ def box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_th
     voted [cap,5]: row k < num is the mean of the class-cls[k] candidates with cls_prob > vote_score_thresh and IoU >= vote_iou_thresh
     with boxes[k], weighted by cls_prob; rows from num on are copies. One launch, no host read."""
     require_cuda(rois, bbox_delta, cls_prob, im_info, boxes, cls, num)
-    rois, bbox_delta, cls_prob, boxes, cls = f32c(rois), f32c(bbox_delta), f32c(cls_prob), f32c(boxes), cls.contiguous()
+    rois, bbox_delta, cls_prob, boxes, cls = f32c(rois), f32c(bbox_delta), f32c(cls_prob), f32c(boxes), dense(cls)
     N, C = cls_prob.shape
     cap = boxes.shape[0]
     if tuple(rois.shape) != (N, 5) or bbox_delta.dim() != 2 or tuple(bbox_delta.shape) != (N, 4 * C):
@@ -139,6 +140,7 @@ def box_vote(rois, bbox_delta, cls_prob, im_info, boxes, cls, num, vote_score_th
         raise ValueError("box_vote: boxes must be [cap,5] and cls int64 [cap], got %s and %s %s" % (tuple(boxes.shape), cls.dtype, tuple(cls.shape)))
     if num.dtype != torch.int32 or num.numel() != 1 or (num_rois_dev is not None and (num_rois_dev.dtype != torch.int32 or num_rois_dev.numel() != 1)):
         raise ValueError("box_vote: the counts must be one int32 each")
+    num, num_rois_dev = dense(num), dense(num_rois_dev)
     voted = torch.empty((cap, 5), dtype=torch.float32, device=boxes.device)
     im_info = f32c(im_info.reshape(-1))
     check(lib().upsnet_box_vote(stream(), ptr(rois), ptr(bbox_delta), ptr(cls_prob), N, ptr(num_rois_dev), C,
@@ -167,6 +169,7 @@ def mask_roi_soft(rois, bbox_delta, cls_prob, im_info, score_thresh, nms_thresh,
                          % (tuple(rois.shape), tuple(bbox_delta.shape), (N, C)))
     if num_rois_dev is not None and (num_rois_dev.dtype != torch.int32 or num_rois_dev.numel() != 1):
         raise ValueError("mask_roi_soft: the row count must be one int32")
+    num_rois_dev = dense(num_rois_dev)
     dev = rois.device
     cap = lib().upsnet_mask_roi_capacity(max(N, 1), max(C, 2), 0)
     boxes = torch.empty((cap, 5), dtype=torch.float32, device=dev)
